@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- the hot path on MI355X (BASELINE.json metric), one JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg1|cfg2|cfg3|cfg4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg1|cfg2|cfg3|cfg4] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, higher_is_better,
+dtype, ms_per_step and the settle / host-stall bookkeeping).  --full adds everything else the line used to carry:
+per-kernel times and rooflines, the measured HBM peak, the idle-ramp figure, the exchange timings of N > 1, the
+total-variation pass, and at cfg1 N = 1 the cfg2 block and the CPU baseline.  --dump-outputs DIR writes what the last
+timed step computed (image, radii, gradients; cfg3/cfg4: loss, image, parameters after Adam) as DIR/<name>.npy; the inputs
+are seeded, so two builds can be compared output for output.
 
 --config (default cfg1) names the BASELINE.json configuration:
   cfg1  configs[1]: 1M synthetic Gaussians, 1 view 1920x1080 per GPU, GaussianRasterizer forward+backward.  One
@@ -40,6 +47,7 @@ import subprocess
 import sys
 import time
 import types
+import zlib
 
 import numpy as np
 import torch
@@ -356,6 +364,35 @@ def exposed_exchange(step, state, steps, ms_with, ms_alone, dev):
             "note": "without = the same steps with the gradient exchange skipped (timed after the headline region)"}
 
 
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def seeded_index(name, n, k, dev):
+    """k of n positions, sorted, drawn with a seed derived from `name`: the same sample in every run and every build."""
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    return torch.as_tensor(np.sort(rng.choice(n, size=k, replace=False)), device=dev)
+
+
+def dump_outputs(path, whole=None, rows=None, elems=None, k_rows=1 << 18, k_elems=1 << 16):
+    """--dump-outputs DIR: what the timed path handed its caller in its last step, as DIR/<name>.npy in float32 (integer
+    outputs such as radii convert exactly).  `whole`: written as they are; `rows`: per-Gaussian arrays, a fixed seeded
+    sample of k_rows rows when longer; `elems`: parameters of any shape, a fixed seeded sample of k_elems elements of the
+    flattened tensor when larger.  At most DUMP_MAX_BYTES in all."""
+    arrays = dict(whole or {})
+    for name, t in (rows or {}).items():
+        arrays[name] = t[seeded_index(name, t.shape[0], k_rows, t.device)] if t.shape[0] > k_rows else t
+    for name, t in (elems or {}).items():
+        t = t.reshape(-1)
+        arrays[name] = t[seeded_index(name, t.numel(), k_elems, t.device)] if t.numel() > k_elems else t
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total / 2**20:.1f} MiB of outputs, more than {DUMP_MAX_BYTES / 2**20:.0f} MiB")
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def pick_dominant(warm_prof):
     kern = {k: ms / n for k, (ms, n) in warm_prof.items() if n}
     per_step = {k: ms for k, (ms, n) in warm_prof.items() if n}
@@ -574,16 +611,17 @@ def run_cfg1(args, rank, world, dev):
         for shp in ("all_reduce", "rs_ag"):
             shapes_ms[shp] = time_allreduce(lambda: allreduce_gradients(leaves, agree="once", shape=shp), dev, reps=3)
         state["shape"] = min(shapes_ms, key=shapes_ms.get)
-    # warm-up: the last warm-up steps are timed per kernel class (HIP events around every launch)
+    # warm-up.  --full: the last warm-up steps are timed per kernel class (HIP events around every launch)
     # to find the dominant kernel; the timed region then brackets ONLY that class, because each
     # event pair costs a few microseconds of stream time.
     for w in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # three more untimed steps with every launch bracketed (the per-class table), at the clocks the chip holds under load
     clock_settle, warm_prof = 0, {}
     if args.warmup:
         clock_settle = settle_clocks(step, world, dev)
+    if args.warmup and args.full:
+        # three more untimed steps with every launch bracketed (the per-class table), at the clocks the chip holds under load
         _C.profile_enable(True)
         _C.profile_read()
         for _ in range(3):
@@ -591,10 +629,11 @@ def run_cfg1(args, rank, world, dev):
         torch.cuda.synchronize()
         warm_prof = _C.profile_read()
     dominant, warm_kern = pick_dominant(warm_prof)
-    # the dominant class is timed inside the timed region on every 4th step only: an event pair costs ~6 us of stream time
-    # on each side of the launch it brackets (1 % of a cfg1 step); the average is over ceil(K / 4) launches
-    _C.profile_enable(dominant, every=4 if args.steps >= 8 else 1)
-    _C.profile_read()
+    if args.full:
+        # the dominant class is timed inside the timed region on every 4th step only: an event pair costs ~6 us of stream
+        # time on each side of the launch it brackets (1 % of a cfg1 step); the average is over ceil(K / 4) launches
+        _C.profile_enable(dominant, every=4 if args.steps >= 8 else 1)
+        _C.profile_read()
     # the interpreter's cyclic collector is parked for the timed region: a generation-2 pass over this process's objects takes
     # milliseconds, and one of them inside 20 steps of 1 ms is a quarter of a millisecond per step (seen once in round 5:
     # 1.28 ms per step with the kernels summing to 1.06 -- profiles/HISTORY.md).  Nothing is skipped.
@@ -617,35 +656,40 @@ def run_cfg1(args, rank, world, dev):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    prof = _C.profile_read()
-    # Straight behind the timed region, same process, same clocks (no host pause in between): K more steps with EVERY kernel
-    # class bracketed by HIP events on every launch -- the per-class table and its sum (`kernel_sum_ms`) beside this run's own
-    # `ms_per_step`.  Each event pair costs ~6 us of stream time on both sides of its launch, which is why these steps are
-    # not the timed ones; the kernels' own durations are not affected.
-    _C.profile_enable(True)
-    same_run = {}
-    if args.steps:
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        same_run = {k: ms / n for k, (ms, n) in _C.profile_read().items() if n}
-    _C.profile_enable(False)
-    # ... and what the same K steps take when the chip has idled first (50 ms: the clocks have dropped, profiles/r05_clock_ramp.txt):
-    # the figure a caller sees who renders now and then, next to the sustained one a training loop sees
-    ramp_ms = None
-    if args.steps and args.warmup:
-        time.sleep(0.05)
-        tr0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        ramp_ms = (time.perf_counter() - tr0) / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # the last timed step's image, radii and gradients (after the exchange when N > 1), before anything runs again
+        dump_outputs(args.dump_outputs, whole={"image": state["img"]},
+                     rows={"radii": state["radii"], **{"grad_" + n: p.grad for n, p in params.items()}, "grad_means2D": means2D.grad})
+    prof = _C.profile_read() if args.full else {}
+    same_run, ramp_ms = {}, None
+    if args.full:
+        # Straight behind the timed region, same process, same clocks (no host pause in between): K more steps with EVERY
+        # kernel class bracketed by HIP events on every launch -- the per-class table and its sum (`kernel_sum_ms`) beside this
+        # run's own `ms_per_step`.  Each event pair costs ~6 us of stream time on both sides of its launch, which is why these
+        # steps are not the timed ones; the kernels' own durations are not affected.
+        _C.profile_enable(True)
+        if args.steps:
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            same_run = {k: ms / n for k, (ms, n) in _C.profile_read().items() if n}
+        _C.profile_enable(False)
+        # ... and what the same K steps take when the chip has idled first (50 ms: the clocks have dropped, profiles/r05_clock_ramp.txt):
+        # the figure a caller sees who renders now and then, next to the sustained one a training loop sees
+        if args.steps and args.warmup:
+            time.sleep(0.05)
+            tr0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            ramp_ms = (time.perf_counter() - tr0) / args.steps * 1e3
     gc.enable()
     allreduce_info, exposed = None, None
     if world > 1:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if world > 1 and args.full:
         # bookkeeping (outside the timed region): the gradient all-reduce on its own, SURVEY.md 8(e)
         shp = state.get("shape", "all_reduce")
         bucket = allreduce_gradients(leaves, agree="once", shape=shp)
@@ -656,52 +700,58 @@ def run_cfg1(args, rank, world, dev):
         exposed = exposed_exchange(step, state, args.steps, elapsed / args.steps * 1e3, ms, dev)
     if rank != 0:
         return None
-    with torch.no_grad():
-        _, _, st = R.rasterize_forward(R._CSettings(rast.raster_settings), params["means3D"].detach(),
-                                       params["opacities"].detach(), params["scales"].detach(),
-                                       params["rotations"].detach(), None, None, params["colors_precomp"].detach())
-    I, npix = st.I, W * H
-    kern = dict(warm_kern)                                   # all classes: from the warm-up steps ...
-    kern.update(same_run)                                    # ... replaced by the K bracketed steps behind the timed region
-    kern.update({k: (ms / max(n, 1)) for k, (ms, n) in prof.items() if n})   # dominant: timed region
-    peak = hbm_copy_peak(dev)
-    ab = algorithmic_bytes(dominant, P, I, npix)
+    developer_scene = args.scene != "uniform" or args.sigma_scale != 1.0
     out = {
         "metric": METRIC, "value": world * P / (elapsed / args.steps) / 1e6, "unit": "Msplats/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "clock_settle_steps": clock_settle,      # untimed, after the W warm-up steps: see settle_clocks()
-        # EVERY untimed step before the timed region: the W asked for + the clock-settling blocks + the three bracketed ones
-        "effective_warmup_steps": args.warmup + clock_settle + (3 if args.warmup else 0),
-        # the same K steps after 50 ms of idling (clocks dropped), measured behind the timed region; `ms_per_step` is the sustained figure
-        "ramp_ms_per_step": None if ramp_ms is None else round(ramp_ms, 4),
-        # sum of the per-class kernel times of THIS run (K steps straight behind the timed region, every launch bracketed) beside
-        # this run's wall time per step: the difference is launch gaps and host-side time, not another box
-        "kernel_sum_ms": round(sum(same_run.values()), 4) if same_run else None,
+        # EVERY untimed step before the timed region: the W asked for + the clock-settling blocks (+ the three bracketed ones of --full)
+        "effective_warmup_steps": args.warmup + clock_settle + (3 if args.warmup and args.full else 0),
         # when each step's calls RETURNED to the host, as differences (no synchronisation involved): a host-side stall shows here
         "host_step_ms": {"median": round(1e3 * float(np.median(np.diff([t0] + host_ms))), 4), "max": round(1e3 * float(np.max(np.diff([t0] + host_ms))), 4)},
         "config": {"workload": "cfg1: 1M synthetic Gaussians (seed 0), 1 view 1920x1080 per GPU, "
                                "GaussianRasterizer forward+backward, colors_precomp + scale/rotation path",
-                   "gaussians": P, "image": f"{W}x{H}", "tile_instances": I,
+                   "gaussians": P, "image": f"{W}x{H}",
                    "visible": int((state["radii"] > 0).sum().item()),
                    "parallelism": "1 view per GPU (mv sharding)" + (
                        f", RCCL all-reduce(SUM) of {P}x14 fp32 per-Gaussian grads per step" if world > 1 else "")},
-        "roofline": roofline_object(dominant, kern[dominant], ab, peak,
-                                    "blend kernels are FP32-VALU/exp-issue bound at this density (SURVEY.md 8d); "
-                                    "the HBM fraction is reported as the contract asks"),
-        "kernel_ms": {k: round(v, 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1])},
-        "kernel_ms_source": f"{dominant}: HIP events inside the timed region (every 4th step); the other classes: HIP events around "
-                            "every launch of K untimed steps straight behind the timed region (same clocks), each pair adding ~6 us of "
-                            "stream time on both sides of its launch -- the kernels' own durations are not affected; ms_per_step is "
-                            "wall time over K undisturbed steps",
-        "hbm_gbs_all_kernels": sum(algorithmic_bytes(k, P, I, npix) for k in kern) / (sum(kern.values()) * 1e-3) / 1e9,
-        # every kernel class against ITS byte model, from the per-launch times above
-        "kernel_rooflines": {k: {"ms": round(ms, 4), "algorithmic_MB": round(algorithmic_bytes(k, P, I, npix) / 1e6, 1),
-                                 "GBps": round(algorithmic_bytes(k, P, I, npix) / (ms * 1e-3) / 1e9, 1),
-                                 "frac_of_8TBps": round(algorithmic_bytes(k, P, I, npix) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 3),
-                                 "frac_of_measured_peak": round(algorithmic_bytes(k, P, I, npix) / (ms * 1e-3) / 1e9 / peak, 3)}
-                             for k, ms in sorted(kern.items(), key=lambda kv: -kv[1]) if ms > 0},
     }
+    if args.full or developer_scene:
+        with torch.no_grad():
+            _, _, st = R.rasterize_forward(R._CSettings(rast.raster_settings), params["means3D"].detach(),
+                                           params["opacities"].detach(), params["scales"].detach(),
+                                           params["rotations"].detach(), None, None, params["colors_precomp"].detach())
+        I, npix = st.I, W * H
+        out["config"]["tile_instances"] = I
+    if args.full:
+        kern = dict(warm_kern)                                   # all classes: from the warm-up steps ...
+        kern.update(same_run)                                    # ... replaced by the K bracketed steps behind the timed region
+        kern.update({k: (ms / max(n, 1)) for k, (ms, n) in prof.items() if n})   # dominant: timed region
+        peak = hbm_copy_peak(dev)
+        ab = algorithmic_bytes(dominant, P, I, npix)
+        out.update({
+            # the same K steps after 50 ms of idling (clocks dropped), measured behind the timed region; `ms_per_step` is the sustained figure
+            "ramp_ms_per_step": None if ramp_ms is None else round(ramp_ms, 4),
+            # sum of the per-class kernel times of THIS run (K steps straight behind the timed region, every launch bracketed) beside
+            # this run's wall time per step: the difference is launch gaps and host-side time, not another box
+            "kernel_sum_ms": round(sum(same_run.values()), 4) if same_run else None,
+            "roofline": roofline_object(dominant, kern[dominant], ab, peak,
+                                        "blend kernels are FP32-VALU/exp-issue bound at this density (SURVEY.md 8d); "
+                                        "the HBM fraction is reported as the contract asks"),
+            "kernel_ms": {k: round(v, 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1])},
+            "kernel_ms_source": f"{dominant}: HIP events inside the timed region (every 4th step); the other classes: HIP events around "
+                                "every launch of K untimed steps straight behind the timed region (same clocks), each pair adding ~6 us of "
+                                "stream time on both sides of its launch -- the kernels' own durations are not affected; ms_per_step is "
+                                "wall time over K undisturbed steps",
+            "hbm_gbs_all_kernels": sum(algorithmic_bytes(k, P, I, npix) for k in kern) / (sum(kern.values()) * 1e-3) / 1e9,
+            # every kernel class against ITS byte model, from the per-launch times above
+            "kernel_rooflines": {k: {"ms": round(ms, 4), "algorithmic_MB": round(algorithmic_bytes(k, P, I, npix) / 1e6, 1),
+                                     "GBps": round(algorithmic_bytes(k, P, I, npix) / (ms * 1e-3) / 1e9, 1),
+                                     "frac_of_8TBps": round(algorithmic_bytes(k, P, I, npix) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 3),
+                                     "frac_of_measured_peak": round(algorithmic_bytes(k, P, I, npix) / (ms * 1e-3) / 1e9 / peak, 3)}
+                                 for k, ms in sorted(kern.items(), key=lambda kv: -kv[1]) if ms > 0},
+        })
     if args.scene != "uniform":
         out["config"]["workload"] += (f" -- DEVELOPER SCENE '{args.scene}': 80 % of the Gaussians in the central eighth of the image "
                                       "(not the headline: longest-tile-first scheduling and the merge-path sort at work)")
@@ -716,21 +766,21 @@ def run_cfg1(args, rank, world, dev):
         out["allreduce"] = allreduce_info
     if exposed is not None:
         out["exchange"] = exposed
-    hip_image = state["img"].detach().cpu().numpy()
-    if world == 1 and not args.no_cfg2 and args.sigma_scale == 1.0 and args.scene == "uniform":
+    hip_image = state["img"].detach().cpu().numpy() if args.full else None
+    if args.full and world == 1 and not args.no_cfg2 and not developer_scene:
         # the largest single-GPU configuration (BASELINE.json configs[2]) measured by the same process, after the headline:
         # cfg1 stays the line's metric / value, cfg2 rides along so that it is timed under the driver's clock too
         del params, leaves, means2D, dL, st
         state.clear()
         torch.cuda.empty_cache()
         sub = argparse.Namespace(**vars(args))
-        sub.config, sub.steps, sub.warmup, sub.anchors = "cfg2", 10, 3, 0
+        sub.config, sub.steps, sub.warmup, sub.anchors, sub.dump_outputs = "cfg2", 10, 3, 0, None
         c2 = run_anchor_config(sub, rank, world, dev)
         out["cfg2"] = {k: c2[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "config", "stages", "roofline",
                                           "kernel_ms_per_step", "peak_mem_GiB", "time_settle_steps")}
         out["cfg2"]["kernel_rooflines"] = {k: {kk: v[kk] for kk in ("ms_per_step", "GBps", "frac_of_measured_peak") if kk in v}
                                            for k, v in c2["kernel_rooflines"].items()}
-    if world == 1 and not args.no_cpu_baseline and args.sigma_scale == 1.0 and args.scene == "uniform":
+    if args.full and world == 1 and not args.no_cpu_baseline and not developer_scene:
         out["cpu_baseline"], out["psnr_match_db"] = cpu_baseline(g, cam, dev, hip_image)
     return out
 
@@ -808,7 +858,7 @@ def run_anchor_config(args, rank, world, dev):
             loss, out, _ = collaborative_step(pc, views, gts, pipe, bg, optimizer=opt, densifier=den, arena=arena,
                                               iteration=stats["iteration"], tv_weight=TV_WEIGHT_A)
             stats["P"], stats["V"] = out["radii"].shape[0], int(out["selection_mask"].numel() // pc.n_offsets)
-            stats["rendered"] = out["radii"]
+            stats["rendered"], stats["img"], stats["loss"] = out["radii"], out["render"], loss
     else:
         target = gts[0]
 
@@ -820,7 +870,7 @@ def run_anchor_config(args, rank, world, dev):
             loss = (out["render"] - target).abs().mean() + 0.01 * scaling_reg(out["scaling"])
             loss.backward()
             stats["P"], stats["V"] = out["radii"].shape[0], int(out["selection_mask"].numel() // pc.n_offsets)
-            stats["rendered"] = out["radii"]
+            stats["rendered"], stats["img"], stats["loss"] = out["radii"], out["render"], loss
 
     if DRY is not None:
         step(); step()                                       # the first exchange agrees on the issue order; the second uses it
@@ -831,13 +881,13 @@ def run_anchor_config(args, rank, world, dev):
         dry_run_report(args, step, rank, world, dev, f"{args.config}: the step of iteration {stats.get('iteration', 0) + 1}")
         return None
     for w in range(args.warmup):
-        if w == max(args.warmup - 2, 0):
+        if w == max(args.warmup - 2, 0) and args.full:     # --full: the last two warm-up steps give the per-class table
             torch.cuda.synchronize()
             _C.profile_enable(True)
             _C.profile_read()
         step()
     torch.cuda.synchronize()
-    warm_prof = _C.profile_read() if args.warmup else {}
+    warm_prof = _C.profile_read() if args.warmup and args.full else {}
     # The anchors move with every Adam step, so the number of visible anchors / kept Gaussians -- and with it the size of
     # every intermediate -- changes from step to step, and torch's caching allocator keeps requesting fresh device memory
     # (hundreds of ms per step on a fresh box) until its pool covers the pattern: at 20 M anchors the pool grows for
@@ -881,10 +931,11 @@ def run_anchor_config(args, rank, world, dev):
     nwarm = min(args.warmup, 2) or 1
     dominant, warm_kern = pick_dominant(warm_prof)
     warm_step_ms = {k: ms / nwarm for k, (ms, n) in warm_prof.items() if n}
-    # the dominant class is timed inside the timed region on every 4th step only: an event pair costs ~6 us of stream time
-    # on each side of the launch it brackets (1 % of a cfg1 step); the average is over ceil(K / 4) launches
-    _C.profile_enable(dominant, every=4 if args.steps >= 8 else 1)
-    _C.profile_read()
+    if args.full:
+        # the dominant class is timed inside the timed region on every 4th step only: an event pair costs ~6 us of stream
+        # time on each side of the launch it brackets (1 % of a cfg1 step); the average is over ceil(K / 4) launches
+        _C.profile_enable(dominant, every=4 if args.steps >= 8 else 1)
+        _C.profile_read()
     # the interpreter's cyclic collector is parked for the timed region: a generation-2 pass over this process's objects takes
     # milliseconds, and one of them inside 20 steps of 1 ms is a quarter of a millisecond per step (seen once in round 5:
     # 1.28 ms per step with the kernels summing to 1.06 -- profiles/HISTORY.md).  Nothing is skipped.
@@ -909,7 +960,14 @@ def run_anchor_config(args, rank, world, dev):
     elapsed = time.perf_counter() - t0
     gc.enable()
     dev_allocs = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - dev_allocs0    # hipMalloc calls inside the timed region (0: the pool covered it)
-    prof = _C.profile_read()
+    if args.dump_outputs and rank == 0:
+        # the last timed step's loss and image; cfg2: the parameter gradients, cfg3/cfg4: the parameters Adam left
+        named = [(n, p) for n, p in pc.named_parameters() if p.requires_grad]
+        dump_outputs(args.dump_outputs,
+                     whole={"image": stats["img"], **({"loss": stats["loss"].reshape(1)} if stats["loss"] is not None else {})},
+                     elems={f"param.{n}": p for n, p in named} if train else
+                           {f"grad.{n}": p.grad for n, p in named if p.grad is not None})
+    prof = _C.profile_read() if args.full else {}
     _C.profile_enable(False)
     Pt = torch.tensor([stats["P"]], device=dev, dtype=torch.float64)
     allreduce_info, exposed = None, None
@@ -918,7 +976,7 @@ def run_anchor_config(args, rank, world, dev):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
         dist.all_reduce(Pt)                                  # Gaussians rasterised by all ranks in one step
-        if train:
+        if train and args.full:
             def exchange(mode):
                 a2 = GradArena(arena.params, mode=mode, overlap=False)
                 ms = time_allreduce(lambda: (a2.zero(), a2.reduce()), dev, reps=3)
@@ -949,7 +1007,7 @@ def run_anchor_config(args, rank, world, dev):
     ras_f = sum(warm_step_ms.get(k, 0) for k in ("preprocess_kernel", "plan_scan_kernel", "scatter_kernel", "tile_sort_kernel", "blend_forward_kernel"))
     ras_b = sum(warm_step_ms.get(k, 0) for k in ("blend_backward_kernel", "preprocess_backward_kernel"))
     P1 = stats["P"]
-    peak = hbm_copy_peak(dev)
+    peak = hbm_copy_peak(dev) if args.full else None
     V = stats.get("V", 0)
     lvl0 = pc.feat_planes._feat.k0s[0]
     extra = {"N": N, "V": V, "n": V * pc.n_offsets, "C": lvl0.channels,
@@ -983,41 +1041,46 @@ def run_anchor_config(args, rank, world, dev):
                                      "sharded": "splatco_amd.adam.ShardedFusedAdam (Adam and its moments / ranks; parameters all-gathered)"}[args.optimizer]}
                       if train else {})},
         "iter_per_s": 1.0 / step_s,
-        "stages": {
-            "rasterizer_kernels_ms": {"forward": ras_f, "backward": ras_b},
-            "rasterizer_Msplats_per_s": P1 / (ras_f + ras_b) / 1e3 if ras_f + ras_b else None,
-            "anchor_path_ms": step_s * 1e3 - ras_f - ras_b if not train else None,
-            "anchor_path_Manchors_per_s": N / (step_s * 1e3 - ras_f - ras_b) / 1e3 if not train else None,
-        },
-        "roofline": roofline_object(dominant, kern.get(dominant, 0.0), ab, peak,
-                                    "dominant among this library's kernel classes by time per step",
-                                    flops=algorithmic_flops(dominant, V), traffic_file=f"hbm_traffic_{args.config}.json",
-                                    launches=max(launches.get(dominant, 1.0), 1.0), issued=issued_mfma_flops(dominant, V)),
-        "kernel_ms_per_step": {k: round(v, 4) for k, v in sorted(warm_step_ms.items(), key=lambda kv: -kv[1])},
-        # every kernel class of this library against ITS byte model (per step, all launches of the class)
-        "kernel_rooflines": {k: {"ms_per_step": round(ms, 4),
-                                 "algorithmic_MB_per_step": round(algorithmic_bytes(k, P1, I, W * H, extra) / 1e6, 1),
-                                 "GBps": round(algorithmic_bytes(k, P1, I, W * H, extra) / (ms * 1e-3) / 1e9, 1),
-                                 "frac_of_measured_peak": round(algorithmic_bytes(k, P1, I, W * H, extra) / (ms * 1e-3) / 1e9 / peak, 3),
-                                 **({"mfma_TFLOPs": round(algorithmic_flops(k, V) / (ms * 1e-3) / 1e12, 1),
-                                     "frac_of_f32_mfma_peak": round(algorithmic_flops(k, V) / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 3),
-                                     "mfma_issue_frac": round(issued_mfma_flops(k, V) / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 3)}
-                                    if algorithmic_flops(k, V) else {})}
-                             for k, ms in sorted(warm_step_ms.items(), key=lambda kv: -kv[1]) if ms > 0},
         "peak_mem_GiB": torch.cuda.max_memory_allocated() / 2 ** 30,
     }
-    for k, v in out["kernel_rooflines"].items():
-        # PMC traffic of the class per step (tools/profile_cfg_pmc.sh) at the default scene of the config -- only if it
-        # was collected on the kernel code that is running now
-        t_pmc, _src = profile_value(f"hbm_traffic_{args.config}.json", k) if not args.anchors else (None, None)
-        if t_pmc is not None:
-            v["pmc_traffic_MB_per_step"] = round(t_pmc / 1e6, 1)
-            v["pmc_GBps"] = round(t_pmc / (v["ms_per_step"] * 1e-3) / 1e9, 1)
-            v["pmc_collected_at_git"] = _src.get("collected_at_git")
-        if k == "blend_forward_kernel" and v["frac_of_measured_peak"] > 1.0:
-            v["note"] = ("the byte model counts every entry of every tile list; the forward stops reading a tile's list once "
-                         "all of its pixels are opaque (T < 1e-4), which at this density is long before the end")
+    if args.full:
+        out.update({
+            "stages": {
+                "rasterizer_kernels_ms": {"forward": ras_f, "backward": ras_b},
+                "rasterizer_Msplats_per_s": P1 / (ras_f + ras_b) / 1e3 if ras_f + ras_b else None,
+                "anchor_path_ms": step_s * 1e3 - ras_f - ras_b if not train else None,
+                "anchor_path_Manchors_per_s": N / (step_s * 1e3 - ras_f - ras_b) / 1e3 if not train else None,
+            },
+            "roofline": roofline_object(dominant, kern.get(dominant, 0.0), ab, peak,
+                                        "dominant among this library's kernel classes by time per step",
+                                        flops=algorithmic_flops(dominant, V), traffic_file=f"hbm_traffic_{args.config}.json",
+                                        launches=max(launches.get(dominant, 1.0), 1.0), issued=issued_mfma_flops(dominant, V)),
+            "kernel_ms_per_step": {k: round(v, 4) for k, v in sorted(warm_step_ms.items(), key=lambda kv: -kv[1])},
+            # every kernel class of this library against ITS byte model (per step, all launches of the class)
+            "kernel_rooflines": {k: {"ms_per_step": round(ms, 4),
+                                     "algorithmic_MB_per_step": round(algorithmic_bytes(k, P1, I, W * H, extra) / 1e6, 1),
+                                     "GBps": round(algorithmic_bytes(k, P1, I, W * H, extra) / (ms * 1e-3) / 1e9, 1),
+                                     "frac_of_measured_peak": round(algorithmic_bytes(k, P1, I, W * H, extra) / (ms * 1e-3) / 1e9 / peak, 3),
+                                     **({"mfma_TFLOPs": round(algorithmic_flops(k, V) / (ms * 1e-3) / 1e12, 1),
+                                         "frac_of_f32_mfma_peak": round(algorithmic_flops(k, V) / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 3),
+                                         "mfma_issue_frac": round(issued_mfma_flops(k, V) / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 3)}
+                                        if algorithmic_flops(k, V) else {})}
+                                 for k, ms in sorted(warm_step_ms.items(), key=lambda kv: -kv[1]) if ms > 0},
+        })
+        for k, v in out["kernel_rooflines"].items():
+            # PMC traffic of the class per step (tools/profile_cfg_pmc.sh) at the default scene of the config -- only if it
+            # was collected on the kernel code that is running now
+            t_pmc, _src = profile_value(f"hbm_traffic_{args.config}.json", k) if not args.anchors else (None, None)
+            if t_pmc is not None:
+                v["pmc_traffic_MB_per_step"] = round(t_pmc / 1e6, 1)
+                v["pmc_GBps"] = round(t_pmc / (v["ms_per_step"] * 1e-3) / 1e9, 1)
+                v["pmc_collected_at_git"] = _src.get("collected_at_git")
+            if k == "blend_forward_kernel" and v["frac_of_measured_peak"] > 1.0:
+                v["note"] = ("the byte model counts every entry of every tile list; the forward stops reading a tile's list once "
+                             "all of its pixels are opaque (T < 1e-4), which at this density is long before the end")
     if train:
+        out["config"]["tv"] = f"every {TV_EVERY}th step (train.py:242-243), weight {TV_WEIGHT_A}, after the gradient exchange, once"
+    if train and args.full:
         # the total-variation pass on its own (it runs on every 4th timed step): HBM-bound, 12 algorithmic bytes per plane
         # element (read plane, read + write gradient) over the planes of the active grids
         feat = pc.feat_planes._feat
@@ -1031,7 +1094,6 @@ def run_anchor_config(args, rank, world, dev):
         e1.record()
         torch.cuda.synchronize()
         tv_ms = e0.elapsed_time(e1) / 10
-        out["config"]["tv"] = f"every {TV_EVERY}th step (train.py:242-243), weight {TV_WEIGHT_A}, after the gradient exchange, once"
         out["tv_pass"] = {"kernel": "tv_add_grad_kernel", "ms": round(tv_ms, 4), "plane_elements": elems,
                           "algorithmic_MB": round(12 * elems / 1e6, 1), "GBps": round(12 * elems / (tv_ms * 1e-3) / 1e9, 1),
                           "frac_of_measured_peak": round(12 * elems / (tv_ms * 1e-3) / 1e9 / peak, 3),
@@ -1073,8 +1135,15 @@ def main():
                          "(uneven tile lists: the tile scheduler and the deep-list sort are timed, not just tested); the headline is 'uniform'")
     ap.add_argument("--sigma-scale", type=float, default=1.0,
                     help="cfg1 developer sweep: multiply every screen-space sigma (sparser tile lists; the headline is 1.0)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cfg2", action="store_true", help="cfg1 at N = 1: skip the cfg2 block that rides along on the line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel times and rooflines, the measured HBM peak, the idle-ramp "
+                         "figure, the exchange timings of N > 1, the total-variation pass, and at cfg1 N = 1 the cfg2 block and "
+                         "the CPU baseline with its PSNR match")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; a fixed "
+                         "seeded sample of the larger arrays, at most 64 MiB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-cfg2", action="store_true", help="with --full, cfg1 at N = 1: skip the cfg2 block that rides along on the line")
     ap.add_argument("--timeout", type=float, default=1500.0,
                     help="--gpus N > 1 started by this script: kill the ranks and exit non-zero after this many seconds")
     args = ap.parse_args()

@@ -165,7 +165,7 @@ def test_bench_sharded_optimizer_and_dry_run():
     env.pop("WORLD_SIZE", None)
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "cfg3", "--anchors", "200000",
             "--exchange", "rs_ag", "--optimizer", "sharded"]
-    r = subprocess.run(base + ["--steps", "2", "--warmup", "2"], capture_output=True, text=True, env=env, timeout=900)
+    r = subprocess.run(base + ["--steps", "2", "--warmup", "2", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["value"] > 0 and "ShardedFusedAdam" in out["config"]["optimizer"]
@@ -190,7 +190,7 @@ def test_bench_starts_its_own_ranks(config):
     bookkeeping."""
     env = dict(os.environ, SPLATCO_BENCH_ONE_DEVICE="1", SPLATCO_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2", "--config", config]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2", "--config", config, "--full"]
     if config != "cfg1":
         cmd += ["--anchors", "200000"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)

@@ -2,7 +2,7 @@
 # Developer A/B: per-kernel-class ms per step of a configuration, product library against a variant, and the differences.
 # usage: tools/ab_diff.sh CONFIG variant.so [extra bench.py arguments]
 CFG=$1; VAR=$2; shift 2
-run() { python bench.py --config $CFG --steps 6 --warmup 3 --no-cpu-baseline "$@" 2>&1 | grep '^{"metric"' | tail -1; }
+run() { python bench.py --full --config $CFG --steps 6 --warmup 3 --no-cpu-baseline "$@" 2>&1 | grep '^{"metric"' | tail -1; }
 unset SPLATCO_RASTER_LIB; run "$@" > /tmp/ab_base.json
 SPLATCO_RASTER_LIB=$PWD/$VAR run "$@" > /tmp/ab_var.json
 python - <<'PY'

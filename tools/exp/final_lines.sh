@@ -1,9 +1,9 @@
 #!/bin/bash
 # Run on the GPU box: the round's final bench lines with the counter tables installed (default line incl. cfg2 + CPU baseline; cfg3; cfg4).
 O=gpurun_out; T=${1:-r06z}
-python bench.py > $O/${T}_bench_cfg1.json 2> $O/${T}_bench_cfg1.err
-python bench.py --config cfg3 --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 > $O/${T}_bench_cfg3.json
-python bench.py --config cfg4 --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 > $O/${T}_bench_cfg4.json
+python bench.py --full > $O/${T}_bench_cfg1.json 2> $O/${T}_bench_cfg1.err
+python bench.py --full --config cfg3 --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 > $O/${T}_bench_cfg3.json
+python bench.py --full --config cfg4 --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 > $O/${T}_bench_cfg4.json
 python - <<PY
 import json
 d=json.load(open('$O/${T}_bench_cfg1.json'))

@@ -1,8 +1,8 @@
 set -x
 O=gpurun_out
-python bench.py --config cfg3 --steps 8 --warmup 3 --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 > $O/r06m_bench_cfg3.json
-python bench.py --config cfg4 --steps 6 --warmup 3 --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 > $O/r06m_bench_cfg4.json
-python bench.py --scene clustered --steps 20 --warmup 5 2>/dev/null | grep '^{"metric"' | tail -1 > $O/r06m_bench_cfg1_clustered.json
+python bench.py --full --config cfg3 --steps 8 --warmup 3 --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 > $O/r06m_bench_cfg3.json
+python bench.py --full --config cfg4 --steps 6 --warmup 3 --no-cpu-baseline 2>/dev/null | grep '^{"metric"' | tail -1 > $O/r06m_bench_cfg4.json
+python bench.py --full --scene clustered --steps 20 --warmup 5 2>/dev/null | grep '^{"metric"' | tail -1 > $O/r06m_bench_cfg1_clustered.json
 python bench.py --gpus 8 --config cfg4 --anchors 2000000 --exchange rs_ag --optimizer sharded --sparse-exchange --dry-run-ranks --steps 1 --warmup 1 > $O/r06m_dry_cfg4_sparse_sharded.log 2>&1
 python bench.py --gpus 4 --config cfg3 --anchors 1000000 --dry-run-ranks --steps 1 --warmup 1 > $O/r06m_dry_cfg3.log 2>&1
 python - <<'PY'

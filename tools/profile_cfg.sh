@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=$REPO/gpurun_out
 mkdir -p $OUT
 cd /tmp
-timeout -k 5 900 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o stats -- python3 $REPO/bench.py --config $CFG --no-cpu-baseline "$@" > $OUT/bench_$TAG.log 2>&1
+timeout -k 5 900 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o stats -- python3 $REPO/bench.py --full --config $CFG --no-cpu-baseline "$@" > $OUT/bench_$TAG.log 2>&1
 cd $REPO
 tail -1 $OUT/bench_$TAG.log
 DB=$(find $OUT/prof_$TAG -name "*.db" | head -1)

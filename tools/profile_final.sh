@@ -14,6 +14,6 @@ for CFG in cfg3 cfg4; do
   rm -rf $OUT/prof_${TAG}_$CFG
 done
 bash tools/profile_cfg_pmc.sh $TAG cfg4 >> $OUT/profile_final_$TAG.log 2>&1
-python3 bench.py > $OUT/${TAG}_bench_cfg1.json 2> $OUT/${TAG}_bench_cfg1.err
+python3 bench.py --full > $OUT/${TAG}_bench_cfg1.json 2> $OUT/${TAG}_bench_cfg1.err
 ls -la $OUT | grep $TAG | head -40
 tail -5 $OUT/profile_final_$TAG.log

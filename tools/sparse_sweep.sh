@@ -7,7 +7,7 @@ OUT=$REPO/gpurun_out
 export TMPDIR=/tmp
 mkdir -p $OUT
 for S in 1 0.5 0.25 0.1; do
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-cfg2 --sigma-scale $S > $OUT/${TAG}_s${S}.json 2> $OUT/${TAG}_s${S}.err
+  python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-cfg2 --sigma-scale $S > $OUT/${TAG}_s${S}.json 2> $OUT/${TAG}_s${S}.err
   (cd /tmp && timeout -k 5 240 rocprofv3 --kernel-trace --stats -d $OUT/prof_${TAG}_s${S} -o stats -- python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-cfg2 --sigma-scale $S > $OUT/${TAG}_s${S}_prof.log 2>&1)
   DB=$(find $OUT/prof_${TAG}_s${S} -name "*.db" | head -1)
   python3 tools/rocpd_summary.py $DB $OUT/${TAG}_s${S}_kernel_stats.txt "bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-cfg2 --sigma-scale $S (rocprofv3 --kernel-trace --stats)" > /dev/null
