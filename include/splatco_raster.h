@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SCR_ABI_VERSION 27
+#define SCR_ABI_VERSION 28
 #define SCR_TILE 16 /* 16x16-pixel tiles: part of the result contract (tile rects, ranges, sort keys) */
 
 /* The 12 fields of GaussianRasterizationSettings, same order (gaussian_renderer/__init__.py:145-158).
@@ -290,6 +290,25 @@ int scr_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float* img1, con
                          const void* scratch, const float* g_l1, const float* g_ssim, float* dimg1,
                          void* stream);
 
+/* ---- LDR-FLIP of [N,3,H,W] image pairs (ABI 28; metrics.py:38-108, utils/flip.py LDRFLIPLoss / compute_ldrflip at
+ * their defaults qc 0.7, qf 0.5, pc 0.4, pt 0.95, eps 1e-15).  test / ref are sRGB in [0,1] (clamped; with quantize != 0
+ * also rounded to 8 bits, x <- floor(255 x + 0.5) / 255, as a PNG written and read back).  pixels_per_degree sets the
+ * filters: CSF radius ceil(3 sqrt(0.04 / 2 pi^2) ppd), feature radius ceil(3 * 0.5 * 0.082 ppd); both must be at most
+ * SCR_FLIP_MAX_RADIUS and ppd >= 1 (1 <= ppd <= 118.4), otherwise the call fails.  Writes to DEVICE memory
+ * mean_out[N] = per-image mean FLIP, mse_out[N] (may be NULL) = per-image mean squared error of the clamped (quantized)
+ * pair over its 3 H W values, map_out[N,H,W] (may be NULL) = per-pixel FLIP.  Deterministic (per-tile partials, a
+ * fixed-order sum per image: an image scores the same bits alone or in a batch); no host synchronisation.
+ * scr_flip_filters is host-only: the binary64 1-D weights the kernel receives (rounded to binary32) for `ppd`, as
+ * weights[7][2 SCR_FLIP_MAX_RADIUS + 1] = (A, RG, BY1, BY2 CSF profiles; edge, point, Gaussian feature profiles), tap
+ * k at offset k - r (zeros past 2r), radii[2] = (CSF, feature) and scalars[3] = (BY1 weight, BY2 weight, cmax): the
+ * 2-D CSF kernels are A (x) A, RG (x) RG, c1 BY1 (x) BY1 + c2 BY2 (x) BY2; the x-detectors are edge / point along x
+ * times the Gaussian along y, the y-detectors their transposes. */
+#define SCR_FLIP_MAX_RADIUS 16
+size_t scr_flip_scratch_bytes(int32_t N, int32_t H, int32_t W);
+int scr_flip_forward(int32_t N, int32_t H, int32_t W, const float* test, const float* ref, double pixels_per_degree,
+                     int32_t quantize, void* scratch, float* mean_out, float* mse_out, float* map_out, void* stream);
+int scr_flip_filters(double pixels_per_degree, double* weights, int32_t* radii, double* scalars);
+
 /* The loss's scaling regulariser, mean_p(scaling[p,0] scaling[p,1] scaling[p,2]) (train.py:192-196:
  * `scaling.prod(dim=1).mean()`) -> out[1], and its gradient dscaling[P,3] = g[0] / P * (products of the other two).
  * One streaming pass per direction, ordered partial sums (deterministic); no host read. */
@@ -505,7 +524,7 @@ enum {
     SCR_PROF_PREPROCESS_BACKWARD = 7, SCR_PROF_EXPAND = 8, SCR_PROF_EXPAND_BACKWARD = 9, SCR_PROF_PLANE_BACKWARD = 10,
     SCR_PROF_L1_SSIM = 11, SCR_PROF_L1_SSIM_BACKWARD = 12, SCR_PROF_TRIPLANE_FORWARD = 13, SCR_PROF_MLP_HEADS = 14,
     SCR_PROF_MLP_HEADS_BACKWARD = 15, SCR_PROF_NORM_LINEAR = 16, SCR_PROF_NORM_LINEAR_BACKWARD = 17, SCR_PROF_PLANE_ATTENTION = 18,
-    SCR_PROF_COUNT = 19
+    SCR_PROF_FLIP = 19, SCR_PROF_COUNT = 20
 };
 int scr_profile_enable(int mask);
 /* Bracket only every `every`-th launch of a selected class (default 1 = every launch): a benchmark that times K steps

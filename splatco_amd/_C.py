@@ -23,6 +23,7 @@ SYMBOLS = [
     "scr_profile_kernel_name", "scr_expand_scratch_bytes", "scr_expand_plan", "scr_expand_run",
     "scr_expand_backward", "scr_mask_index_plan", "scr_mask_index_run", "scr_plane_sample_scratch_bytes", "scr_plane_sample_backward", "scr_triplane_backward_multi_scratch_bytes", "scr_triplane_backward_multi", "scr_plane_row_pairs", "scr_triplane_forward", "scr_triplane_backward_scratch_bytes", "scr_triplane_backward",
     "scr_l1_ssim_scratch_bytes", "scr_l1_ssim_forward", "scr_l1_ssim_backward",
+    "scr_flip_scratch_bytes", "scr_flip_forward", "scr_flip_filters",
     "scr_scaling_reg_scratch_bytes", "scr_scaling_reg_forward", "scr_scaling_reg_backward",
     "scr_pair_l1_scratch_bytes", "scr_pair_l1_forward", "scr_pair_l1_backward",
     "scr_tpa_scratch_bytes", "scr_tpa_stats", "scr_tpa_forward", "scr_tpa_backward", "scr_tpa_backward_stats",
@@ -34,8 +35,9 @@ SYMBOLS = [
     "scr_markers_enable", "scr_marker_push", "scr_marker_pop", "scr_norm_linear_dx",
 ]
 PLAN_NONFINITE_COLOUR, PLAN_LARGE_RECTS = 1, 2      # SCR_PLAN_*
-PROF_COUNT = 19
-ABI_VERSION = 27
+PROF_COUNT = 20
+ABI_VERSION = 28
+FLIP_MAX_RADIUS = 16                                # SCR_FLIP_MAX_RADIUS
 
 (DBG_TILES_TOUCHED, DBG_POINT_OFFSETS, DBG_RANGES, DBG_POINT_LIST, DBG_N_CONTRIB, DBG_FINAL_T, DBG_SPLAT_RECORDS, DBG_QMASK,
  DBG_GM_INDEX) = range(9)
@@ -151,6 +153,11 @@ def _load():
     lib.scr_l1_ssim_forward.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, vp]
     lib.scr_l1_ssim_backward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.scr_l1_ssim_forward.restype = lib.scr_l1_ssim_backward.restype = C.c_int
+    lib.scr_flip_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.scr_flip_scratch_bytes.restype = C.c_size_t
+    lib.scr_flip_forward.argtypes = [i32, i32, i32, vp, vp, C.c_double, i32, vp, vp, vp, vp, vp]
+    lib.scr_flip_filters.argtypes = [C.c_double, vp, vp, vp]
+    lib.scr_flip_forward.restype = lib.scr_flip_filters.restype = C.c_int
     lib.scr_scaling_reg_scratch_bytes.argtypes = [i64]
     lib.scr_scaling_reg_scratch_bytes.restype = C.c_size_t
     lib.scr_scaling_reg_forward.argtypes = [i64, vp, vp, vp, vp]

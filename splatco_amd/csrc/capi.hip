@@ -84,7 +84,7 @@ const char* const kProfNames[SCR_PROF_COUNT] = {
     "blend_forward_kernel", "blend_backward_kernel", "preprocess_backward_kernel", "expand_kernel",
     "expand_backward_kernel", "plane_sample_backward_kernels", "l1_ssim_forward_kernel",
     "l1_ssim_backward_kernel", "triplane_forward_kernel", "mlp_heads_kernel", "mlp_heads_backward_kernel",
-    "norm_linear_kernels", "norm_linear_backward_kernels", "plane_attention_kernels"};
+    "norm_linear_kernels", "norm_linear_backward_kernels", "plane_attention_kernels", "flip_kernel"};
 }  // namespace
 
 // streaming copy, 16 B per lane, four loads in flight per thread, non-temporal: the shape that reaches the highest HBM
@@ -742,6 +742,34 @@ int scr_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float* img1, con
     { ProfScope ps_(SCR_PROF_L1_SSIM_BACKWARD, st);
       launch_l1_ssim_backward(C, H, W, img1, img2, scratch, g_l1, g_ssim, dimg1, st); }
     CHECK_LAUNCH("l1_ssim_backward_kernel", 0, st);
+    return 0;
+}
+
+// ---- LDR-FLIP of image pairs (flip.hip)
+size_t scr_flip_scratch_bytes(int32_t N, int32_t H, int32_t W) {
+    return (N <= 0 || H <= 0 || W <= 0) ? 0 : flip_scratch_bytes(N, H, W);
+}
+
+int scr_flip_forward(int32_t N, int32_t H, int32_t W, const float* test, const float* ref, double pixels_per_degree,
+                     int32_t quantize, void* scratch, float* mean_out, float* mse_out, float* map_out, void* stream) {
+    SCR_MARK_FN;
+    if (N <= 0 || H <= 0 || W <= 0) return fail("bad image size");
+    if (N > 65535 || (H + 15) / 16 > 65535) return fail("N = %d / H = %d exceed the launch grid", N, H);
+    if (!test || !ref || !scratch || !mean_out) return fail("NULL argument");
+    int rc, rf;
+    if (flip_radii(pixels_per_degree, &rc, &rf))
+        return fail("pixels_per_degree %g: must be >= 1 with filter radii <= %d", pixels_per_degree, SCR_FLIP_MAX_RADIUS);
+    hipStream_t st = (hipStream_t)stream;
+    { ProfScope ps_(SCR_PROF_FLIP, st);
+      launch_flip_forward(N, H, W, test, ref, pixels_per_degree, quantize, scratch, mean_out, mse_out, map_out, st); }
+    CHECK_LAUNCH("flip_kernel", 0, st);
+    return 0;
+}
+
+int scr_flip_filters(double pixels_per_degree, double* weights, int32_t* radii, double* scalars) {
+    if (!weights || !radii || !scalars) return fail("NULL argument");
+    if (flip_filters(pixels_per_degree, weights, radii, scalars))
+        return fail("pixels_per_degree %g: must be >= 1 with filter radii <= %d", pixels_per_degree, SCR_FLIP_MAX_RADIUS);
     return 0;
 }
 

@@ -445,6 +445,11 @@ void launch_tpa_backward_stats(int R, int64_t HW, const float* davg, const float
                                float* d1, float* d2, hipStream_t st);
 
 size_t l1_ssim_scratch_bytes(int C, int H, int W, int with_grad);
+int flip_radii(double ppd, int* rc, int* rf);
+int flip_filters(double ppd, double* w, int* radii, double* scalars);
+size_t flip_scratch_bytes(int N, int H, int W);
+int launch_flip_forward(int N, int H, int W, const float* test, const float* ref, double ppd, int quantize,
+                        void* scratch, float* mean_out, float* mse_out, float* map_out, hipStream_t st);
 size_t scaling_reg_scratch_bytes(int64_t P);
 size_t pair_l1_scratch_bytes(int64_t n);
 void launch_pair_l1_forward(int64_t n, const float* g1, const float* g2, const float* r1, const float* r2, void* scratch, float* out,
