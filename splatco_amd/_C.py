@@ -10,30 +10,12 @@ import os
 # PyTorch-ROCm carries its own libamdhip64: load it BEFORE this library, so that both use ONE HIP runtime (the library's
 # device pointers and streams are torch's).  Loaded the other way round -- e.g. build() and smoke() in one process --
 # this library binds to /opt/rocm's copy and its first HIP call fails with "no ROCm-capable device is detected".
-import torch  # noqa: F401
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # developer override for A/B experiments with variant builds of the same library
 LIB_PATH = os.environ.get("SPLATCO_RASTER_LIB", os.path.join(_HERE, "csrc", "libsplatco_raster.so"))
 
-SYMBOLS = [
-    "scr_abi_version", "scr_last_error", "scr_geom_bytes", "scr_binning_bytes", "scr_image_bytes",
-    "scr_backward_scratch_bytes", "scr_visible_filter", "scr_mark_visible", "scr_forward_plan",
-    "scr_forward_run", "scr_backward", "scr_debug_get", "scr_profile_enable", "scr_profile_read",
-    "scr_profile_kernel_name", "scr_expand_scratch_bytes", "scr_expand_plan", "scr_expand_run",
-    "scr_expand_backward", "scr_mask_index_plan", "scr_mask_index_run", "scr_plane_sample_scratch_bytes", "scr_plane_sample_backward", "scr_triplane_backward_multi_scratch_bytes", "scr_triplane_backward_multi", "scr_plane_row_pairs", "scr_triplane_forward", "scr_triplane_backward_scratch_bytes", "scr_triplane_backward",
-    "scr_l1_ssim_scratch_bytes", "scr_l1_ssim_forward", "scr_l1_ssim_backward",
-    "scr_flip_scratch_bytes", "scr_flip_forward", "scr_flip_filters",
-    "scr_scaling_reg_scratch_bytes", "scr_scaling_reg_forward", "scr_scaling_reg_backward",
-    "scr_pair_l1_scratch_bytes", "scr_pair_l1_forward", "scr_pair_l1_backward",
-    "scr_tpa_scratch_bytes", "scr_tpa_stats", "scr_tpa_forward", "scr_tpa_backward", "scr_tpa_backward_stats",
-    "scr_statis_compute", "scr_statis_apply", "scr_copy_probe",
-    "scr_knn", "scr_knn_curvature", "scr_anchor_gather_stat_rows", "scr_anchor_gather_stat_buffer_rows", "scr_anchor_gather", "scr_anchor_gather_backward", "scr_mlp_heads_hidden_bytes", "scr_mlp_heads_partial_bytes", "scr_mlp_heads_forward", "scr_mlp_heads_backward",
-    "scr_norm_linear_scratch_bytes", "scr_norm_linear_forward", "scr_norm_linear_backward",
-    "scr_norm_fold", "scr_norm_fold_backward", "scr_norm_running_stats", "scr_box_coords", "scr_forward_plan_run",
-    "scr_profile_stride", "scr_debug_force_deep_lists", "scr_adam_step", "scr_tv_add_grad",
-    "scr_markers_enable", "scr_marker_push", "scr_marker_pop", "scr_norm_linear_dx",
-]
 PLAN_NONFINITE_COLOUR, PLAN_LARGE_RECTS = 1, 2      # SCR_PLAN_*
 PROF_COUNT = 20
 ABI_VERSION = 28
@@ -42,30 +24,114 @@ FLIP_MAX_RADIUS = 16                                # SCR_FLIP_MAX_RADIUS
 (DBG_TILES_TOUCHED, DBG_POINT_OFFSETS, DBG_RANGES, DBG_POINT_LIST, DBG_N_CONTRIB, DBG_FINAL_T, DBG_SPLAT_RECORDS, DBG_QMASK,
  DBG_GM_INDEX) = range(9)
 
-
-class AdamTensor(C.Structure):
-    """scr_adam_tensor (include/splatco_raster.h)."""
-    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
-                ("numel", C.c_int64), ("step_size", C.c_double), ("bias_correction2_sqrt", C.c_double)]
-
-
-class TvPlane(C.Structure):
-    """scr_tv_plane (include/splatco_raster.h)."""
-    _fields_ = [("plane", C.c_void_p), ("grad", C.c_void_p), ("channels", C.c_int32), ("rows", C.c_int32),
-                ("cols", C.c_int32), ("coef", C.c_float)]
+vp, cp, u8, i32, i64, f32, f64, sz = C.c_void_p, C.c_char_p, C.c_uint8, C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t
+P = C.POINTER
 
 
 class Settings(C.Structure):
     """struct scr_settings (include/splatco_raster.h): the 12 fields of
     GaussianRasterizationSettings, same order (gaussian_renderer/__init__.py:145-158)."""
     _fields_ = [
-        ("image_height", C.c_int32), ("image_width", C.c_int32),
-        ("tanfovx", C.c_float), ("tanfovy", C.c_float),
-        ("bg", C.c_void_p), ("scale_modifier", C.c_float),
-        ("viewmatrix", C.c_void_p), ("projmatrix", C.c_void_p),
-        ("sh_degree", C.c_int32), ("campos", C.c_void_p),
-        ("prefiltered", C.c_int32), ("debug", C.c_int32),
+        ("image_height", i32), ("image_width", i32),
+        ("tanfovx", f32), ("tanfovy", f32),
+        ("bg", vp), ("scale_modifier", f32),
+        ("viewmatrix", vp), ("projmatrix", vp),
+        ("sh_degree", i32), ("campos", vp),
+        ("prefiltered", i32), ("debug", i32),
     ]
+
+
+class AdamTensor(C.Structure):
+    """scr_adam_tensor (include/splatco_raster.h)."""
+    _fields_ = [("param", vp), ("grad", vp), ("exp_avg", vp), ("exp_avg_sq", vp),
+                ("numel", i64), ("step_size", f64), ("bias_correction2_sqrt", f64)]
+
+
+class TvPlane(C.Structure):
+    """scr_tv_plane (include/splatco_raster.h)."""
+    _fields_ = [("plane", vp), ("grad", vp), ("channels", i32), ("rows", i32), ("cols", i32), ("coef", f32)]
+
+
+# (name, restype, *argtypes) of every function in include/splatco_raster.h, in header order.  `int` is i32 here;
+# tests/test_abi_and_multiview.py checks every entry, struct and constant above against the header.
+SIGNATURES = [
+    ("scr_abi_version", i32),
+    ("scr_last_error", cp),
+    ("scr_geom_bytes", sz, i64, i32, i32),
+    ("scr_binning_bytes", sz, i64, i64),
+    ("scr_image_bytes", sz, i32, i32),
+    ("scr_backward_scratch_bytes", sz, i64),
+    ("scr_visible_filter", i32, i64, vp, vp, vp, vp, P(Settings), vp, vp),
+    ("scr_mark_visible", i32, i64, vp, vp, vp, vp),
+    ("scr_forward_plan", i32, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp),
+    ("scr_forward_run", i32, i64, i64, i64, i64, P(Settings), *[vp] * 5),
+    ("scr_forward_plan_run", i32, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp, sz, vp, vp, vp),
+    ("scr_backward", i32, i64, i32, i64, i64, *[vp] * 5, P(Settings), *[vp] * 15),
+    ("scr_debug_force_deep_lists", i32, i32),
+    ("scr_debug_get", i32, i32, i64, i64, i32, i32, *[vp] * 5),
+    ("scr_tpa_scratch_bytes", sz, i32, i32, i32),
+    ("scr_tpa_stats", i32, i32, i32, i32, *[vp] * 8),
+    ("scr_tpa_forward", i32, i32, i32, i32, *[vp] * 12),
+    ("scr_tpa_backward", i32, i32, i32, i32, *[vp] * 18),
+    ("scr_tpa_backward_stats", i32, i32, i32, i32, *[vp] * 7),
+    ("scr_expand_scratch_bytes", sz, i64),
+    ("scr_expand_plan", i32, i64, vp, vp, P(i64), vp),
+    ("scr_mask_index_plan", i32, i64, vp, vp, P(i64), vp),
+    ("scr_mask_index_run", i32, i64, *[vp] * 5),
+    ("scr_expand_run", i32, i64, i32, vp, vp, vp, vp, i32, *[vp] * 11),
+    ("scr_expand_backward", i32, i64, i32, vp, vp, i32, *[vp] * 14, i64, vp),
+    ("scr_triplane_backward_multi_scratch_bytes", sz, i64, i32, vp, vp, vp, vp),
+    ("scr_triplane_backward_multi", i32, i64, vp, i32, i32, *[vp] * 6, i32, vp, vp, vp, vp, i32, vp, i32, vp),
+    ("scr_plane_row_pairs", i32, i32, i32, i32, vp, vp, vp),
+    ("scr_triplane_forward", i32, i64, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp),
+    ("scr_plane_sample_scratch_bytes", sz, i64, i32, i32, i32),
+    ("scr_triplane_backward_scratch_bytes", sz, i64, i32, i32, i32, i32),
+    ("scr_triplane_backward", i32, i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp),
+    ("scr_plane_sample_backward", i32, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp),
+    ("scr_l1_ssim_scratch_bytes", sz, i32, i32, i32, i32),
+    ("scr_l1_ssim_forward", i32, i32, i32, i32, vp, vp, vp, i32, vp, vp),
+    ("scr_l1_ssim_backward", i32, i32, i32, i32, *[vp] * 7),
+    ("scr_flip_scratch_bytes", sz, i32, i32, i32),
+    ("scr_flip_forward", i32, i32, i32, i32, vp, vp, f64, i32, *[vp] * 5),
+    ("scr_flip_filters", i32, f64, vp, vp, vp),
+    ("scr_scaling_reg_scratch_bytes", sz, i64),
+    ("scr_scaling_reg_forward", i32, i64, vp, vp, vp, vp),
+    ("scr_scaling_reg_backward", i32, i64, vp, vp, vp, vp),
+    ("scr_pair_l1_scratch_bytes", sz, i64),
+    ("scr_pair_l1_forward", i32, i64, *[vp] * 7),
+    ("scr_pair_l1_backward", i32, i64, *[vp] * 8),
+    ("scr_anchor_gather_stat_rows", i32, i64),
+    ("scr_anchor_gather_stat_buffer_rows", i64, i64),
+    ("scr_anchor_gather", i32, i64, *[vp] * 10, i32, vp, vp),
+    ("scr_anchor_gather_backward", i32, i64, i64, *[vp] * 7, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp),
+    ("scr_norm_linear_scratch_bytes", sz, i64),
+    ("scr_box_coords", i32, i64, *[vp] * 5),
+    ("scr_norm_fold", i32, i32, i32, *[vp] * 10),
+    ("scr_norm_fold_backward", i32, i32, i32, *[vp] * 13),
+    ("scr_norm_running_stats", i32, i32, i32, *[vp] * 9, i64, vp),
+    ("scr_norm_linear_forward", i32, i64, i32, vp, i32, vp, vp, f32, *[vp] * 6, i32, vp),
+    ("scr_norm_linear_dx", i32, i64, i32, vp, i32, vp, i32, vp, vp, i32, vp),
+    ("scr_norm_linear_backward", i32, i64, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, *[vp] * 5),
+    ("scr_mlp_heads_hidden_bytes", sz, i64),
+    ("scr_mlp_heads_partial_bytes", sz, i64),
+    ("scr_mlp_heads_forward", i32, i64, vp, i32, *[vp] * 17),
+    ("scr_mlp_heads_backward", i32, i64, vp, i32, *[vp] * 28),
+    ("scr_statis_compute", i32, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp),
+    ("scr_statis_apply", i32, i64, i32, *[vp] * 8),
+    ("scr_adam_step", i32, i32, P(AdamTensor), f64, f64, f64, vp),
+    ("scr_tv_add_grad", i32, i32, P(TvPlane), vp),
+    ("scr_knn", i32, i64, i32, P(f32), *[vp] * 5),
+    ("scr_knn_curvature", i32, i64, i32, vp, vp, vp, vp),
+    ("scr_copy_probe", i32, vp, vp, sz, vp),
+    ("scr_profile_enable", i32, i32),
+    ("scr_profile_stride", i32, i32),
+    ("scr_profile_read", i32, P(f64), P(i64)),
+    ("scr_profile_kernel_name", cp, i32),
+    ("scr_markers_enable", i32, i32),
+    ("scr_marker_push", i32, cp),
+    ("scr_marker_pop", i32),
+]
+SYMBOLS = [s[0] for s in SIGNATURES]
 
 
 def _load():
@@ -75,141 +141,13 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C splatco_amd/csrc`). "
             "There is deliberately no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for s in SYMBOLS:
-        if not hasattr(lib, s):
-            raise ImportError(f"{LIB_PATH} does not export {s}")
-    lib.scr_abi_version.restype = C.c_int
+    for name, restype, *argtypes in SIGNATURES:
+        if not hasattr(lib, name):
+            raise ImportError(f"{LIB_PATH} does not export {name}")
+        f = getattr(lib, name)
+        f.restype, f.argtypes = restype, argtypes
     if lib.scr_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {lib.scr_abi_version()}, expected {ABI_VERSION}")
-    lib.scr_last_error.restype = C.c_char_p
-    for f in ("scr_geom_bytes", "scr_binning_bytes", "scr_image_bytes", "scr_backward_scratch_bytes",
-              "scr_expand_scratch_bytes"):
-        getattr(lib, f).restype = C.c_size_t
-    lib.scr_geom_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-    lib.scr_binning_bytes.argtypes = [C.c_int64, C.c_int64]
-    lib.scr_image_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.scr_backward_scratch_bytes.argtypes = [C.c_int64]
-    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int32
-    sp = C.POINTER(Settings)
-    lib.scr_visible_filter.argtypes = [i64, vp, vp, vp, vp, sp, vp, vp]
-    lib.scr_mark_visible.argtypes = [i64, vp, vp, vp, vp]
-    lib.scr_forward_plan.argtypes = [i64, i32, vp, vp, vp, vp, vp, vp, vp, sp, vp, vp, C.POINTER(C.c_int64), vp]
-    lib.scr_forward_run.argtypes = [i64, i64, i64, i64, sp, vp, vp, vp, vp, vp]
-    lib.scr_forward_plan_run.argtypes = [i64, i32, vp, vp, vp, vp, vp, vp, vp, sp, vp, vp, C.POINTER(C.c_int64), vp, C.c_size_t,
-                                         vp, vp, vp]
-    lib.scr_forward_plan_run.restype = C.c_int
-    lib.scr_debug_force_deep_lists.argtypes = [C.c_int]
-    lib.scr_debug_force_deep_lists.restype = C.c_int
-    lib.scr_profile_stride.argtypes = [C.c_int]
-    lib.scr_profile_stride.restype = C.c_int
-    lib.scr_markers_enable.argtypes = [C.c_int]
-    lib.scr_markers_enable.restype = C.c_int
-    lib.scr_marker_push.argtypes = [C.c_char_p]
-    lib.scr_marker_push.restype = C.c_int
-    lib.scr_marker_pop.argtypes = []
-    lib.scr_marker_pop.restype = C.c_int
-    lib.scr_backward.argtypes = [i64, i32, i64, i64, vp, vp, vp, vp, vp, sp, vp, vp, vp, vp, vp, vp,
-                                 vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.scr_debug_get.argtypes = [C.c_int, i64, i64, i32, i32, vp, vp, vp, vp, vp]
-    lib.scr_expand_scratch_bytes.argtypes = [C.c_int64]
-    lib.scr_expand_plan.argtypes = [i64, vp, vp, C.POINTER(C.c_int64), vp]
-    lib.scr_expand_run.argtypes = [i64, i32, vp, vp, vp, vp, i32] + [vp] * 11
-    lib.scr_expand_backward.argtypes = [i64, i32, vp, vp, i32] + [vp] * 14 + [i64, vp]
-    for f in ("scr_expand_plan", "scr_expand_run", "scr_expand_backward"):
-        getattr(lib, f).restype = C.c_int
-    lib.scr_plane_sample_scratch_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
-    lib.scr_plane_sample_scratch_bytes.restype = C.c_size_t
-    lib.scr_plane_sample_backward.argtypes = [i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp]
-    lib.scr_triplane_forward.argtypes = [i64, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp]
-    lib.scr_triplane_forward.restype = C.c_int
-    lib.scr_plane_row_pairs.argtypes = [i32, i32, i32, vp, vp, vp]
-    lib.scr_triplane_backward_multi_scratch_bytes.argtypes = [i64, i32, vp, vp, vp, vp]
-    lib.scr_triplane_backward_multi_scratch_bytes.restype = C.c_size_t
-    lib.scr_triplane_backward_multi.argtypes = [i64, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, vp]
-    lib.scr_triplane_backward_multi.restype = C.c_int
-    lib.scr_plane_row_pairs.restype = C.c_int
-    lib.scr_triplane_backward_scratch_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    lib.scr_triplane_backward_scratch_bytes.restype = C.c_size_t
-    lib.scr_triplane_backward.argtypes = [i64, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp]
-    lib.scr_triplane_backward.restype = C.c_int
-    lib.scr_norm_linear_scratch_bytes.argtypes = [C.c_int64]
-    lib.scr_norm_linear_scratch_bytes.restype = C.c_size_t
-    lib.scr_norm_linear_forward.argtypes = [i64, i32, vp, i32, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, i32, vp]
-    lib.scr_norm_linear_forward.restype = C.c_int
-    lib.scr_norm_linear_backward.argtypes = [i64, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
-    lib.scr_norm_linear_backward.restype = C.c_int
-    lib.scr_norm_linear_dx.argtypes = [i64, i32, vp, i32, vp, i32, vp, vp, i32, vp]
-    lib.scr_norm_linear_dx.restype = C.c_int
-    lib.scr_box_coords.argtypes = [i64, vp, vp, vp, vp, vp]
-    lib.scr_box_coords.restype = C.c_int
-    lib.scr_norm_fold.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.scr_norm_fold_backward.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.scr_norm_running_stats.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
-    for f in ("scr_norm_fold", "scr_norm_fold_backward", "scr_norm_running_stats"):
-        getattr(lib, f).restype = C.c_int
-    lib.scr_plane_sample_backward.restype = C.c_int
-    lib.scr_l1_ssim_scratch_bytes.argtypes = [i32, i32, i32, i32]
-    lib.scr_l1_ssim_scratch_bytes.restype = C.c_size_t
-    lib.scr_l1_ssim_forward.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, vp]
-    lib.scr_l1_ssim_backward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.scr_l1_ssim_forward.restype = lib.scr_l1_ssim_backward.restype = C.c_int
-    lib.scr_flip_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.scr_flip_scratch_bytes.restype = C.c_size_t
-    lib.scr_flip_forward.argtypes = [i32, i32, i32, vp, vp, C.c_double, i32, vp, vp, vp, vp, vp]
-    lib.scr_flip_filters.argtypes = [C.c_double, vp, vp, vp]
-    lib.scr_flip_forward.restype = lib.scr_flip_filters.restype = C.c_int
-    lib.scr_scaling_reg_scratch_bytes.argtypes = [i64]
-    lib.scr_scaling_reg_scratch_bytes.restype = C.c_size_t
-    lib.scr_scaling_reg_forward.argtypes = [i64, vp, vp, vp, vp]
-    lib.scr_scaling_reg_backward.argtypes = [i64, vp, vp, vp, vp]
-    lib.scr_scaling_reg_forward.restype = lib.scr_scaling_reg_backward.restype = C.c_int
-    lib.scr_pair_l1_scratch_bytes.argtypes = [i64]
-    lib.scr_pair_l1_scratch_bytes.restype = C.c_size_t
-    lib.scr_pair_l1_forward.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp]
-    lib.scr_pair_l1_backward.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.scr_pair_l1_forward.restype = lib.scr_pair_l1_backward.restype = C.c_int
-    lib.scr_mask_index_plan.argtypes = [i64, vp, vp, C.POINTER(C.c_int64), vp]
-    lib.scr_mask_index_run.argtypes = [i64, vp, vp, vp, vp, vp]
-    lib.scr_mask_index_plan.restype = lib.scr_mask_index_run.restype = C.c_int
-    lib.scr_tpa_scratch_bytes.argtypes = [i32, i32, i32]
-    lib.scr_tpa_scratch_bytes.restype = C.c_size_t
-    lib.scr_tpa_stats.argtypes = [i32, i32, i32] + [vp] * 8
-    lib.scr_tpa_forward.argtypes = [i32, i32, i32] + [vp] * 12
-    lib.scr_tpa_backward.argtypes = [i32, i32, i32] + [vp] * 18
-    lib.scr_tpa_backward_stats.argtypes = [i32, i32, i32] + [vp] * 7
-    lib.scr_tpa_stats.restype = lib.scr_tpa_forward.restype = C.c_int
-    lib.scr_tpa_backward.restype = lib.scr_tpa_backward_stats.restype = C.c_int
-    lib.scr_statis_compute.argtypes = [i64, i32, vp, vp, vp, vp, i32, vp, vp, vp]
-    lib.scr_statis_apply.argtypes = [i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.scr_statis_compute.restype = lib.scr_statis_apply.restype = C.c_int
-    lib.scr_mlp_heads_hidden_bytes.argtypes = lib.scr_mlp_heads_partial_bytes.argtypes = [i64]
-    lib.scr_mlp_heads_hidden_bytes.restype = lib.scr_mlp_heads_partial_bytes.restype = C.c_size_t
-    lib.scr_mlp_heads_forward.argtypes = [i64, vp, i32] + [vp] * 17
-    lib.scr_mlp_heads_backward.argtypes = [i64, vp, i32] + [vp] * 28
-    lib.scr_mlp_heads_forward.restype = lib.scr_mlp_heads_backward.restype = C.c_int
-    lib.scr_anchor_gather.argtypes = [i64] + [vp] * 10 + [i32, vp, vp]
-    lib.scr_anchor_gather_stat_rows.argtypes = [i64]
-    lib.scr_anchor_gather_stat_rows.restype = C.c_int32
-    lib.scr_anchor_gather_stat_buffer_rows.argtypes = [i64]
-    lib.scr_anchor_gather_stat_buffer_rows.restype = C.c_int64
-    lib.scr_anchor_gather_backward.argtypes = [i64, i64] + [vp] * 7 + [i32] + [vp] * 4 + [i32, vp, vp, i32, vp, i32, vp]
-    lib.scr_anchor_gather.restype = lib.scr_anchor_gather_backward.restype = C.c_int
-    lib.scr_knn.argtypes = [i64, i32, C.POINTER(C.c_float), vp, vp, vp, vp, vp]
-    lib.scr_knn_curvature.argtypes = [i64, i32, vp, vp, vp, vp]
-    lib.scr_knn.restype = lib.scr_knn_curvature.restype = C.c_int
-    lib.scr_adam_step.argtypes = [i32, C.POINTER(AdamTensor), C.c_double, C.c_double, C.c_double, vp]
-    lib.scr_adam_step.restype = C.c_int
-    lib.scr_tv_add_grad.argtypes = [i32, C.POINTER(TvPlane), vp]
-    lib.scr_tv_add_grad.restype = C.c_int
-    lib.scr_copy_probe.argtypes = [vp, vp, C.c_size_t, vp]
-    lib.scr_copy_probe.restype = C.c_int
-    lib.scr_profile_enable.argtypes = [C.c_int]
-    lib.scr_profile_read.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    lib.scr_profile_kernel_name.argtypes = [C.c_int]
-    lib.scr_profile_kernel_name.restype = C.c_char_p
-    for f in ("scr_visible_filter", "scr_mark_visible", "scr_forward_plan", "scr_forward_run",
-              "scr_backward", "scr_debug_get"):
-        getattr(lib, f).restype = C.c_int
     return lib
 
 
@@ -258,7 +196,6 @@ class stage:
 
     def __exit__(self, *exc):
         if self.on:
-            import torch
             if torch.cuda.is_available():
                 torch.cuda.synchronize()
             lib.scr_marker_pop()
@@ -278,6 +215,28 @@ def check(rc):
         raise RuntimeError("splatco_raster: " + lib.scr_last_error().decode())
 
 
+def stream(device=None):
+    """The caller's current stream ON THE TENSORS' DEVICE (the process may have another device current).  Without a
+    device: the current device's, for calls made inside a `torch.cuda.device(...)` block."""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def ptr(t):
+    """A tensor argument: its device address, NULL for None or an empty tensor."""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def host_array(values, ctype=i32):
+    """A host array argument (the header's `*_host` parameters): int32 unless another ctype is given."""
+    values = list(values)
+    return (ctype * len(values))(*values)
+
+
+def ptr_array(tensors):
+    """A host array of the tensors' device addresses (the header's `void* const*` / `float* const*` parameters)."""
+    return host_array([t.data_ptr() for t in tensors], vp)
+
+
 def scratch_size(nbytes):
     """Size class of a large scratch request: above 32 MiB the next multiple of 1/8 of the power of two below it (eight
     classes per octave, at most 12.5 % more than asked).  The buffers behind these requests scale with the number of
@@ -293,7 +252,6 @@ def scratch_size(nbytes):
 
 def scratch(nbytes, device):
     """Uninitialised device bytes for a kernel's scratch / saved state, in scratch_size() classes."""
-    import torch
     return torch.empty(scratch_size(nbytes), dtype=torch.uint8, device=device)
 
 

@@ -8,7 +8,6 @@ work on it unchanged and checkpoints interchange with torch.optim.Adam.  What di
 launch of `scr_adam_step` (csrc/adam.hip) over parameter, gradient and moments -- at 20 M anchors that is 40 GB of
 traffic, priced against the copy probe.  weight_decay / amsgrad / maximize are not part of the reference's optimizer and
 are refused."""
-import ctypes as C
 import math
 
 import torch
@@ -69,7 +68,7 @@ class FusedAdam(torch.optim.Optimizer):
                 e.step_size = lr / (1.0 - b1 ** t)                     # doubles, as torch's Python forms them
                 e.bias_correction2_sqrt = math.sqrt(1.0 - b2 ** t)
             with torch.cuda.device(dev):
-                _C.check(_C.lib.scr_adam_step(len(ps), table, b1, b2, float(group["eps"]), torch.cuda.current_stream(dev).cuda_stream))
+                _C.check(_C.lib.scr_adam_step(len(ps), table, b1, b2, float(group["eps"]), _C.stream(dev)))
             for p in ps:                        # the update is queued for every tensor of the group: the step counts move together
                 self.state[p]["step"] += 1
         return loss
@@ -85,7 +84,7 @@ def _adam_apply(entries, beta1, beta2, eps, device):
         e.param, e.grad, e.exp_avg, e.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
         e.numel, e.step_size, e.bias_correction2_sqrt = p.numel(), step_size, bc2
     with torch.cuda.device(device):
-        _C.check(_C.lib.scr_adam_step(len(entries), table, beta1, beta2, eps, torch.cuda.current_stream(device).cuda_stream))
+        _C.check(_C.lib.scr_adam_step(len(entries), table, beta1, beta2, eps, _C.stream(device)))
 
 
 class ShardedFusedAdam:

@@ -4,7 +4,6 @@ concatenation that feeds FeaturePlanes' attribute branch.  Device tensors only."
 import torch
 
 from . import _C
-from .rasterizer import _stream
 
 
 import os
@@ -72,14 +71,12 @@ class DeferredDx:
     def materialise(self):
         """dx [V, width] as a real matrix (16-byte aligned rows) from the coefficients: for a producer that finds it cannot
         form the rows inside its own backward after all."""
-        from . import _C
-        from .rasterizer import _stream
         V, d = self.x.shape
         ld = (d + 3) // 4 * 4
         dx = torch.empty(V, ld, dtype=torch.float32, device=self.x.device)[:, :d]
         with torch.cuda.device(self.x.device):
             _C.check(_C.lib.scr_norm_linear_dx(V, d, self.x.data_ptr(), self.x.stride(0), self.dy.data_ptr(), self.dy.stride(0),
-                                               self.coef.data_ptr(), dx.data_ptr(), ld, _stream(self.x.device)))
+                                               self.coef.data_ptr(), dx.data_ptr(), ld, _C.stream(self.x.device)))
         return dx
 
     @staticmethod
@@ -109,7 +106,7 @@ class _AnchorGather(torch.autograd.Function):
             with torch.cuda.device(dev):
                 _C.check(_C.lib.scr_anchor_gather(V, idx.data_ptr(), anchor_feat.data_ptr(), anchor.data_ptr(),
                                                   offset.data_ptr(), scaling.data_ptr(), None, anc.data_ptr(),
-                                                  None, gs.data_ptr(), g72.data_ptr(), 72, stats.data_ptr(), _stream()))
+                                                  None, gs.data_ptr(), g72.data_ptr(), 72, stats.data_ptr(), _C.stream()))
         inv = getattr(idx, "_scr_inverse", None)       # left by expand.mask_indices: position of every anchor in idx, -1 = invisible
         if inv is not None and (inv.shape != (N,) or inv.device != dev):
             inv = None
@@ -143,7 +140,6 @@ class _AnchorGather(torch.autograd.Function):
         else:
             d_g_fea = p(d_g_fea)
         d_feat, d_anc, d_off, d_gs = p(d_feat), p(d_anc), p(d_off), p(d_gs)
-        ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
         sink = ctx.sink
         ranges = [(0, N)]
         if sink is not None:
@@ -163,9 +159,9 @@ class _AnchorGather(torch.autograd.Function):
                 # ones own consecutive upstream rows wherever the range starts (n0 is a multiple of 64)
                 if n1 > n0:
                     _C.check(_C.lib.scr_anchor_gather_backward(
-                        n1 - n0, V, inv.data_ptr() + 8 * n0, ptr(gs), ptr(d_feat), ptr(d_anc), ptr(d_off), ptr(d_gs),
-                        ptr(d_g_fea), ldg, g_feat.data_ptr() + 4 * 32 * n0, g_anchor.data_ptr() + 4 * 3 * n0,
-                        g_offset.data_ptr() + 4 * 30 * n0, g_scaling.data_ptr() + 4 * 6 * n0, accumulate, *nl, _stream(dev)))
+                        n1 - n0, V, inv.data_ptr() + 8 * n0, _C.ptr(gs), _C.ptr(d_feat), _C.ptr(d_anc), _C.ptr(d_off),
+                        _C.ptr(d_gs), _C.ptr(d_g_fea), ldg, g_feat.data_ptr() + 4 * 32 * n0, g_anchor.data_ptr() + 4 * 3 * n0,
+                        g_offset.data_ptr() + 4 * 30 * n0, g_scaling.data_ptr() + 4 * 6 * n0, accumulate, *nl, _C.stream(dev)))
                 if sink is not None and ranges is sink.ranges:
                     sink.on_range(r)
         if box is not None:

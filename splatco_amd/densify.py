@@ -46,9 +46,7 @@ def _knn_indices(points, k):
     goes to sklearn on the host); CPU tensors (the golden tests): brute force."""
     N = points.shape[0]
     if points.is_cuda:
-        import ctypes as C
         from . import _C
-        from .rasterizer import _stream
         if k > 16:
             raise ValueError("k <= 16")
         pts = points.detach().float().contiguous()
@@ -61,10 +59,10 @@ def _knn_indices(points, k):
         cell_start = torch.searchsorted(skey, torch.arange(ncell + 1, device=pts.device)).int()
         spts = pts.index_select(0, order).contiguous()
         out = torch.empty(N, k, dtype=torch.long, device=pts.device)
-        grid = (C.c_float * 7)(float(lo[0]), float(lo[1]), float(lo[2]), h, nx, ny, nz)
+        grid = _C.host_array((float(lo[0]), float(lo[1]), float(lo[2]), h, nx, ny, nz), _C.f32)
         with torch.cuda.device(pts.device):
             _C.check(_C.lib.scr_knn(N, k, grid, spts.data_ptr(), order.data_ptr(), cell_start.data_ptr(), out.data_ptr(),
-                                    _stream()))
+                                    _C.stream()))
         return out
     out = torch.empty(N, k, dtype=torch.long, device=points.device)
     step = max(1, (1 << 24) // max(N, 1))
@@ -80,11 +78,10 @@ def compute_curvature(points, k=10):
     idx = _knn_indices(pts, k)
     if pts.is_cuda:          # covariance + closed-form eigenvalues on the device (fp64), one thread per point
         from . import _C
-        from .rasterizer import _stream
         p32 = pts.float().contiguous()
         out = torch.empty(p32.shape[0], dtype=torch.float32, device=p32.device)
         with torch.cuda.device(p32.device):
-            _C.check(_C.lib.scr_knn_curvature(p32.shape[0], k, p32.data_ptr(), idx.data_ptr(), out.data_ptr(), _stream()))
+            _C.check(_C.lib.scr_knn_curvature(p32.shape[0], k, p32.data_ptr(), idx.data_ptr(), out.data_ptr(), _C.stream()))
         return out
     nb = pts[idx]                                                   # [N,k,3]
     c = nb - nb.mean(dim=1, keepdim=True)

@@ -51,7 +51,6 @@ class _L1Ssim(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y):
         from . import _C
-        from .rasterizer import _stream
         # whether the derivative maps are needed is a property of the INPUT: grad mode is off inside forward, so a
         # converted copy (non-contiguous crop, other dtype) would report requires_grad = False
         need = bool(ctx.needs_input_grad[0])
@@ -61,7 +60,7 @@ class _L1Ssim(torch.autograd.Function):
         out = torch.empty(2, dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):      # kernels launch on the CURRENT device: make it the tensors' device
             _C.check(_C.lib.scr_l1_ssim_forward(C, H, W, x.data_ptr(), y.data_ptr(), scratch.data_ptr(), int(need),
-                                                out.data_ptr(), _stream(x.device)))
+                                                out.data_ptr(), _C.stream(x.device)))
         ctx.save_for_backward(x, y, scratch)
         ctx.have_maps = need
         return out[0], out[1]
@@ -69,7 +68,6 @@ class _L1Ssim(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_l1, g_ssim):
         from . import _C
-        from .rasterizer import _stream
         x, y, scratch = ctx.saved_tensors
         if not ctx.have_maps:
             raise RuntimeError("l1_ssim backward without the derivative maps of the forward pass")
@@ -79,7 +77,7 @@ class _L1Ssim(torch.autograd.Function):
         dx = torch.empty_like(x)
         with torch.cuda.device(x.device):
             _C.check(_C.lib.scr_l1_ssim_backward(C, H, W, x.data_ptr(), y.data_ptr(), scratch.data_ptr(),
-                                                 g_l1.data_ptr(), g_ssim.data_ptr(), dx.data_ptr(), _stream(x.device)))
+                                                 g_l1.data_ptr(), g_ssim.data_ptr(), dx.data_ptr(), _C.stream(x.device)))
         return dx, None
 
 
@@ -90,7 +88,6 @@ class _PairL1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gen1, gen2, real1, real2):
         from . import _C
-        from .rasterizer import _stream
         c = lambda t: t.detach().contiguous().float()
         gen1, gen2, real1, real2 = c(gen1), c(gen2), c(real1), c(real2)
         n, dev = gen1.numel(), gen1.device
@@ -98,14 +95,13 @@ class _PairL1(torch.autograd.Function):
         out = torch.empty(1, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _C.check(_C.lib.scr_pair_l1_forward(n, gen1.data_ptr(), gen2.data_ptr(), real1.data_ptr(), real2.data_ptr(),
-                                                scratch.data_ptr(), out.data_ptr(), _stream(dev)))
+                                                scratch.data_ptr(), out.data_ptr(), _C.stream(dev)))
         ctx.save_for_backward(gen1, gen2, real1, real2)
         return out.reshape(())
 
     @staticmethod
     def backward(ctx, g):
         from . import _C
-        from .rasterizer import _stream
         gen1, gen2, real1, real2 = ctx.saved_tensors
         n, dev = gen1.numel(), gen1.device
         g = g.contiguous().float().reshape(1)
@@ -114,7 +110,7 @@ class _PairL1(torch.autograd.Function):
         with torch.cuda.device(dev):
             _C.check(_C.lib.scr_pair_l1_backward(n, gen1.data_ptr(), gen2.data_ptr(), real1.data_ptr(), real2.data_ptr(), g.data_ptr(),
                                                  None if d1 is None else d1.data_ptr(), None if d2 is None else d2.data_ptr(),
-                                                 _stream(dev)))
+                                                 _C.stream(dev)))
         return d1, d2, None, None
 
 
@@ -139,25 +135,23 @@ class _ScalingReg(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scaling):
         from . import _C
-        from .rasterizer import _stream
         s = scaling.detach().contiguous().float()
         P = s.shape[0]
         scratch = torch.empty(_C.lib.scr_scaling_reg_scratch_bytes(P), dtype=torch.uint8, device=s.device)
         out = torch.empty(1, dtype=torch.float32, device=s.device)
         with torch.cuda.device(s.device):
-            _C.check(_C.lib.scr_scaling_reg_forward(P, s.data_ptr(), scratch.data_ptr(), out.data_ptr(), _stream(s.device)))
+            _C.check(_C.lib.scr_scaling_reg_forward(P, s.data_ptr(), scratch.data_ptr(), out.data_ptr(), _C.stream(s.device)))
         ctx.save_for_backward(s)
         return out.reshape(())
 
     @staticmethod
     def backward(ctx, g):
         from . import _C
-        from .rasterizer import _stream
         (s,) = ctx.saved_tensors
         g = g.contiguous().float().reshape(1)
         d = torch.empty_like(s)
         with torch.cuda.device(s.device):
-            _C.check(_C.lib.scr_scaling_reg_backward(s.shape[0], s.data_ptr(), g.data_ptr(), d.data_ptr(), _stream(s.device)))
+            _C.check(_C.lib.scr_scaling_reg_backward(s.shape[0], s.data_ptr(), g.data_ptr(), d.data_ptr(), _C.stream(s.device)))
         return d
 
 
@@ -170,13 +164,12 @@ class _ScalingRegTap(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tap, scaling):
         from . import _C
-        from .rasterizer import _stream
         s = scaling.detach().contiguous().float()
         P = s.shape[0]
         scratch = torch.empty(_C.lib.scr_scaling_reg_scratch_bytes(P), dtype=torch.uint8, device=s.device)
         out = torch.empty(1, dtype=torch.float32, device=s.device)
         with torch.cuda.device(s.device):
-            _C.check(_C.lib.scr_scaling_reg_forward(P, s.data_ptr(), scratch.data_ptr(), out.data_ptr(), _stream(s.device)))
+            _C.check(_C.lib.scr_scaling_reg_forward(P, s.data_ptr(), scratch.data_ptr(), out.data_ptr(), _C.stream(s.device)))
         return out.reshape(())
 
     @staticmethod

@@ -4,7 +4,6 @@
 All functions take device fp32 images, return device tensors and make no host synchronisation.  None of them has a
 backward: they are evaluation metrics.  LPIPS is not here -- it needs pretrained VGG weights, which this project
 cannot obtain."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -29,8 +28,7 @@ def flip_filters(pixels_per_degree=DEFAULT_PPD):
     w = np.zeros(7 * nw, dtype=np.float64)
     radii = np.zeros(2, dtype=np.int32)
     sc = np.zeros(3, dtype=np.float64)
-    rc = _C.lib.scr_flip_filters(float(pixels_per_degree), w.ctypes.data_as(C.c_void_p), radii.ctypes.data_as(C.c_void_p),
-                                 sc.ctypes.data_as(C.c_void_p))
+    rc = _C.lib.scr_flip_filters(float(pixels_per_degree), w.ctypes.data, radii.ctypes.data, sc.ctypes.data)
     if rc != 0:
         raise ValueError("flip: " + _C.lib.scr_last_error().decode())
     rcsf, rfeat = int(radii[0]), int(radii[1])
@@ -63,7 +61,6 @@ def _pairs(test, reference, what):
 
 def _flip_run(test, reference, pixels_per_degree, quantize, return_map):
     from . import _C
-    from .rasterizer import _stream
     (t, r), single = _pairs(test, reference, "flip")
     N, _, H, W = t.shape
     dev = t.device
@@ -74,7 +71,7 @@ def _flip_run(test, reference, pixels_per_degree, quantize, return_map):
     with torch.cuda.device(dev):
         rc = _C.lib.scr_flip_forward(N, H, W, t.data_ptr(), r.data_ptr(), float(pixels_per_degree), int(bool(quantize)),
                                      scratch.data_ptr(), mean.data_ptr(), mse.data_ptr(),
-                                     None if fmap is None else fmap.data_ptr(), _stream(dev))
+                                     None if fmap is None else fmap.data_ptr(), _C.stream(dev))
     if rc != 0:
         raise ValueError("flip: " + _C.lib.scr_last_error().decode())
     if single:
@@ -124,7 +121,6 @@ def ssim_value(a, b):
     """Mean SSIM (11x11 Gaussian window, sigma 1.5, zero padding; losses.ssim, utils/loss_utils.py) of two [3,H,W]
     device images as a 0-d device tensor: the forward of the fused L1 + SSIM kernel without its derivative maps."""
     from . import _C
-    from .rasterizer import _stream
     if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or a.shape != b.shape or a.dim() != 3:
         raise ValueError("ssim_value: expected two [C,H,W] images of one shape")
     if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
@@ -137,5 +133,5 @@ def ssim_value(a, b):
     out = torch.empty(2, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _C.check(_C.lib.scr_l1_ssim_forward(Cc, H, W, x.data_ptr(), y.data_ptr(), scratch.data_ptr(), 0, out.data_ptr(),
-                                            _stream(x.device)))
+                                            _C.stream(x.device)))
     return out[1]

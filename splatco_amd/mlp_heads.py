@@ -9,7 +9,6 @@ gradients in HBM.  fp32 MFMA on the device; there is no CPU path.
 import torch
 
 from . import _C
-from .rasterizer import _stream
 
 
 def supported(pc, feat, geo_a, geo_b=None):
@@ -45,7 +44,7 @@ class _MlpHeads(torch.autograd.Function):
             with torch.cuda.device(dev):
                 _C.check(_C.lib.scr_mlp_heads_forward(V, feat.data_ptr(), feat.stride(0), anchor.data_ptr(), campos.data_ptr(), geo_a.data_ptr(),
                                                       geo_b.data_ptr(), *[t.data_ptr() for t in ws], hidden.data_ptr(), out_o.data_ptr(),
-                                                      out_c.data_ptr(), out_v.data_ptr(), _stream()))
+                                                      out_c.data_ptr(), out_v.data_ptr(), _C.stream()))
         ctx.save_for_backward(feat, anchor, campos, geo_a, geo_b, ws[0], ws[2], ws[4], ws[6], hidden, out_o, out_c)
         return out_o, out_c, out_v
 
@@ -70,7 +69,7 @@ class _MlpHeads(torch.autograd.Function):
                     w2c.data_ptr(), w2v.data_ptr(), hidden.data_ptr(), out_o.data_ptr(), out_c.data_ptr(), g_o.data_ptr(),
                     g_c.data_ptr(), g_v.data_ptr(), partial.data_ptr(), d_feat.data_ptr(), d_anchor.data_ptr(),
                     d_geo_a.data_ptr(), d_geo_b.data_ptr(), d_w1.data_ptr(), d_b1.data_ptr(), d_w2o.data_ptr(), d_b2o.data_ptr(), d_w2c.data_ptr(),
-                    d_b2c.data_ptr(), d_w2v.data_ptr(), d_b2v.data_ptr(), _stream()))
+                    d_b2c.data_ptr(), d_w2v.data_ptr(), d_b2v.data_ptr(), _C.stream()))
         return d_feat, d_anchor, None, d_geo_a, d_geo_b, d_w1, d_b1, d_w2o, d_b2o, d_w2c, d_b2c, d_w2v, d_b2v
 
 

@@ -11,7 +11,6 @@ import torch
 import torch.nn.functional as F
 
 from . import _C
-from .rasterizer import _stream
 
 
 def _channel_mlp(avg, mx, w1, w2):
@@ -36,7 +35,7 @@ class _AttendedPairs(torch.autograd.Function):
         avg, mx = torch.empty(C3, device=dev), torch.empty(C3, device=dev)
         arg = torch.empty(C3, dtype=torch.int32, device=dev)
         _C.check(_C.lib.scr_tpa_stats(R, H, W, *(p.data_ptr() for p in planes), avg.data_ptr(), mx.data_ptr(),
-                                      arg.data_ptr(), scratch.data_ptr(), _stream()))
+                                      arg.data_ptr(), scratch.data_ptr(), _C.stream()))
         ca = _channel_mlp(avg, mx, w1.detach().float(), w2.detach().float()).contiguous()
         wcc = wc.detach().contiguous().float()
         s = torch.empty(2, H, W, device=dev)
@@ -44,7 +43,7 @@ class _AttendedPairs(torch.autograd.Function):
         sa = torch.empty(H, W, device=dev)
         out = [torch.empty(1, 2 * R, H, W, device=dev) for _ in range(3)]
         _C.check(_C.lib.scr_tpa_forward(R, H, W, *(p.data_ptr() for p in planes), ca.data_ptr(), wcc.data_ptr(),
-                                        s.data_ptr(), am.data_ptr(), sa.data_ptr(), *(o.data_ptr() for o in out), _stream()))
+                                        s.data_ptr(), am.data_ptr(), sa.data_ptr(), *(o.data_ptr() for o in out), _C.stream()))
         ctx.save_for_backward(*planes, w1, w2, wcc, avg, mx, arg, ca, s, am, sa)
         ctx.dims = (R, H, W)
         return tuple(out)
@@ -66,14 +65,14 @@ class _AttendedPairs(torch.autograd.Function):
         _C.check(_C.lib.scr_tpa_backward(R, H, W, p0.data_ptr(), p1.data_ptr(), p2.data_ptr(), ca.data_ptr(), wcc.data_ptr(),
                                          s.data_ptr(), am.data_ptr(), sa.data_ptr(), *(g.data_ptr() for g in gs),
                                          *(t.data_ptr() for t in d), dca.data_ptr(), dw.data_ptr(), scratch.data_ptr(),
-                                         _stream()))
+                                         _C.stream()))
         # the 15-number MLP and its sigmoid: re-run under autograd (a dozen tiny kernels)
         with torch.enable_grad():
             a_, m_ = avg.detach().requires_grad_(True), mx.detach().requires_grad_(True)
             w1_, w2_ = w1.detach().float().requires_grad_(True), w2.detach().float().requires_grad_(True)
             davg, dmx, dw1, dw2 = torch.autograd.grad(_channel_mlp(a_, m_, w1_, w2_), (a_, m_, w1_, w2_), dca)
         _C.check(_C.lib.scr_tpa_backward_stats(R, H, W, davg.contiguous().data_ptr(), dmx.contiguous().data_ptr(),
-                                               arg.data_ptr(), *(t.data_ptr() for t in d), _stream()))
+                                               arg.data_ptr(), *(t.data_ptr() for t in d), _C.stream()))
         return d[0], d[1], d[2], dw1.reshape(w1.shape), dw2.reshape(w2.shape), dw.reshape(1, 2, 7, 7)
 
 

@@ -44,10 +44,6 @@ def _dev_f32(t, name):
     return t
 
 
-def _ptr(t):
-    return None if t is None or t.numel() == 0 else t.data_ptr()
-
-
 class _CSettings:
     """Keeps the device tensors alive next to the C struct that points at them."""
 
@@ -71,15 +67,6 @@ class _CSettings:
         return C.byref(self.c)
 
 
-def _stream(device=None):
-    """The caller's current stream ON THE TENSORS' DEVICE (the process may have another device current)."""
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _bytes(n, device):
-    return _C.scratch(n, device)
-
-
 class RasterState:
     """Per-call saved buffers (opaque to Python) + what the debug getters need."""
     __slots__ = ("P", "M", "I", "max_tile", "flags", "cs", "geom", "binning", "image", "radii")
@@ -100,8 +87,8 @@ class RasterState:
         out = torch.empty(shape, dtype=dt, device=dev)
         if out.numel():
           with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_debug_get(which, self.P, self.I, self.cs.H, self.cs.W, _ptr(self.geom),
-                                          _ptr(self.binning), _ptr(self.image), out.data_ptr(), _stream()))
+            _C.check(_C.lib.scr_debug_get(which, self.P, self.I, self.cs.H, self.cs.W, _C.ptr(self.geom),
+                                          _C.ptr(self.binning), _C.ptr(self.image), out.data_ptr(), _C.stream()))
         return out
 
 
@@ -116,8 +103,8 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
     M = 0 if shs is None else shs.shape[1]
     st = RasterState()
     st.P, st.M, st.cs = P, M, cs
-    st.geom = _bytes(_C.lib.scr_geom_bytes(P, cs.H, cs.W), dev)
-    st.image = _bytes(_C.lib.scr_image_bytes(cs.H, cs.W), dev)
+    st.geom = _C.scratch(_C.lib.scr_geom_bytes(P, cs.H, cs.W), dev)
+    st.image = _C.scratch(_C.lib.scr_image_bytes(cs.H, cs.W), dev)
     radii = torch.empty(P, dtype=torch.int32, device=dev)      # every entry is written by preprocess_kernel
     color = torch.empty(3, cs.H, cs.W, dtype=torch.float32, device=dev)
     plan = (C.c_int64 * 4)(0, 0, 0, 0)   # (tile instances, largest per-tile instance count, phase 2 already ran, plan flags)
@@ -131,20 +118,20 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
         if SPECULATE and guess is not None and guess[0] > 0 and 0.5 <= P / guess[0] <= 2.0:
             scale = 1.06 * P / guess[0]
             cap = _C.lib.scr_binning_bytes(min(int(guess[1] * scale) + 4096, (1 << 32) - 2), max(int(guess[2] * 1.25), guess[2] + 64))
-            spec = _bytes(cap, dev)
-        _C.check(_C.lib.scr_forward_plan_run(P, M, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(cov3D_precomp),
-                                             _ptr(opacities), _ptr(shs), _ptr(colors_precomp), cs.ref(),
-                                             st.geom.data_ptr(), _ptr(radii), plan, None if spec is None else spec.data_ptr(),
-                                             0 if spec is None else spec.numel(), st.image.data_ptr(), color.data_ptr(), _stream()))
+            spec = _C.scratch(cap, dev)
+        _C.check(_C.lib.scr_forward_plan_run(P, M, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D_precomp),
+                                             _C.ptr(opacities), _C.ptr(shs), _C.ptr(colors_precomp), cs.ref(),
+                                             st.geom.data_ptr(), _C.ptr(radii), plan, None if spec is None else spec.data_ptr(),
+                                             0 if spec is None else spec.numel(), st.image.data_ptr(), color.data_ptr(), _C.stream()))
         st.I, st.max_tile, st.flags = int(plan[0]), int(plan[1]), int(plan[3])
         _plan_guess[key] = (P, st.I, st.max_tile)
         if plan[2]:
             st.binning = spec
         else:
             del spec
-            st.binning = _bytes(_C.lib.scr_binning_bytes(st.I, st.max_tile), dev)
+            st.binning = _C.scratch(_C.lib.scr_binning_bytes(st.I, st.max_tile), dev)
             _C.check(_C.lib.scr_forward_run(P, st.I, st.max_tile, st.flags, cs.ref(), st.geom.data_ptr(), st.binning.data_ptr(),
-                                            st.image.data_ptr(), color.data_ptr(), _stream()))
+                                            st.image.data_ptr(), color.data_ptr(), _C.stream()))
     st.radii = radii
     return color, radii, st
 
@@ -227,14 +214,14 @@ class _RasterizeGaussians(torch.autograd.Function):
         if g_sh is not None:
             g_sh = g_sh.view(P, st.M, 3)
         del arena, parts
-        scratch = _bytes(_C.lib.scr_backward_scratch_bytes(st.I), dev)
+        scratch = _C.scratch(_C.lib.scr_backward_scratch_bytes(st.I), dev)
         try:
           with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_backward(P, st.M, st.I, st.flags, _ptr(means3D), _ptr(scales), _ptr(rotations), _ptr(cov3D),
-                                         _ptr(sh), cs.ref(), st.radii.data_ptr(), st.geom.data_ptr(),
+            _C.check(_C.lib.scr_backward(P, st.M, st.I, st.flags, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D),
+                                         _C.ptr(sh), cs.ref(), st.radii.data_ptr(), st.geom.data_ptr(),
                                          st.binning.data_ptr(), st.image.data_ptr(), g.data_ptr(), scratch.data_ptr(),
-                                         g_means3D.data_ptr(), g_means2D.data_ptr(), _ptr(g_col), _ptr(g_sh),
-                                         g_op.data_ptr(), _ptr(g_scales), _ptr(g_rot), _ptr(g_cov), _stream()))
+                                         g_means3D.data_ptr(), g_means2D.data_ptr(), _C.ptr(g_col), _C.ptr(g_sh),
+                                         g_op.data_ptr(), _C.ptr(g_scales), _C.ptr(g_rot), _C.ptr(g_cov), _C.stream()))
         except RuntimeError as e:
             if ctx.raster_settings.debug:
                 raise RuntimeError(str(e) + _debug_dump("snapshot_bw.dump", ctx.raster_settings, means3D=means3D, sh=sh,
@@ -270,7 +257,7 @@ class GaussianRasterizer(nn.Module):
             view = _dev_f32(self.raster_settings.viewmatrix, "viewmatrix")
             if P:
                 with torch.cuda.device(positions.device):
-                    _C.check(_C.lib.scr_mark_visible(P, positions.data_ptr(), view.data_ptr(), out.data_ptr(), _stream()))
+                    _C.check(_C.lib.scr_mark_visible(P, positions.data_ptr(), view.data_ptr(), out.data_ptr(), _C.stream()))
             return out.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -299,6 +286,6 @@ class GaussianRasterizer(nn.Module):
             radii = torch.empty(P, dtype=torch.int32, device=means3D.device)  # filter_kernel writes every entry
             if P:
                 with torch.cuda.device(means3D.device):
-                    _C.check(_C.lib.scr_visible_filter(P, means3D.data_ptr(), _ptr(scales), _ptr(rotations),
-                                                       _ptr(cov3D_precomp), cs.ref(), radii.data_ptr(), _stream()))
+                    _C.check(_C.lib.scr_visible_filter(P, means3D.data_ptr(), _C.ptr(scales), _C.ptr(rotations),
+                                                       _C.ptr(cov3D_precomp), cs.ref(), radii.data_ptr(), _C.stream()))
             return radii

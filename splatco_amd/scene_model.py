@@ -121,7 +121,6 @@ class _NormLinearFn(torch.autograd.Function):
         ctx.defer = defer if ctx.fused else None      # anchor_gather.DeferredDx: the producer of x forms dx in ITS backward
         if ctx.fused:
             from . import _C
-            from .rasterizer import _stream
             V, d = x.shape
             Gc, cc = G.detach().contiguous(), c.detach().contiguous().float()
             y = torch.empty(V, 32, dtype=torch.float32, device=x.device)
@@ -134,7 +133,7 @@ class _NormLinearFn(torch.autograd.Function):
                 _C.check(_C.lib.scr_norm_linear_forward(V, d, x.data_ptr(), x.stride(0), Gc.data_ptr(), cc.data_ptr(), float(eps),
                                                         y.data_ptr(), mean.data_ptr(), var.data_ptr(), inv.data_ptr(),
                                                         scratch.data_ptr(), col_stats.data_ptr() if ok_stats else None,
-                                                        col_stats.shape[0] if ok_stats else 0, _stream()))
+                                                        col_stats.shape[0] if ok_stats else 0, _C.stream()))
             ctx.save_for_backward(x, Gc, mean, inv)
             ctx.mark_non_differentiable(mean, var)
             return y, mean, var
@@ -152,7 +151,6 @@ class _NormLinearFn(torch.autograd.Function):
         V = x.shape[0]
         if ctx.fused:
             from . import _C
-            from .rasterizer import _stream
             d = x.shape[1]
             if dy.dtype != torch.float32 or dy.stride(1) != 1 or dy.stride(0) % 4 or dy.data_ptr() % 16:
                 dy = dy.contiguous().float()
@@ -168,7 +166,7 @@ class _NormLinearFn(torch.autograd.Function):
                 _C.check(_C.lib.scr_norm_linear_backward(V, d, x.data_ptr(), x.stride(0), dy.data_ptr(), dy.stride(0), G.data_ptr(),
                                                          mean.data_ptr(), inv.data_ptr(), dx.data_ptr() if dx is not None else None,
                                                          ldx, dG.data_ptr(), dc.data_ptr(), scratch.data_ptr(),
-                                                         coef.data_ptr() if coef is not None else None, _stream()))
+                                                         coef.data_ptr() if coef is not None else None, _C.stream()))
             if defer is not None:
                 # the producer of x (the anchor gather) forms dx = k0 + x k1 + dy Gi inside its own backward kernel: it gets the
                 # coefficients, and autograd a gradient of zeros that occupies no memory (anchor_gather.DeferredDx)
@@ -190,11 +188,6 @@ class _NormLinearFn(torch.autograd.Function):
         return dx, H, sdy, None, None, None
 
 
-def _ptr_table(tensors):
-    import ctypes as C
-    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
 class _NormFold(torch.autograd.Function):
     """(G [32, d], c [32]) of sum_i Linear_i(BatchNorm_i(.)) from the pairs' parameters, as ONE launch per direction
     (csrc/normlinear.hip nl_fold_kernel / nl_fold_backward_kernel) instead of ~15 framework kernels on 32 x 71 numbers
@@ -202,30 +195,26 @@ class _NormFold(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, d, widths, cols, col_at, *tensors):
-        import ctypes as C
         from . import _C
-        from .rasterizer import _stream
         L, dev = len(widths), tensors[0].device
-        at = None if col_at is None else (C.c_uint8 * d)(*col_at)
+        at = None if col_at is None else _C.host_array(col_at, _C.u8)
         ts = [t.detach().contiguous().float() for t in tensors]
         W, b, ga, be = ts[0::4], ts[1::4], ts[2::4], ts[3::4]
         G, c = torch.empty(32, d, device=dev), torch.empty(32, device=dev)
-        wi, ci = (C.c_int32 * L)(*widths), (C.c_int32 * L)(*cols)
+        wi, ci = _C.host_array(widths), _C.host_array(cols)
         with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_norm_fold(L, d, wi, ci, at, _ptr_table(W), _ptr_table(b), _ptr_table(ga), _ptr_table(be),
-                                          G.data_ptr(), c.data_ptr(), _stream(dev)))
+            _C.check(_C.lib.scr_norm_fold(L, d, wi, ci, at, _C.ptr_array(W), _C.ptr_array(b), _C.ptr_array(ga), _C.ptr_array(be),
+                                          G.data_ptr(), c.data_ptr(), _C.stream(dev)))
         ctx.save_for_backward(*W, *ga, *be)
         ctx.meta = (d, tuple(widths), tuple(cols), None if col_at is None else tuple(col_at))
         return G, c
 
     @staticmethod
     def backward(ctx, dG, dc):
-        import ctypes as C
         from . import _C
-        from .rasterizer import _stream
         d, widths, cols, col_at = ctx.meta
         L = len(widths)
-        at = None if col_at is None else (C.c_uint8 * d)(*col_at)
+        at = None if col_at is None else _C.host_array(col_at, _C.u8)
         saved = ctx.saved_tensors
         W, ga, be = saved[:L], saved[L:2 * L], saved[2 * L:]
         dev = W[0].device
@@ -234,11 +223,11 @@ class _NormFold(torch.autograd.Function):
         dW = [torch.empty_like(w) for w in W]
         db = [torch.empty(32, device=dev) for _ in range(L)]
         dga, dbe = [torch.empty_like(g) for g in ga], [torch.empty_like(g) for g in be]
-        wi, ci = (C.c_int32 * L)(*widths), (C.c_int32 * L)(*cols)
+        wi, ci = _C.host_array(widths), _C.host_array(cols)
         with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_norm_fold_backward(L, d, wi, ci, at, _ptr_table(W), _ptr_table(ga), _ptr_table(be), dG.data_ptr(),
-                                                   dc.data_ptr(), _ptr_table(dW), _ptr_table(db), _ptr_table(dga),
-                                                   _ptr_table(dbe), _stream(dev)))
+            _C.check(_C.lib.scr_norm_fold_backward(L, d, wi, ci, at, _C.ptr_array(W), _C.ptr_array(ga), _C.ptr_array(be), dG.data_ptr(),
+                                                   dc.data_ptr(), _C.ptr_array(dW), _C.ptr_array(db), _C.ptr_array(dga),
+                                                   _C.ptr_array(dbe), _C.stream(dev)))
         out = []
         for i in range(L):
             out += [dW[i], db[i], dga[i], dbe[i]]
@@ -292,17 +281,15 @@ def _norm_linear(x, bns, linears, col_at=None):
         track = [bn for bn in bns if bn.track_running_stats and bn.training]
         if on_device and len(track) == len(bns) and all(bn.momentum is not None for bn in bns) and mean.is_cuda:
             # nn.BatchNorm1d's running-statistics update for all pairs in one launch (six tiny kernels per BatchNorm otherwise)
-            import ctypes as C
             from . import _C
-            from .rasterizer import _stream
             L = len(bns)
             with torch.cuda.device(x.device):
                 _C.check(_C.lib.scr_norm_running_stats(
-                    L, d, (C.c_int32 * L)(*widths), (C.c_int32 * L)(*cols),
-                    None if col_at is None else (C.c_uint8 * d)(*[int(v) for v in col_at]),
-                    (C.c_float * L)(*[float(bn.momentum) for bn in bns]),
-                    _ptr_table([bn.running_mean for bn in bns]), _ptr_table([bn.running_var for bn in bns]),
-                    _ptr_table([bn.num_batches_tracked for bn in bns]), mean.data_ptr(), var.data_ptr(), n, _stream(x.device)))
+                    L, d, _C.host_array(widths), _C.host_array(cols),
+                    None if col_at is None else _C.host_array([int(v) for v in col_at], _C.u8),
+                    _C.host_array([float(bn.momentum) for bn in bns], _C.f32),
+                    _C.ptr_array([bn.running_mean for bn in bns]), _C.ptr_array([bn.running_var for bn in bns]),
+                    _C.ptr_array([bn.num_batches_tracked for bn in bns]), mean.data_ptr(), var.data_ptr(), n, _C.stream(x.device)))
             return y
         if col_at is not None:                     # statistics back in the reference's column order
             if at_idx is None:
@@ -401,15 +388,13 @@ class PlaneGrid(nn.Module):                   # scene/grids.py:102-201
         (scr_box_coords: the same IEEE operations in the same order) instead of four."""
         p = xyz.reshape(-1, 3)
         if p.is_cuda and p.dtype == torch.float32 and not p.requires_grad and p.shape[0] > 0:
-            import ctypes as C
             from . import _C
-            from .rasterizer import _stream
             b = self.bounds_key()
             p = p.contiguous()
             out = torch.empty_like(p)
             with torch.cuda.device(p.device):
-                _C.check(_C.lib.scr_box_coords(p.shape[0], p.data_ptr(), (C.c_float * 3)(*b[:3]), (C.c_float * 3)(*b[3:]),
-                                               out.data_ptr(), _stream(p.device)))
+                _C.check(_C.lib.scr_box_coords(p.shape[0], p.data_ptr(), _C.host_array(b[:3], _C.f32), _C.host_array(b[3:], _C.f32),
+                                               out.data_ptr(), _C.stream(p.device)))
             return out
         return (p - self.xyz_min) / (self.xyz_max - self.xyz_min) * 2 - 1
 

@@ -15,7 +15,6 @@ Fixture: tests/golden/training_statis.npz (captured from the reference's own fun
 import torch
 
 from . import _C
-from .rasterizer import _stream
 
 
 def _need_cuda(*ts):
@@ -58,7 +57,7 @@ def statis_increments(n_offsets, viewspace_point_grad, opacity, update_filter, o
                                                upd.data_ptr() if upd.numel() else None,
                                                grad.data_ptr() if grad.numel() else None,
                                                grad.shape[1] if grad.dim() == 2 else 2,
-                                               inc_op.data_ptr(), inc_g.data_ptr(), _stream()))
+                                               inc_op.data_ptr(), inc_g.data_ptr(), _C.stream()))
     return inc_op, inc_g
 
 
@@ -77,7 +76,7 @@ def statis_apply(opacity_accum, anchor_demon, offset_gradient_accum, offset_deno
         with torch.cuda.device(opacity_accum.device):
             _C.check(_C.lib.scr_statis_apply(V, int(n_offsets), visible_index.data_ptr(), inc_opacity.data_ptr(),
                                              inc_grad.data_ptr(), opacity_accum.data_ptr(), anchor_demon.data_ptr(),
-                                             offset_gradient_accum.data_ptr(), offset_denom.data_ptr(), _stream()))
+                                             offset_gradient_accum.data_ptr(), offset_denom.data_ptr(), _C.stream()))
     return accs
 
 

@@ -12,7 +12,6 @@ The sample positions get no gradient: the reference detaches them (scene/gaussia
 import torch
 
 from . import _C
-from .rasterizer import _stream
 
 # (column of ind holding grid-x -> last plane dim, column holding grid-y) for xy / xz / yz (scene/grids.py:148-150)
 _PAIRS = ((1, 0), (2, 0), (2, 1))
@@ -39,30 +38,27 @@ def _forward_into(out, ind, cols, planes):
                 p = p.contiguous()
                 rp = torch.empty(p.shape[2] - 1, p.shape[3], 2, R, dtype=torch.float32, device=p.device)
                 with torch.cuda.device(p.device):
-                    _C.check(_C.lib.scr_plane_row_pairs(R, p.shape[2], p.shape[3], p.data_ptr(), rp.data_ptr(), _stream(p.device)))
+                    _C.check(_C.lib.scr_plane_row_pairs(R, p.shape[2], p.shape[3], p.data_ptr(), rp.data_ptr(), _C.stream(p.device)))
                 return rp
             xy, xz, yz = pairs(xy), pairs(xz), pairs(yz)
         else:
             xy, xz, yz = (p.contiguous() for p in (xy, xz, yz))
         _C.check(_C.lib.scr_triplane_forward(V, ind.data_ptr(), ind.stride(0), xy.data_ptr(), xz.data_ptr(), yz.data_ptr(),
                                              R, X, Y, Z, cl, out.data_ptr(), out.stride(0), cols[t], cols[t + 1], cols[t + 2],
-                                             _stream()))
+                                             _C.stream()))
 
 
 def _backward_from(g, ind, cols, shapes):
     """Gradients of the planes of one grid (3 or 6 planes; planes j and j + 3 -- plain / attended,
     scene/grids.py:174-181 -- are sampled at the same positions): the three projections x (1 or 2) planes go
     through ONE pass over the points.  g [V, ld] (unit column stride) is read in place."""
-    import ctypes as C
     V, n = ind.shape[0], len(shapes)
     R, X, Y, Z = shapes[0][1], shapes[0][2], shapes[0][3], shapes[1][3]
     gp = [torch.empty(s, dtype=torch.float32, device=g.device) for s in shapes]
     scratch = torch.empty(_C.scratch_size(_C.lib.scr_triplane_backward_scratch_bytes(V, X, Y, Z, R * (n // 3))), dtype=torch.uint8,
                           device=g.device)
-    c_cols = (C.c_int32 * n)(*cols)
-    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in gp])
     _C.check(_C.lib.scr_triplane_backward(V, ind.data_ptr(), ind.stride(0), R, X, Y, Z, n // 3, g.data_ptr(), g.stride(0),
-                                          c_cols, ptrs, scratch.data_ptr(), _stream()))
+                                          _C.host_array(cols), _C.ptr_array(gp), scratch.data_ptr(), _C.stream()))
     return gp
 
 
@@ -128,7 +124,6 @@ def _backward_all(ctx, g, inds, nl=None):
     """All grids of the op in ONE pass over the points (scr_triplane_backward_multi) when they were sampled at the same
     coordinates (the same tensor), each is a plain triple, their column blocks lie back to back in standard order and
     the library knows the channel layout; None otherwise (the caller goes grid by grid)."""
-    import ctypes as C
     ng = len(ctx.meta)
     if not FUSE_GRIDS or ng > 3 or any(i.data_ptr() != inds[0].data_ptr() or i.shape != inds[0].shape or i.stride() != inds[0].stride() for i in inds):
         return None
@@ -141,11 +136,10 @@ def _backward_all(ctx, g, inds, nl=None):
     if not all(ctx.needs_input_grad[3:][j] for j in range(len(ctx.needs_input_grad) - 3) if j % 4 != 0):
         return None                                          # a plane without a gradient: the per-grid path skips whole grids
     ind, V = inds[0], inds[0].shape[0]
-    arr = lambda v: (C.c_int32 * ng)(*v)
-    cR, cX, cY, cZ, ccol = arr(R), arr(X), arr(Y), arr(Z), arr(col)
+    cR, cX, cY, cZ, ccol = map(_C.host_array, (R, X, Y, Z, col))
     dev = ind.device
     gp = [torch.empty(s, dtype=torch.float32, device=dev) for shapes in ctx.shapes for s in shapes]
-    ptrs = (C.c_void_p * (3 * ng))(*[t.data_ptr() for t in gp])
+    ptrs = _C.ptr_array(gp)
     nlargs = (None, None, 0, None, 0) if nl is None else (nl.coef.data_ptr(), nl.dy.data_ptr(), nl.dy.stride(0), nl.x.data_ptr(),
                                                         nl.x.stride(0))
     with torch.cuda.device(dev):
@@ -153,7 +147,7 @@ def _backward_all(ctx, g, inds, nl=None):
         scratch = _C.scratch(max(int(nbytes), 16), dev)
         rc = _C.lib.scr_triplane_backward_multi(V, ind.data_ptr(), ind.stride(0), ng, cR, cX, cY, cZ, ccol,
                                                 None if g is None else g.data_ptr(), 0 if g is None else g.stride(0), ptrs,
-                                                scratch.data_ptr(), *nlargs, _stream())
+                                                scratch.data_ptr(), *nlargs, _C.stream())
     if rc == 3:
         return None
     _C.check(rc)
@@ -225,5 +219,5 @@ class _PlaneSample(torch.autograd.Function):
         with torch.cuda.device(g.device):
             _C.check(_C.lib.scr_plane_sample_backward(V, grid.data_ptr(), 2, 0, 1, R, A, B, 1, g.data_ptr(), g.data_ptr(),
                                                       g.stride(0), grad_plane.data_ptr(), grad_plane.data_ptr(),
-                                                      scratch.data_ptr(), _stream(g.device)))
+                                                      scratch.data_ptr(), _C.stream(g.device)))
         return grad_plane, None

@@ -10,8 +10,6 @@ gives grid `level` of the ACTIVE levels the weight w * 0.5^(2 - level); PlaneGri
 Here: the closed-form derivative, one launch of scr_tv_add_grad (csrc/tv.hip) for all planes of all active grids, no
 autograd graph.  The term is a function of the parameters only -- in a sharded step it must be added ONCE, after the
 gradient SUM, identically on every rank (train_step.collaborative_step does that).  No CPU path."""
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -64,7 +62,7 @@ def tv_add_grad(entries):
         e.channels, e.rows, e.cols = p.shape[1], p.shape[2], p.shape[3]
         e.coef = tv_coef(w)
     with torch.cuda.device(dev):
-        _C.check(_C.lib.scr_tv_add_grad(len(entries), table, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _C.check(_C.lib.scr_tv_add_grad(len(entries), table, _C.stream(dev)))
 
 
 def feature_planes_tv(feat, w):

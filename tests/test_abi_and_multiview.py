@@ -42,6 +42,82 @@ def test_c_abi_exports_every_declared_symbol():
     assert set(_C.SYMBOLS) == declared
 
 
+_SCALARS = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+            "float": ctypes.c_float, "double": ctypes.c_double, "uint8_t": ctypes.c_uint8, "char": ctypes.c_char}
+_STRUCTS = {"scr_settings": "Settings", "scr_adam_tensor": "AdamTensor", "scr_tv_plane": "TvPlane"}
+
+
+def _c_type(decl):
+    """'const float* const* grad_planes' -> ('float', 2): base type and pointer depth (qualifiers and name dropped)."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    return next(w for w in words if w != "*"), words.count("*")
+
+
+def _binds(base, depth, got):
+    """Whether ctypes type `got` passes a C `base` with `depth` pointers: scalars and structs exactly, char* as c_char_p,
+    any other pointer as c_void_p or a POINTER of the matching type."""
+    from splatco_amd import _C
+    if depth == 0:
+        return got is (getattr(_C, _STRUCTS[base]) if base in _STRUCTS else _SCALARS.get(base, object()))
+    if base == "char" and depth == 1:
+        return got is ctypes.c_char_p
+    if got is ctypes.c_void_p:
+        return True
+    return isinstance(got, type) and issubclass(got, ctypes._Pointer) and _binds(base, depth - 1, got._type_)
+
+
+def test_c_abi_binding_matches_the_header():
+    """_C.SIGNATURES, the three structs and the copied constants against include/splatco_raster.h: a prototype, field or
+    value changed in the header without the binding fails here, on a CPU, instead of passing garbage arguments on the GPU."""
+    from splatco_amd import _C
+    hdr = open(os.path.join(ROOT, "include", "splatco_raster.h")).read()
+    hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    defines = {k: int(v) for k, v in re.findall(r"^\s*#\s*define\s+(\w+)\s+(-?\d+)\s*$", hdr, flags=re.M)}
+    code = re.sub(r"^\s*#[^\n]*", "", hdr, flags=re.M)
+
+    enums, value = {}, 0
+    for body in re.findall(r"\benum\s*\{(.*?)\}\s*;", code, flags=re.S):
+        for item in filter(None, (s.strip() for s in body.split(","))):
+            name, _, v = (s.strip() for s in item.partition("="))
+            value = int(v) if v else value
+            enums[name] = value
+            value += 1
+    consts = {**defines, **enums}
+    assert _C.ABI_VERSION == consts["SCR_ABI_VERSION"] and _C.FLIP_MAX_RADIUS == consts["SCR_FLIP_MAX_RADIUS"]
+    assert _C.PROF_COUNT == consts["SCR_PROF_COUNT"]
+    copied = {k for k in vars(_C) if k.startswith(("PLAN_", "DBG_"))}
+    assert copied == {k[4:] for k in consts if k.startswith(("SCR_PLAN_", "SCR_DBG_"))}
+    for k in copied:
+        assert getattr(_C, k) == consts["SCR_" + k], k
+
+    structs = re.findall(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", code, flags=re.S)
+    assert sorted(tag for tag, _, _ in structs) == sorted(_STRUCTS)
+    for tag, body, _ in structs:
+        fields = []
+        for decl in filter(None, (s.strip() for s in body.split(";"))):
+            first, *more = decl.split(",")                  # `int32_t channels, rows, cols;`
+            typ, name = re.match(r"(.*?)(\w+)$", first.strip()).groups()
+            base, depth = _c_type(typ)
+            fields.append((name, base, depth))
+            fields += [(m.replace("*", "").strip(), base, m.count("*")) for m in more]
+        cls = getattr(_C, _STRUCTS[tag])
+        assert [f[0] for f in cls._fields_] == [f[0] for f in fields], tag
+        for (name, got), (_, base, depth) in zip(cls._fields_, fields):
+            assert _binds(base, depth, got), f"{tag}.{name}: {got.__name__} does not bind {base}{'*' * depth}"
+
+    rest = re.sub(r"typedef\s+struct.*?\}\s*\w+\s*;|\benum\s*\{.*?\}\s*;", "", code, flags=re.S)
+    protos = re.findall(r"([A-Za-z_][\w\s*]*?)\b(scr_\w+)\s*\(([^()]*)\)\s*;", rest)
+    assert [name for _, name, _ in protos] == _C.SYMBOLS, "SIGNATURES must list the header's functions in header order"
+    for (ret, name, params), (_, restype, *argtypes) in zip(protos, _C.SIGNATURES):
+        params = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+        assert len(argtypes) == len(params), f"{name}: {len(argtypes)} argtypes for {len(params)} parameters"
+        assert _binds(*_c_type(ret), restype), f"{name}: restype {restype.__name__} does not bind {ret.strip()}"
+        for i, (p, got) in enumerate(zip(params, argtypes)):
+            assert _binds(*_c_type(p), got), f"{name} parameter {i} `{p}`: {got.__name__}"
+        f = getattr(_C.lib, name)
+        assert f.restype is restype and list(f.argtypes) == argtypes, f"{name}: not bound from SIGNATURES"
+
+
 def test_stage_markers_are_off_by_default_and_load_roctx_on_demand():
     """scr_markers_enable (ABI 27): nothing is loaded before the first enable; enabled, the C-ABI ranges and the host-side
     stage() ranges push and pop in pairs (roctx without a profiler attached is a no-op library); disabled again, stage() is
