@@ -16,7 +16,8 @@
  *   - Plain C, no exceptions, no torch types.  Every pointer is a DEVICE pointer unless the
  *     name ends in `_host`.  All arrays are contiguous fp32 / int32 / uint32 as stated.
  *   - `stream` is a hipStream_t passed as void*.  Nothing synchronises the device; the only host waits
- *     are the ones that return a data-dependent count (scr_forward_plan: num_rendered; scr_expand_plan; scr_mask_index_plan):
+ *     are the ones that return a data-dependent count (scr_forward_plan: num_rendered; scr_expand_plan; scr_mask_index_plan;
+ *     scr_voxel_unique_plan):
  *     the kernel posts the count to a pinned mailbox the calling thread polls, with a copy +
  *     hipStreamSynchronize as fallback (and a sync + error check after every kernel when settings.debug != 0).
  *   - The caller allocates every buffer (sizes from the scr_*_bytes queries), so several forward graphs
@@ -36,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SCR_ABI_VERSION 28
+#define SCR_ABI_VERSION 29
 #define SCR_TILE 16 /* 16x16-pixel tiles: part of the result contract (tile rects, ranges, sort keys) */
 
 /* The 12 fields of GaussianRasterizationSettings, same order (gaussian_renderer/__init__.py:145-158).
@@ -504,6 +505,37 @@ int scr_tv_add_grad(int32_t n_planes, const scr_tv_plane* planes, void* stream);
 int scr_knn(int64_t N, int32_t k, const float* grid_host, const float* sorted_pts, const int64_t* sorted_id,
             const int32_t* cell_start, int64_t* out_idx, void* stream);
 int scr_knn_curvature(int64_t N, int32_t k, const float* points, const int64_t* idx, float* curvature, void* stream);
+
+/* ---- a scene from a point cloud (ABI 29): GaussianModel.create_from_pcd (scene/gaussian_model.py:472-508) without the
+ * host row sort of voxelize_sample (:447-451) and without simple_knn.  Semantics: splatco_amd/scene_init.py.
+ *
+ * scr_points_bounds: out7 (DEVICE floats) = min x, y, z, max x, y, z of points[N,3] and a flag that is > 0 when a coordinate
+ * is NaN or infinite (which min / max ignore); scratch: scr_points_bounds_scratch_bytes(N) bytes.  Plain reductions.
+ *
+ * scr_voxel_keys: q = rint(points / voxel_size) per component in binary32.  lo_host[3] (HOST int32) = rint(min / voxel_size)
+ * of every axis.  packed != 0: out[N] = (qx - lo_x) << 42 | (qy - lo_y) << 21 | (qz - lo_z) -- the caller has checked
+ * that every axis spans fewer than 2^21 voxels; packed == 0: out[N,3] = q itself.  The caller checks |q| < 2^31 on the
+ * bounding box and sorts the keys.
+ * scr_voxel_unique_plan counts the distinct keys of the SORTED key array (one stream synchronisation, like
+ * scr_expand_plan; scratch: scr_voxel_unique_scratch_bytes(N) bytes, passed on to _run); scr_voxel_unique_run writes
+ * out_xyz[num_unique,3] = float(q) * voxel_size in key order.
+ *
+ * scr_knn3_dist2: out[N] = mean of the squared distances to the 3 nearest OTHER points (exact duplicates count, at 0):
+ * d = (ex*ex + ey*ey) + ez*ez, ((b0 + b1) + b2) / 3 of the three smallest, no contraction -- equal to a brute force bit
+ * for bit.  grid_host[8] = x0, y0, z0, cell size h, nx, ny, nz, slack (HOST floats; slack >= the rounding error of the
+ * cell function, as a length); scr_knn3_cell_keys writes every point's cell (z * ny + y) * nx + x; the caller sorts the
+ * points by it (sorted_pts[N,3], sorted_id[N] = original index, cell_start[nx*ny*nz + 1]).  N >= 4. */
+size_t scr_points_bounds_scratch_bytes(int64_t N);
+int scr_points_bounds(int64_t N, const float* points, void* scratch, float* out7, void* stream);
+size_t scr_voxel_unique_scratch_bytes(int64_t N);
+int scr_voxel_keys(int64_t N, const float* points, float voxel_size, const int32_t* lo_host, int32_t packed, int64_t* out,
+                   void* stream);
+int scr_voxel_unique_plan(int64_t N, const int64_t* sorted_keys, void* scratch, int64_t* num_unique_host, void* stream);
+int scr_voxel_unique_run(int64_t N, const int64_t* sorted_keys, const void* scratch, float voxel_size,
+                         const int32_t* lo_host, float* out_xyz, void* stream);
+int scr_knn3_cell_keys(int64_t N, const float* grid_host, const float* points, int64_t* keys, void* stream);
+int scr_knn3_dist2(int64_t N, const float* grid_host, const float* sorted_pts, const int64_t* sorted_id,
+                   const int32_t* cell_start, float* out, void* stream);
 
 /* ---- measurement aid: a float4 grid-stride copy of `bytes` bytes (src -> dst, device pointers).  bench.py times it to
  * quote the HBM bandwidth a streaming kernel reaches on the box next to the 8 TB/s datasheet figure. */

@@ -1109,6 +1109,99 @@ int scr_knn_curvature(int64_t N, int32_t k, const float* points, const int64_t* 
     return 0;
 }
 
+// ---- a scene from a point cloud (scene_init.hip)
+size_t scr_voxel_unique_scratch_bytes(int64_t N) { return align_up((voxel_unique_nwg(N > 0 ? N : 1) + 1) * 4) + 256; }
+
+size_t scr_points_bounds_scratch_bytes(int64_t N) { return align_up(points_bounds_nwg(N > 0 ? N : 1) * 8 * sizeof(float)); }
+
+int scr_points_bounds(int64_t N, const float* points, void* scratch, float* out7, void* stream) {
+    SCR_MARK_FN;
+    if (N <= 0 || N >= (1ll << 31)) return fail("scr_points_bounds: need 0 < N < 2^31");
+    if (!points || !scratch || !out7) return fail("scr_points_bounds: NULL argument");
+    launch_points_bounds(N, points, (float*)scratch, out7, (hipStream_t)stream);
+    CHECK_LAUNCH("points_bounds_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+static int check_voxel_args(const char* who, int64_t N, float voxel_size, const int32_t* lo_host) {
+    if (N <= 0 || N >= (1ll << 31)) return fail("%s: need 0 < N < 2^31", who);
+    if (!(voxel_size > 0.0f) || !(voxel_size <= 3.0e38f)) return fail("%s: voxel_size must be positive and finite", who);
+    if (!lo_host) return fail("%s: lo_host is NULL", who);
+    return 0;
+}
+
+int scr_voxel_keys(int64_t N, const float* points, float voxel_size, const int32_t* lo_host, int32_t packed, int64_t* out,
+                   void* stream) {
+    SCR_MARK_FN;
+    if (check_voxel_args("scr_voxel_keys", N, voxel_size, lo_host)) return 1;
+    if (!points || !out) return fail("scr_voxel_keys: NULL argument");
+    launch_voxel_keys(N, points, voxel_size, lo_host, packed != 0, out, (hipStream_t)stream);
+    CHECK_LAUNCH("voxel_keys_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+int scr_voxel_unique_plan(int64_t N, const int64_t* sorted_keys, void* scratch, int64_t* num_unique_host, void* stream) {
+    SCR_MARK_FN;
+    if (!num_unique_host) return fail("num_unique_host is NULL");
+    *num_unique_host = 0;
+    if (N <= 0 || N >= (1ll << 31)) return fail("scr_voxel_unique_plan: need 0 < N < 2^31");
+    if (!sorted_keys || !scratch) return fail("scr_voxel_unique_plan: NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* wg = (uint32_t*)scratch;
+    unsigned long long* total = (unsigned long long*)((char*)scratch + align_up((voxel_unique_nwg(N) + 1) * 4));
+    Mailbox& mb = mailbox();
+    const unsigned long long seq = ++mb.seq;
+    launch_voxel_unique_count(N, sorted_keys, wg, total, mb.dev, seq, st);
+    CHECK_LAUNCH("voxel_unique_count_kernel", 0, st);
+    unsigned long long t = 0;
+    if (mailbox_wait(mb, seq, false, st)) {
+        t = mb.host[0];
+    } else {
+        HIP_TRY(hipMemcpyAsync(&t, total, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    *num_unique_host = (int64_t)t;
+    return 0;
+}
+
+int scr_voxel_unique_run(int64_t N, const int64_t* sorted_keys, const void* scratch, float voxel_size,
+                         const int32_t* lo_host, float* out_xyz, void* stream) {
+    SCR_MARK_FN;
+    if (check_voxel_args("scr_voxel_unique_run", N, voxel_size, lo_host)) return 1;
+    if (!sorted_keys || !scratch || !out_xyz) return fail("scr_voxel_unique_run: NULL argument");
+    launch_voxel_unique_write(N, sorted_keys, (const uint32_t*)scratch, voxel_size, lo_host, out_xyz, (hipStream_t)stream);
+    CHECK_LAUNCH("voxel_unique_write_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+static int check_knn3_grid(const char* who, int64_t N, const float* g) {
+    if (N <= 0 || N >= (1ll << 31)) return fail("%s: need 0 < N < 2^31", who);
+    if (!g) return fail("%s: grid_host is NULL", who);
+    if (!(g[3] > 0.0f) || g[4] < 1 || g[5] < 1 || g[6] < 1 || !(g[7] >= 0.0f)) return fail("%s: bad grid", who);
+    if ((double)g[4] * g[5] * g[6] >= 2147483647.0) return fail("%s: more than 2^31 - 2 cells", who);
+    return 0;
+}
+
+int scr_knn3_cell_keys(int64_t N, const float* grid_host, const float* points, int64_t* keys, void* stream) {
+    SCR_MARK_FN;
+    if (check_knn3_grid("scr_knn3_cell_keys", N, grid_host)) return 1;
+    if (!points || !keys) return fail("scr_knn3_cell_keys: NULL argument");
+    launch_knn3_cell_keys(N, grid_host, points, keys, (hipStream_t)stream);
+    CHECK_LAUNCH("knn3_cell_keys_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+int scr_knn3_dist2(int64_t N, const float* grid_host, const float* sorted_pts, const int64_t* sorted_id,
+                   const int32_t* cell_start, float* out, void* stream) {
+    SCR_MARK_FN;
+    if (check_knn3_grid("scr_knn3_dist2", N, grid_host)) return 1;
+    if (N < 4) return fail("scr_knn3_dist2: fewer than 4 points");
+    if (!sorted_pts || !sorted_id || !cell_start || !out) return fail("scr_knn3_dist2: NULL argument");
+    launch_knn3_dist2(N, grid_host, sorted_pts, sorted_id, cell_start, out, (hipStream_t)stream);
+    CHECK_LAUNCH("knn3_dist2_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
 int scr_copy_probe(const void* src, void* dst, size_t bytes, void* stream) {
     SCR_MARK_FN;
     if (!src || !dst || bytes < 16) return fail("NULL argument");

@@ -411,6 +411,20 @@ void launch_anchor_gather_backward(int64_t N, int64_t V, const int64_t* inv, con
 void launch_knn(int64_t N, int k, const float* grid9, const float* sorted_pts, const int64_t* sorted_id,
                 const int32_t* cell_start, int64_t* out_idx, hipStream_t st);
 void launch_knn_curvature(int64_t N, int k, const float* pts, const int64_t* idx, float* curvature, hipStream_t st);
+// scene_init.hip: voxelisation and the fused 3-NN mean squared distance
+void launch_wg_scan(uint32_t nwg, uint32_t* wg_count, unsigned long long* total, unsigned long long* mailbox,
+                    unsigned long long seq, hipStream_t st);
+size_t points_bounds_nwg(int64_t N);
+void launch_points_bounds(int64_t N, const float* pts, float* partial, float* out, hipStream_t st);
+size_t voxel_unique_nwg(int64_t n);
+void launch_voxel_keys(int64_t N, const float* pts, float v, const int32_t* lo, int packed, int64_t* out, hipStream_t st);
+void launch_voxel_unique_count(int64_t n, const int64_t* keys, uint32_t* wg_count, unsigned long long* total,
+                               unsigned long long* mailbox, unsigned long long seq, hipStream_t st);
+void launch_voxel_unique_write(int64_t n, const int64_t* keys, const uint32_t* wg_offset, float v, const int32_t* lo,
+                               float* out, hipStream_t st);
+void launch_knn3_cell_keys(int64_t N, const float* grid8, const float* pts, int64_t* keys, hipStream_t st);
+void launch_knn3_dist2(int64_t N, const float* grid8, const float* sorted_pts, const int64_t* sorted_id,
+                       const int32_t* cell_start, float* out, hipStream_t st);
 size_t norm_linear_scratch_bytes(int64_t V);
 int launch_norm_linear_forward(int64_t V, int d, const float* x, int ldx, const float* G, const float* c, float eps, float* y,
                                float* mean, float* var, float* inv, void* scratch, const float* stats, int stat_rows,

@@ -300,6 +300,11 @@ void launch_mask_count(int64_t n, const uint8_t* mask, uint32_t* wg_count, unsig
     mask_count_kernel<<<nwg, EXP_THREADS, 0, st>>>(n, mask, wg_count);
     expand_scan_kernel<<<1, 1024, 0, st>>>(nwg, wg_count, total, mailbox, seq);
 }
+// the scan pass alone, for compactions whose count kernel lives in another file (scene_init.hip)
+void launch_wg_scan(uint32_t nwg, uint32_t* wg_count, unsigned long long* total, unsigned long long* mailbox,
+                    unsigned long long seq, hipStream_t st) {
+    expand_scan_kernel<<<1, 1024, 0, st>>>(nwg, wg_count, total, mailbox, seq);
+}
 void launch_mask_index(int64_t n, const uint8_t* mask, const uint32_t* wg_offset, int64_t* index, int64_t* inverse,
                        hipStream_t st) {
     const uint32_t nwg = (uint32_t)((n + EXP_PER_WG - 1) / EXP_PER_WG);

@@ -1,0 +1,314 @@
+// splatco_amd/csrc/scene_init.hip -- a scene from a point cloud on the device (gfx950): the kernels behind
+// splatco_amd/scene_init.py (GaussianModel.create_from_pcd / voxelize_sample, scene/gaussian_model.py:447-451,472-508,
+// and simple_knn's distCUDA2, whose source is not in the reference tree -- the arithmetic below is this project's
+// specification of it, see scene_init.py).
+//
+//   points_bounds   per-axis min / max and a non-finite flag of the cloud (12 B read per point).
+//   voxel_keys      q = rint(p / v) per component (binary32 division, round half to even); packed: one 63-bit key
+//                   (qx - lo_x) << 42 | (qy - lo_y) << 21 | (qz - lo_z), whose integer order is the lexicographic order
+//                   of (qx, qy, qz) -- what np.unique(axis=0) returns; unpacked (an axis needs more than 21 bits): the
+//                   three integers, for the caller's lexicographic row sort.  12 B read, 8 B written per point.
+//   voxel_unique    on the SORTED keys: head flags (key[i] != key[i-1]), wave ballot + mbcnt compaction with the
+//                   expansion's count / scan / write scheme (expand.hip), decode to float32(q) * v.  8 B read per key in
+//                   each pass, 12 B written per survivor.
+//   knn3_dist2      mean of the squared distances to the 3 nearest OTHER points, fused: the points come bucketed in a
+//                   uniform grid (knn3_cell_keys, sorted by the caller), one thread per query in cell order walks the
+//                   cube of cells around its own -- each x-run of cells is ONE contiguous range of the sorted points --
+//                   keeping three distances in registers, and grows the cube shell by shell until the third-best
+//                   distance lies inside it.  Writes 4 B per point; no index array, no gather.
+//
+// Arithmetic order is normative (-ffp-contract=off): e = p_j - p_i, d = (ex*ex + ey*ey) + ez*ez, ((b0 + b1) + b2) / 3.
+// The three smallest VALUES are unique whatever the tie-breaking, so the result is independent of the search order and
+// bit-identical to a brute force.  No atomics.
+#include "common.h"
+
+#include <math.h>
+
+namespace scr {
+
+constexpr int SI_THREADS = 256;
+constexpr int SI_ITEMS = 4;
+constexpr int SI_PER_WG = SI_THREADS * SI_ITEMS;      // keys per workgroup of the unique passes
+
+__device__ __forceinline__ uint32_t si_lanes_below64(unsigned long long ballot) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+}
+
+// ------------------------------------------------------------------ bounding box
+// min / max of every axis and a non-finite flag, in two passes of plain reductions (no atomics): torch.aminmax(dim=0) of a
+// [10 M, 3] tensor took 5 ms of the 6.6 ms of a whole voxelize call (profiles/r07_scene_init.txt).  fminf / fmaxf drop a
+// NaN, so the flag is what reports it.
+constexpr int SI_BOUNDS_PER_WG = SI_THREADS * 16;     // points per workgroup of the first pass
+
+struct Bounds7 { float v[7]; };       // min x, y, z, max x, y, z, flag (> 0: a coordinate is NaN or infinite)
+
+__device__ __forceinline__ void bounds_merge(Bounds7& a, const Bounds7& b) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { a.v[c] = fminf(a.v[c], b.v[c]); a.v[3 + c] = fmaxf(a.v[3 + c], b.v[3 + c]); }
+    a.v[6] = fmaxf(a.v[6], b.v[6]);
+}
+
+// the workgroup's merged value, valid in thread 0
+__device__ __forceinline__ Bounds7 bounds_reduce_wg(Bounds7 a) {
+    __shared__ float part[SI_THREADS / WAVE][7];
+#pragma unroll
+    for (int d = WAVE / 2; d >= 1; d >>= 1) {
+        Bounds7 o;
+#pragma unroll
+        for (int c = 0; c < 7; ++c) o.v[c] = __shfl_xor(a.v[c], d, WAVE);
+        bounds_merge(a, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) part[threadIdx.x >> 6][c] = a.v[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < SI_THREADS / WAVE; ++w) {
+            Bounds7 o;
+#pragma unroll
+            for (int c = 0; c < 7; ++c) o.v[c] = part[w][c];
+            bounds_merge(a, o);
+        }
+    }
+    return a;
+}
+
+__device__ __forceinline__ Bounds7 bounds_identity() {
+    Bounds7 a;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { a.v[c] = INFINITY; a.v[3 + c] = -INFINITY; }
+    a.v[6] = 0.0f;
+    return a;
+}
+
+__global__ void __launch_bounds__(SI_THREADS)
+points_bounds_kernel(int64_t N, const float* __restrict__ pts, float* __restrict__ partial) {
+    Bounds7 a = bounds_identity();
+    const int64_t base = (int64_t)blockIdx.x * SI_BOUNDS_PER_WG + threadIdx.x;
+#pragma unroll 4
+    for (int j = 0; j < SI_BOUNDS_PER_WG / SI_THREADS; ++j) {
+        const int64_t i = base + (int64_t)j * SI_THREADS;
+        if (i < N) {
+            Bounds7 o;
+            o.v[0] = o.v[3] = pts[3 * i]; o.v[1] = o.v[4] = pts[3 * i + 1]; o.v[2] = o.v[5] = pts[3 * i + 2];
+            o.v[6] = (fabsf(o.v[0]) <= 3.4028235e38f && fabsf(o.v[1]) <= 3.4028235e38f && fabsf(o.v[2]) <= 3.4028235e38f) ? 0.0f : 1.0f;
+            bounds_merge(a, o);
+        }
+    }
+    a = bounds_reduce_wg(a);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) partial[(size_t)blockIdx.x * 8 + c] = a.v[c];
+    }
+}
+
+__global__ void __launch_bounds__(SI_THREADS)
+points_bounds_final_kernel(int64_t nwg, const float* __restrict__ partial, float* __restrict__ out) {
+    Bounds7 a = bounds_identity();
+    for (int64_t w = threadIdx.x; w < nwg; w += SI_THREADS) {
+        Bounds7 o;
+#pragma unroll
+        for (int c = 0; c < 7; ++c) o.v[c] = partial[(size_t)w * 8 + c];
+        bounds_merge(a, o);
+    }
+    a = bounds_reduce_wg(a);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) out[c] = a.v[c];
+    }
+}
+
+size_t points_bounds_nwg(int64_t N) { return (size_t)((N + SI_BOUNDS_PER_WG - 1) / SI_BOUNDS_PER_WG); }
+
+void launch_points_bounds(int64_t N, const float* pts, float* partial, float* out, hipStream_t st) {
+    const size_t nwg = points_bounds_nwg(N);
+    points_bounds_kernel<<<(unsigned)nwg, SI_THREADS, 0, st>>>(N, pts, partial);
+    points_bounds_final_kernel<<<1, SI_THREADS, 0, st>>>((int64_t)nwg, partial, out);
+}
+
+// ------------------------------------------------------------------ voxel keys
+__global__ void __launch_bounds__(SI_THREADS)
+voxel_keys_kernel(int64_t N, const float* __restrict__ pts, float v, int lox, int loy, int loz, int packed,
+                  int64_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * SI_THREADS + threadIdx.x;
+    if (i >= N) return;
+    const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+    // |q| < 2^31 and, packed, 0 <= q - lo < 2^21: the caller checked both on the cloud's bounding box (rint(x / v) is
+    // monotone in x)
+    const int64_t qx = (int64_t)rintf(x / v), qy = (int64_t)rintf(y / v), qz = (int64_t)rintf(z / v);
+    if (packed) {
+        out[i] = ((qx - lox) << 42) | ((qy - loy) << 21) | (qz - loz);
+    } else {
+        out[3 * i] = qx; out[3 * i + 1] = qy; out[3 * i + 2] = qz;
+    }
+}
+
+__device__ __forceinline__ bool si_head(const int64_t* __restrict__ keys, int64_t i, int64_t n) {
+    // key[i - 1] from a clamped index, so that the load does not sit behind the branch
+    const int64_t k = keys[min(i, n - 1)], kp = keys[min(max(i - 1, (int64_t)0), n - 1)];
+    return i < n && (i == 0 || k != kp);
+}
+
+__global__ void __launch_bounds__(SI_THREADS)
+voxel_unique_count_kernel(int64_t n, const int64_t* __restrict__ keys, uint32_t* __restrict__ wg_count) {
+    __shared__ uint32_t wsum[SI_THREADS / WAVE];
+    uint32_t c = 0;
+#pragma unroll
+    for (int r = 0; r < SI_ITEMS; ++r) {
+        const int64_t i = (int64_t)blockIdx.x * SI_PER_WG + r * SI_THREADS + threadIdx.x;
+        c += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(si_head(keys, i, n)));
+    }
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;      // every lane of a wave holds the wave's count
+    __syncthreads();
+    if (threadIdx.x == 0) wg_count[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+__global__ void __launch_bounds__(SI_THREADS)
+voxel_unique_write_kernel(int64_t n, const int64_t* __restrict__ keys, const uint32_t* __restrict__ wg_offset, float v,
+                          int lox, int loy, int loz, float* __restrict__ out) {
+    __shared__ uint32_t wcnt[SI_ITEMS][SI_THREADS / WAVE];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    bool keep[SI_ITEMS];
+    uint32_t below[SI_ITEMS];
+#pragma unroll
+    for (int r = 0; r < SI_ITEMS; ++r) {
+        const int64_t i = (int64_t)blockIdx.x * SI_PER_WG + r * SI_THREADS + threadIdx.x;
+        keep[r] = si_head(keys, i, n);
+        const unsigned long long b = __builtin_amdgcn_ballot_w64(keep[r]);
+        below[r] = si_lanes_below64(b);
+        if (lane == 0) wcnt[r][w] = (uint32_t)__builtin_popcountll(b);
+    }
+    __syncthreads();
+    uint32_t base = wg_offset[blockIdx.x];
+#pragma unroll
+    for (int r = 0; r < SI_ITEMS; ++r) {
+        uint32_t before = 0;
+#pragma unroll
+        for (int q = 0; q < SI_THREADS / WAVE; ++q) before += q < w ? wcnt[r][q] : 0u;
+        const int64_t i = (int64_t)blockIdx.x * SI_PER_WG + r * SI_THREADS + threadIdx.x;
+        if (keep[r]) {
+            const int64_t k = keys[i];
+            const size_t o = 3 * (size_t)(base + before + below[r]);
+            out[o] = (float)((int)(k >> 42) + lox) * v;
+            out[o + 1] = (float)((int)((k >> 21) & 0x1fffff) + loy) * v;
+            out[o + 2] = (float)((int)(k & 0x1fffff) + loz) * v;
+        }
+#pragma unroll
+        for (int q = 0; q < SI_THREADS / WAVE; ++q) base += wcnt[r][q];
+    }
+}
+
+void launch_voxel_keys(int64_t N, const float* pts, float v, const int32_t* lo, int packed, int64_t* out, hipStream_t st) {
+    voxel_keys_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, st>>>(N, pts, v, lo[0], lo[1], lo[2],
+                                                                                          packed, out);
+}
+
+size_t voxel_unique_nwg(int64_t n) { return (size_t)((n + SI_PER_WG - 1) / SI_PER_WG); }
+
+void launch_voxel_unique_count(int64_t n, const int64_t* keys, uint32_t* wg_count, unsigned long long* total,
+                               unsigned long long* mailbox, unsigned long long seq, hipStream_t st) {
+    const uint32_t nwg = (uint32_t)voxel_unique_nwg(n);
+    voxel_unique_count_kernel<<<nwg, SI_THREADS, 0, st>>>(n, keys, wg_count);
+    launch_wg_scan(nwg, wg_count, total, mailbox, seq, st);
+}
+
+void launch_voxel_unique_write(int64_t n, const int64_t* keys, const uint32_t* wg_offset, float v, const int32_t* lo,
+                               float* out, hipStream_t st) {
+    voxel_unique_write_kernel<<<(uint32_t)voxel_unique_nwg(n), SI_THREADS, 0, st>>>(n, keys, wg_offset, v, lo[0], lo[1],
+                                                                                   lo[2], out);
+}
+
+// ------------------------------------------------------------------ fused 3-NN mean squared distance
+struct Knn3Grid {
+    float x0, y0, z0, inv_h, h, slack;
+    int nx, ny, nz;
+};
+
+static Knn3Grid knn3_grid(const float* g8) {
+    Knn3Grid g;
+    g.x0 = g8[0]; g.y0 = g8[1]; g.z0 = g8[2]; g.h = g8[3]; g.inv_h = 1.0f / g8[3];
+    g.nx = (int)g8[4]; g.ny = (int)g8[5]; g.nz = (int)g8[6]; g.slack = g8[7];
+    return g;
+}
+
+// the ONE cell function: the bucketing kernel and the search both call it, so a point's bucket is the cell the search
+// believes it is in
+__device__ __forceinline__ int knn3_cell(float v, float lo, float inv_h, int n) {
+    const int c = (int)floorf((v - lo) * inv_h);
+    return c < 0 ? 0 : (c >= n ? n - 1 : c);
+}
+
+__global__ void __launch_bounds__(SI_THREADS)
+knn3_cell_keys_kernel(int64_t N, Knn3Grid gr, const float* __restrict__ pts, int64_t* __restrict__ keys) {
+    const int64_t i = (int64_t)blockIdx.x * SI_THREADS + threadIdx.x;
+    if (i >= N) return;
+    const int cx = knn3_cell(pts[3 * i], gr.x0, gr.inv_h, gr.nx), cy = knn3_cell(pts[3 * i + 1], gr.y0, gr.inv_h, gr.ny),
+              cz = knn3_cell(pts[3 * i + 2], gr.z0, gr.inv_h, gr.nz);
+    keys[i] = ((int64_t)cz * gr.ny + cy) * gr.nx + cx;
+}
+
+// sorted_pts: the points in cell order; sorted_id[s]: original index of sorted point s; cell_start[ncells + 1].
+// out[original index] = ((b0 + b1) + b2) / 3 of the three smallest squared distances to OTHER points (by position:
+// an exact duplicate is another point, at distance 0).
+__global__ void __launch_bounds__(SI_THREADS)
+knn3_dist2_kernel(int64_t N, Knn3Grid gr, const float* __restrict__ sorted_pts, const int64_t* __restrict__ sorted_id,
+                  const int32_t* __restrict__ cell_start, float* __restrict__ out) {
+    const int64_t s = (int64_t)blockIdx.x * SI_THREADS + threadIdx.x;      // position in cell order: neighbours in memory
+    if (s >= N) return;
+    const float qx = sorted_pts[3 * s], qy = sorted_pts[3 * s + 1], qz = sorted_pts[3 * s + 2];
+    const int cx = knn3_cell(qx, gr.x0, gr.inv_h, gr.nx), cy = knn3_cell(qy, gr.y0, gr.inv_h, gr.ny),
+              cz = knn3_cell(qz, gr.z0, gr.inv_h, gr.nz);
+    float b0 = INFINITY, b1 = INFINITY, b2 = INFINITY;      // the three best so far, ascending
+    // the cells of one (y, z) row are contiguous in the sorted points: one range per row of the cube
+    auto scan = [&](int64_t row, int xa, int xb) {
+        const int p1 = cell_start[row + xb + 1];
+        for (int p = cell_start[row + xa]; p < p1; ++p) {
+            const float ex = sorted_pts[3 * (int64_t)p] - qx, ey = sorted_pts[3 * (int64_t)p + 1] - qy,
+                        ez = sorted_pts[3 * (int64_t)p + 2] - qz;
+            const float d = p == s ? INFINITY : (ex * ex + ey * ey) + ez * ez;
+            float t = d;                                    // branch-free insertion into the ascending triple
+            const float n0 = fminf(b0, t); t = fmaxf(b0, t);
+            const float n1 = fminf(b1, t); t = fmaxf(b1, t);
+            b2 = fminf(b2, t); b1 = n1; b0 = n0;
+        }
+    };
+    // distance from the query to the faces of its own cell, in cells: the cube of radius r reaches at least (r + that) * h
+    const float fx = (qx - gr.x0) * gr.inv_h - (float)cx, fy = (qy - gr.y0) * gr.inv_h - (float)cy,
+                fz = (qz - gr.z0) * gr.inv_h - (float)cz;
+    const float margin = gr.h * fminf(fminf(fminf(fx, 1.0f - fx), fminf(fy, 1.0f - fy)), fminf(fz, 1.0f - fz));
+    const int rmax = max(gr.nx, max(gr.ny, gr.nz));
+    for (int r = 1; r <= rmax; ++r) {                       // r = 1 takes the whole 3x3x3 cube, r > 1 the cube's surface
+        for (int dz = -r; dz <= r; ++dz) {
+            const int z = cz + dz;
+            if (z < 0 || z >= gr.nz) continue;
+            for (int dy = -r; dy <= r; ++dy) {
+                const int y = cy + dy;
+                if (y < 0 || y >= gr.ny) continue;
+                const int64_t row = ((int64_t)z * gr.ny + y) * gr.nx;
+                if (r == 1 || dz == -r || dz == r || dy == -r || dy == r) {
+                    scan(row, max(cx - r, 0), min(cx + r, gr.nx - 1));
+                } else {
+                    if (cx - r >= 0) scan(row, cx - r, cx - r);
+                    if (cx + r < gr.nx) scan(row, cx + r, cx + r);
+                }
+            }
+        }
+        // every point closer than `reach` has been seen; slack: the rounding of the cell function (scene_init.py)
+        const float reach = (float)r * gr.h + margin - gr.slack;
+        if (reach > 0.0f && b2 <= reach * reach) break;
+    }
+    out[sorted_id[s]] = ((b0 + b1) + b2) / 3.0f;
+}
+
+void launch_knn3_cell_keys(int64_t N, const float* grid8, const float* pts, int64_t* keys, hipStream_t st) {
+    knn3_cell_keys_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, st>>>(N, knn3_grid(grid8), pts, keys);
+}
+
+void launch_knn3_dist2(int64_t N, const float* grid8, const float* sorted_pts, const int64_t* sorted_id,
+                       const int32_t* cell_start, float* out, hipStream_t st) {
+    knn3_dist2_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, st>>>(N, knn3_grid(grid8), sorted_pts,
+                                                                                          sorted_id, cell_start, out);
+}
+
+}  // namespace scr
