@@ -315,7 +315,10 @@ class ChannelAttention(nn.Module):            # scene/grids.py:22-36
 
     def forward(self, x):
         # global average / max pool (AdaptiveAvgPool2d(1) / AdaptiveMaxPool2d(1)); amax instead of
-        # adaptive_max_pool2d: same value, 2.5 ms -> 0.05 ms on a [1,15,700,700] stack on MI355X
+        # adaptive_max_pool2d: same value, 2.5 ms -> 0.05 ms on a [1,15,700,700] stack on MI355X.
+        # Not the same GRADIENT at a tie: amax's backward splits it between equal maxima, the reference's
+        # AdaptiveMaxPool2d(1) and csrc/attention.hip send all of it to the FIRST maximum (pinned by
+        # tests/test_f64_refs_host.py and tests/test_gpu_f64_parity.py; this mirror is off that contract at ties)
         avg = self.sharedMLP(x.mean(dim=(2, 3), keepdim=True))
         mx = self.sharedMLP(x.amax(dim=(2, 3), keepdim=True))
         return torch.sigmoid(avg + mx)

@@ -1,0 +1,324 @@
+"""Float64 references of the three anchor-path operators between the sampler and the rasterizer, and the inputs the
+parity tests feed them.  TEST INFRASTRUCTURE ONLY; nothing here imports the native library.
+
+  heads_f64       the three Linear-ReLU-Linear heads on x = cat(feat, ob_view, geo_fea)      -> checker of csrc/mlp_heads.hip
+  attention_f64   TriPlaneAttention + chunk + cat(plane, attended plane)                     -> checker of csrc/attention.hip
+  expand_f64      torch_restatements.expand_torch_chain on double inputs                     -> checker of csrc/expand.hip
+
+The references are plain torch op chains, written from scene_model.py / torch_restatements.py, dtype- and device-agnostic:
+on float64 CPU tensors they are the reference, on float32 device tensors the "framework chain" whose own error against
+the float64 result sets the bar of the kernel (tests/test_gpu_f64_parity.py).  Every input is drawn on the CPU from a
+seeded generator, so the host tests (tests/test_f64_refs_host.py) see exactly the inputs the GPU tests use.
+
+Decisive inputs.  A float64 reference and an fp32 kernel may legitimately disagree where a discrete choice hangs on
+rounding: a ReLU whose pre-activation is a rounding error away from 0, a channel maximum with a runner-up a rounding
+error below it.  Whether an input is decisive is decided here, by the reference alone.
+"""
+import torch
+import torch.nn.functional as F
+
+from torch_restatements import expand_torch_chain
+
+# ---------------------------------------------------------------------------------------------------------- comparison
+FLOOR, C_CHAIN = 2e-5, 1.5      # bar = max(FLOOR, C_CHAIN * e_chain): test_fused_norm_linear_matches_batchnorm_linear_chain
+
+
+def _f64(t):
+    return t.detach().to("cpu", torch.float64)
+
+
+def err(got, ref, rows=False, keep=None):
+    """max|got - ref| / max|ref|.  rows: `got` / `ref` are [rows, ...]; the ratio is taken per row, the row's scale
+    floored at 1e-3 of the tensor's, and the largest row is returned (>= the tensor-level ratio by construction): a
+    wrong tail row cannot hide behind 1e5 good ones.  keep: bool [rows], rows that take part."""
+    got, ref = _f64(got), _f64(ref)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    if got.numel() == 0:
+        return 0.0
+    scale = float(ref.abs().max())
+    if not rows:
+        d = float((got - ref).abs().max())
+        return d / scale if scale > 0 else (0.0 if d == 0 else float("inf"))
+    got, ref = got.reshape(got.shape[0], -1), ref.reshape(ref.shape[0], -1)
+    d = (got - ref).abs().amax(dim=1)
+    d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)
+    s = ref.abs().amax(dim=1).clamp_min(1e-3 * scale)
+    if keep is not None:
+        d, s = d[keep], s[keep]
+        if d.numel() == 0:
+            return 0.0
+    if scale == 0:
+        return 0.0 if float(d.max()) == 0 else float("inf")
+    return float((d / s).max())
+
+
+def bar(e_chain, floor=FLOOR, c=C_CHAIN):
+    return max(floor, c * e_chain)
+
+
+# ---------------------------------------------------------------------------------------------------------- heads
+HEADS_V = [1, 15, 16, 17, 63, 64, 65, 960, 961, 1025, 1985, 16383, 16384, 16385, 32768, 32769, 49153, 100003]
+HEADS_EDGE_V = (49153, 100003)                  # the two largest sizes also carry the edge rows
+HEADS_TOL = 100 * 2.0 ** -24                    # a-priori bound of a 100-term fp32 dot product, relative to sum |w x| + |b|
+HEADS_CAP, HEADS_ROUNDS = 0.01, 8
+HEAD_NAMES = ("opacity", "color", "cov")
+HEAD_OUT = (10, 30, 70)
+# second-layer pre-activations planted in output 0 of the tanh (opacity) and sigmoid (colour) heads of the edge rows
+EDGE_Z = (40.0, -40.0, 100.0, -100.0, 1e-4, -1e-4)
+ZERO_UNIT = 5                                   # hidden unit of the covariance head that is exactly 0 on every row
+
+
+def heads_weights(seed, edges=False):
+    """A model whose three heads carry the modules' init plus 0.2 randn (as test_fused_mlp_heads_match_the_torch_chain).
+    edges: the weights that let heads_inputs plant its edge rows, and the zero unit."""
+    from splatco_amd.scene_model import AnchorGaussianModel
+    torch.manual_seed(seed)
+    pc = AnchorGaussianModel(plane_size=16, num_channels=15)
+    heads = (pc.mlp_opacity, pc.mlp_color, pc.mlp_cov)
+    with torch.no_grad():
+        for h in heads:
+            for p in h.parameters():
+                p.add_(0.2 * torch.randn_like(p))
+        if edges:
+            for h in heads[:2]:
+                # feat column 0 feeds only the hidden units 0 (+) and 1 (-), and these feed only output 0:
+                # z[0] = relu(t) - relu(-t) + rest = t + rest with t = feat[v, 0]
+                h[0].weight[:, 0] = 0
+                h[0].weight[:2] = 0
+                h[0].bias[:2] = 0
+                h[0].weight[0, 0], h[0].weight[1, 0] = 1.0, -1.0
+                h[2].weight[:, :2] = 0
+                h[2].weight[0, 0], h[2].weight[0, 1] = 1.0, -1.0
+            heads[2][0].weight[ZERO_UNIT] = 0       # pre-activation exactly 0: relu'(0) = 0
+            heads[2][0].bias[ZERO_UNIT] = 0
+    return pc
+
+
+def weights_of(pc, dtype=torch.float64, device="cpu", requires_grad=False):
+    """{'w1': 3 x [32,99], 'b1': 3 x [32], 'w2': 3 x [n,32], 'b2': 3 x [n]} (opacity, colour, cov): copies of the heads' weights."""
+    heads = (pc.mlp_opacity, pc.mlp_color, pc.mlp_cov)
+    c = lambda t: t.detach().to(device, dtype).clone().requires_grad_(requires_grad)
+    return {"w1": [c(h[0].weight) for h in heads], "b1": [c(h[0].bias) for h in heads],
+            "w2": [c(h[2].weight) for h in heads], "b2": [c(h[2].bias) for h in heads]}
+
+
+def _heads_layers(feat, anchor, campos, geo, w):
+    ob = anchor - campos
+    ob = ob / ob.norm(dim=1, keepdim=True)
+    x = torch.cat([feat, ob, geo], dim=1)
+    zs, pres, bounds = [], [], []
+    for i in range(3):
+        pre = F.linear(x, w["w1"][i], w["b1"][i])
+        zs.append(F.linear(F.relu(pre), w["w2"][i], w["b2"][i]))
+        pres.append(pre)
+        bounds.append(x.detach().abs() @ w["w1"][i].detach().abs().T + w["b1"][i].detach().abs())
+    return zs, torch.cat(pres, dim=1), torch.cat(bounds, dim=1)
+
+
+def heads_f64(feat, anchor, campos, geo, w):
+    """((opacity [V,10], color [V,30], cov [V,70]), pre [V,96], bound [V,96]): the heads, the stacked hidden
+    pre-activations and per hidden unit sum_i |w_i x_i| + |b| (the scale its rounding error is relative to)."""
+    zs, pre, bound = _heads_layers(feat, anchor, campos, geo, w)
+    return (torch.tanh(zs[0]), torch.sigmoid(zs[1]), zs[2]), pre, bound
+
+
+def heads_undecided(feat, anchor, campos, geo, w64):
+    """bool [V]: rows with a hidden unit whose sign the fp32 rounding could flip.  A unit whose terms are all exactly 0
+    is exact in every precision and counts as decided."""
+    with torch.no_grad():
+        _, pre, bound = heads_f64(feat.double(), anchor.double(), campos.double(), geo.double(), w64)
+    return ((pre.abs() <= HEADS_TOL * bound) & (bound > 0)).any(dim=1)
+
+
+def heads_inputs(V):
+    """fp32 CPU inputs of one heads case: dict(pc, feat, anchor, campos, geo, up (upstream gradients), flagged (share of
+    rows the first draw flagged), rounds, edge_rows).  Rows with an undecided unit are replaced: their feat is redrawn
+    from the same generator, at most HEADS_ROUNDS times."""
+    edges = V in HEADS_EDGE_V
+    pc = heads_weights(V, edges)
+    w64 = weights_of(pc)
+    g = torch.Generator().manual_seed(V + 1)
+    r = lambda *s: torch.randn(*s, generator=g)
+    feat, anchor, geo, campos = r(V, 32), r(V, 3) * 2, r(V, 64), torch.tensor([0.3, -0.2, -5.0])
+    up = [r(V, n) for n in HEAD_OUT]
+    bad = heads_undecided(feat, anchor, campos, geo, w64)
+    flagged, rounds = float(bad.float().mean()), 0
+    while bad.any() and rounds < HEADS_ROUNDS:
+        feat[bad] = r(int(bad.sum()), 32)
+        bad = heads_undecided(feat, anchor, campos, geo, w64)
+        rounds += 1
+    edge_rows = {}
+    if edges:
+        # one row per planted value and head, spread over the first and last tiles and both sides of the grid-stride onsets
+        rows = [0, 15, 16, 4095, 16383, 16384, 32767, 32768, V - 17, V - 16, V - 2, V - 1]
+        with torch.no_grad():
+            f0 = feat.clone()
+            f0[:, 0] = 0
+            zs, _, _ = _heads_layers(f0.double(), anchor.double(), campos.double(), geo.double(), w64)
+            rest = {0: zs[0][:, 0], 1: zs[1][:, 0]}                     # z[0] at t = 0
+        for j, row in enumerate(rows):
+            head, z = j // len(EDGE_Z), EDGE_Z[j % len(EDGE_Z)]
+            feat[row, 0] = float(z - rest[head][row])
+            edge_rows[row] = (head, z)
+        bad = heads_undecided(feat, anchor, campos, geo, w64)
+    assert not bad.any(), f"V={V}: {int(bad.sum())} undecided rows left after {rounds} rounds"
+    return dict(pc=pc, feat=feat, anchor=anchor, campos=campos, geo=geo, up=up, flagged=flagged, rounds=rounds,
+                edge_rows=edge_rows)
+
+
+def heads_run(feat, anchor, campos, geo, up, w):
+    """Forward + backward of heads_f64 in the dtype / on the device of its arguments: (outs, grads dict)."""
+    f, a, ge = (t.detach().clone().requires_grad_(True) for t in (feat, anchor, geo))
+    outs, _, _ = heads_f64(f, a, campos, ge, w)
+    sum((o * u).sum() for o, u in zip(outs, up)).backward()
+    grads = {"feat": f.grad, "anchor": a.grad, "geo": ge.grad}
+    for i, h in enumerate(("mlp_opacity", "mlp_color", "mlp_cov")):
+        grads.update({f"{h}.0.weight": w["w1"][i].grad, f"{h}.0.bias": w["b1"][i].grad,
+                      f"{h}.2.weight": w["w2"][i].grad, f"{h}.2.bias": w["b2"][i].grad})
+    return [o.detach() for o in outs], grads
+
+
+# ---------------------------------------------------------------------------------------------------------- attention
+ATTN_R = [2, 3, 4, 5, 6, 7, 8]                                       # at (37, 91): every instantiation the module reaches
+ATTN_HW = [(1, 1), (2, 3), (3, 200), (200, 3), (5, 5), (16, 64), (15, 63), (17, 65), (32, 128), (700, 700)]
+ATTN_TIES = ("constant", "two_blocks", "one_block")                  # at 5 x 48 x 130
+ATTN_TIE_SHAPE = (5, 48, 130)
+ATTN_CASES = ([("R%d" % R, R, 37, 91, None) for R in ATTN_R] + [("%dx%d" % hw, 5, hw[0], hw[1], None) for hw in ATTN_HW]
+              + [("tie_" + t, *ATTN_TIE_SHAPE, t) for t in ATTN_TIES])
+ATTN_TOL, ATTN_CAP = 1e-5, 1e-3
+STAT_BLOCKS = 64                                                     # pooling blocks per channel (TPA_STAT_BLOCKS)
+
+
+def attention_f64(planes, w1, w2, wc):
+    """planes: three [1,R,H,W]; w1 [C//5,C,1,1], w2 [C,C//5,1,1] the shared MLP, wc [1,2,7,7] the window.
+    -> (pairs: three [1,2R,H,W] = cat(plane, attended plane), y = ca * x [1,C,H,W]).  The pools are the reference's
+    AdaptiveAvgPool2d(1) / AdaptiveMaxPool2d(1): a tied maximum belongs to its first pixel, in value and in gradient."""
+    x = torch.cat(planes, dim=1)
+    mlp = lambda t: F.conv2d(F.relu(F.conv2d(t, w1)), w2)
+    ca = torch.sigmoid(mlp(F.adaptive_avg_pool2d(x, 1)) + mlp(F.adaptive_max_pool2d(x, 1)))
+    y = ca * x
+    s = torch.cat([y.mean(dim=1, keepdim=True), torch.max(y, dim=1, keepdim=True)[0]], dim=1)
+    tri = torch.sigmoid(F.conv2d(s, wc, padding=3)) * y
+    return [torch.cat((p, a), dim=1) for p, a in zip(planes, torch.chunk(tri, 3, dim=1))], y
+
+
+def attention_undecided(y):
+    """bool [H,W]: pixels whose two largest channels of y are closer than ATTN_TOL * max|y| (the fp32 kernel may route
+    the max gradient of such a pixel to the other channel)."""
+    top = torch.topk(y.detach()[0], 2, dim=0)[0]
+    return (top[0] - top[1]) <= ATTN_TOL * float(y.detach().abs().max())
+
+
+def attention_inputs(R, H, W, tie=None):
+    """fp32 CPU inputs of one attention case: dict(ta (the module), planes, up, arg (first maximum of every channel))."""
+    from splatco_amd.scene_model import TriPlaneAttention
+    torch.manual_seed(R * 1000 + H)
+    ta = TriPlaneAttention(3 * R)
+    g = torch.Generator().manual_seed(R * 100003 + H * 1009 + W)
+    planes = [torch.randn(1, R, H, W, generator=g) * 0.5 for _ in range(3)]
+    HW = H * W
+    per = (HW + STAT_BLOCKS - 1) // STAT_BLOCKS                      # pixels per pooling block
+    if tie == "constant":
+        planes[1][:] = 0.25                                          # every pixel of R channels is the maximum
+    elif tie == "two_blocks":
+        p = planes[0][0, 2].view(-1)
+        p[3 * per + 7] = p[40 * per + 1] = float(p.max()) + 1.0
+    elif tie == "one_block":
+        p = planes[2][0, 1].view(-1)
+        p[10 * per + 70] = p[10 * per + 5] = float(p.max()) + 1.0
+        assert per > 70
+    up = [torch.randn(1, 2 * R, H, W, generator=g) for _ in range(3)]
+    x = torch.cat(planes, dim=1)[0].reshape(3 * R, HW)
+    mx = x.amax(dim=1, keepdim=True)
+    arg = (x == mx).int().argmax(dim=1).to(torch.int32)              # first maximum
+    return dict(ta=ta, planes=planes, up=up, arg=arg)
+
+
+def attention_weights(ta, dtype=torch.float64, device="cpu", requires_grad=False):
+    c = lambda t: t.detach().to(device, dtype).clone().requires_grad_(requires_grad)
+    return [c(ta.ca.sharedMLP[0].weight), c(ta.ca.sharedMLP[2].weight), c(ta.sa.conv.weight)]
+
+
+def attention_run(planes, up, ws):
+    """Forward + backward of attention_f64 in the dtype / on the device of its arguments:
+    (pairs, y, plane gradients, [d w1, d w2, d wc])."""
+    ps = [p.detach().clone().requires_grad_(True) for p in planes]
+    pairs, y = attention_f64(ps, *ws)
+    sum((o * u).sum() for o, u in zip(pairs, up)).backward()
+    return [o.detach() for o in pairs], y.detach(), [p.grad for p in ps], [w.grad for w in ws]
+
+
+# ---------------------------------------------------------------------------------------------------------- expansion
+EXPAND_K = [1, 5, 10, 33]                                            # at V = 4099, with the edge rows
+EXPAND_V_K = 4099
+EXPAND_N = [10, 1020, 1030, 1_048_570, 1_048_580, 2_100_010]         # k = 10: first workgroup, 1024 and 2048 workgroups of the scan
+EXPAND_SELECT = ("all", "none", "alternating")                       # at n = 1030
+EXPAND_CASES = ([("k%d" % k, EXPAND_V_K, k, "random", True) for k in EXPAND_K]
+                + [("n%d" % n, n // 10, 10, "random", False) for n in EXPAND_N]
+                + [("sel_" + s, 103, 10, s, False) for s in EXPAND_SELECT])
+SUBNORMAL = 2.0 ** -149
+
+
+def expand_f64(neural_opacity, color, scale_rot, grid_offsets, grid_scaling, anchor, k):
+    return expand_torch_chain(neural_opacity, color, scale_rot, grid_offsets, grid_scaling, anchor, k)
+
+
+def expand_inputs(V, k, select="random", edges=False):
+    """fp32 CPU inputs of one expansion case: dict(args (the six tensors), k, edge (candidate index by name))."""
+    g = torch.Generator().manual_seed(V * 131 + k)
+    r = lambda *s: torch.randn(*s, generator=g)
+    n = V * k
+    no, color, sr, off = r(n, 1), r(n, 3), r(n, 7), r(V, k, 3)
+    gs, anchor = torch.rand(V, 6, generator=g) + 0.1, r(V, 3)
+    if select == "all":
+        no = no.abs() + 0.01
+    elif select == "none":
+        no = -no.abs()
+    elif select == "alternating":
+        no = (no.abs() + 0.01) * (1.0 - 2.0 * (torch.arange(n) % 2)).view(n, 1)
+    edge = {}
+    if edges:
+        # candidates spread over the first, a middle and the last workgroup; all of them kept unless the row is about
+        # the mask itself
+        at = [1, 2, 3, 4, 5, 6, n // 2, n // 2 + 1, n - 2, n - 1] if n >= 64 else None
+        assert at is not None
+        names = ["quat_zero", "quat_tiny", "sig_hi", "sig_lo", "op_pzero", "op_nzero", "op_subnormal", "quat_zero2",
+                 "sig_mixed", "quat_tiny2"]
+        edge = dict(zip(names, at))
+        no[at] = no[at].abs() + 0.01
+        sr[edge["quat_zero"], 3:] = 0.0
+        sr[edge["quat_zero2"], 3:] = 0.0
+        sr[edge["quat_tiny"], 3:] = 1e-20 * torch.tensor([1.0, -2.0, 0.5, 3.0])
+        sr[edge["quat_tiny2"], 3:] = 1e-20 * torch.tensor([0.0, 0.0, 1.0, 0.0])
+        sr[edge["sig_hi"], :3] = 90.0
+        sr[edge["sig_lo"], :3] = -90.0
+        sr[edge["sig_mixed"], :3] = torch.tensor([90.0, -90.0, 0.0])
+        no[edge["op_pzero"]] = 0.0
+        no[edge["op_nzero"]] = -0.0
+        no[edge["op_subnormal"]] = SUBNORMAL
+    return dict(args=[no, color, sr, off, gs, anchor], k=k, edge=edge)
+
+
+def expand_upstream(P, edge_pos, seed):
+    """Upstream gradients of the five outputs for P kept candidates.  The rot gradient of the clamped-quaternion rows
+    (positions edge_pos among the kept) is scaled by 1e-12: d scale_rot = g / 1e-12 there, and O(1) values keep the
+    tensor's scale -- and with it the bar of every other row -- where it is without them."""
+    g = torch.Generator().manual_seed(seed)
+    up = [torch.randn(P, c, generator=g) for c in (3, 3, 1, 3, 4)]
+    for p in edge_pos:
+        up[4][p] *= 1e-12
+    return up
+
+
+def expand_run(args, k, up, reg=0.0):
+    """Forward + backward of expand_f64 in the dtype / on the device of its arguments; reg: weight of the regulariser
+    mean(prod(scaling, 1)).  -> (outputs, mask, gradients of the six inputs)."""
+    ins = [t.detach().clone().requires_grad_(True) for t in args]
+    *outs, mask = expand_f64(*ins, k)
+    loss = sum((o * u).sum() for o, u in zip(outs, up))
+    if reg and outs[3].shape[0]:
+        loss = loss + reg * outs[3].prod(dim=1).mean()
+    if loss.requires_grad:
+        loss.backward()
+    grads = [t.grad if t.grad is not None else torch.zeros_like(t) for t in ins]
+    return [o.detach() for o in outs], mask, grads
