@@ -699,16 +699,7 @@ void launch_scatter(int64_t P, const KSettings& ks, const GeomView& gv, const Bi
     if (P <= 0) return;
     Grid g(ks.H, ks.W);
     const unsigned nb = (unsigned)((P + BIN_GPW - 1) / BIN_GPW);
-    // histograms beyond the default 64 KB dynamic-LDS limit (gfx950 has 160 KB per CU): the attribute is per device
-    static bool big_lds[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !big_lds[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)scatter_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 LDS_HIST_MAX_TILES * 4);
-        if (e == hipSuccess && dev >= 0 && dev < 64) big_lds[dev] = true;
-        (void)hipGetLastError();      // a refused attribute shows up as a launch error below
-    }
+    allow_dynamic_lds((const void*)scatter_kernel<true>, LDS_HIST_MAX_TILES * 4);
     if (g.tiles <= LDS_HIST_MAX_TILES)
         scatter_kernel<true><<<nb, BIN_THREADS, (size_t)g.tiles * 4, st>>>(
             P, g.gx, g.tiles, gv.rec, gv.gm_base, gv.live_bits, gv.tiles_touched, gv.block_sums, gv.point_offsets, gv.ranges,
@@ -730,14 +721,7 @@ void launch_tile_sort(const KSettings& ks, const GeomView& gv, const BinView& bv
     if (max_tile_instances <= WAVE_SORT_MAX) return;
     const unsigned chunks = (unsigned)((max_tile_instances + WG_SORT_MAX - 1) / WG_SORT_MAX);
     const size_t lds = (size_t)(WG_SORT_MAX + WG_SORT_MAX / 16) * 8;
-    static bool big_lds[64] = {};      // more than the default 64 KB of dynamic LDS: the attribute is per device
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !big_lds[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)tile_sort_wg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess && dev >= 0 && dev < 64) big_lds[dev] = true;
-        (void)hipGetLastError();
-    }
+    allow_dynamic_lds((const void*)tile_sort_wg_kernel, lds);
     tile_sort_wg_kernel<<<dim3(gt, chunks), WG_SORT_THREADS, lds, st>>>(g.tiles, g.gx, gv.ranges, bv.keys, gv.gm_base, bv.point_list,
                                                                         gm_index, bv.qmask);
     if (chunks <= 1) return;

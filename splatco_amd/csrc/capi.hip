@@ -11,12 +11,30 @@
 #include "adam.h"
 #include "tv.h"
 #include <chrono>
+#include <map>
+#include <mutex>
+#include <utility>
 #include <cstring>
 
 using namespace scr;
 
 static thread_local char g_err[512] = "";
-namespace scr { int g_force_deep_lists = -1; }
+namespace scr {
+int g_force_deep_lists = -1;
+
+void allow_dynamic_lds(const void* kernel, size_t bytes) {
+    if (bytes <= 65536) return;
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, size_t> granted;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(mu);
+    size_t& have = granted[{dev, kernel}];
+    if (bytes <= have) return;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) have = bytes;
+    (void)hipGetLastError();
+}
+}  // namespace scr
 
 static int fail(const char* fmt, ...) {
     va_list ap;

@@ -337,6 +337,11 @@ inline void ZeroList::add(void* ptr, size_t bytes, hipStream_t st) {
     ++count;
 }
 
+// More than the default 64 KB of dynamic LDS for `kernel` on the current device (gfx950 has 160 KB per CU).  The attribute is
+// per function and device: the largest grant of each pair is remembered, and the runtime is asked only for more.  A refused
+// attribute shows up as the error of the launch that follows.  (capi.hip)
+void allow_dynamic_lds(const void* kernel, size_t bytes);
+
 // launchers (defined in the .hip files)
 void launch_box_coords(int64_t V, const float* xyz, const float* lo, const float* hi, float* out, hipStream_t st);
 int launch_nl_fold(int L, int d, const int* dd, const int* col, const unsigned char* col_at, const float* const* W,

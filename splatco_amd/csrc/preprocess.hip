@@ -640,16 +640,7 @@ void launch_preprocess(int64_t P, int M, const float* means3D, const float* scal
                        const KSettings& ks, const GeomView& gv, int32_t* radii, hipStream_t st) {
     if (P <= 0) return;
     Grid g(ks.H, ks.W);
-    // histograms beyond the default 64 KB dynamic-LDS limit (gfx950 has 160 KB per CU): the attribute is per device
-    static bool big_lds[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !big_lds[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)preprocess_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 LDS_HIST_MAX_TILES * 4);
-        if (e == hipSuccess && dev >= 0 && dev < 64) big_lds[dev] = true;
-        (void)hipGetLastError();      // a refused attribute shows up as a launch error below
-    }
+    allow_dynamic_lds((const void*)preprocess_kernel<true>, LDS_HIST_MAX_TILES * 4);
     if (g.tiles <= LDS_HIST_MAX_TILES)
         preprocess_kernel<true><<<nblk(P, BIN_GPW), BIN_THREADS, (size_t)g.tiles * 4, st>>>(
             P, M, means3D, scales, rotations, cov3D, opacities, shs, colors, ks, g.tiles, gv.rec, gv.tiles_touched,

@@ -24,10 +24,7 @@
 // Round 1 kept an index list per tile and gathered coordinates and gradients through it (0.43 ms per plane at
 // 4.6 M points, 5.2 ms per cfg2 step); records + one pass per grid + cell-centred sums: 3.2 ms per step.
 #include "common.h"
-#include <mutex>
-#include <set>
 #include <type_traits>
-#include <utility>
 
 namespace scr {
 
@@ -106,42 +103,100 @@ struct TpProj {
     float* rec;                           // [V][tp_rec(R * NP)]
     float* halo;                          // [tiles][TP_BORDER][R * NP]: every tile's sums for the nodes on its border
 };
-struct TpProjSet {
-    TpProj p[3];
+// the projections of a pass: up to 3 (one grid) or up to 9 (all grids of a step); the slots from n on are copies of p[0]
+template <int N>
+struct TpProjSetT {
+    TpProj p[N];
     int n;
 };
 
+__device__ __forceinline__ float tp_pick(float x, float y, float z, int c) { return c == 0 ? x : (c == 1 ? y : z); }
+
+// The per-workgroup LDS histogram holds the tiles of the pass's projections one after the other.
+template <int N>
+__host__ __device__ __forceinline__ int tp_total_tiles(const TpProjSetT<N>& ps) {
+    int total = 0;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        if (q >= ps.n) break;
+        total += ps.p[q].tiles;
+    }
+    return total;
+}
+// f(projection, tile, slot of the tile in the histogram) for every tile of the pass, the workgroup's threads side by side
+template <int N, typename F>
+__device__ __forceinline__ void tp_for_tiles(const TpProjSetT<N>& ps, F f) {
+    int off = 0;
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        if (q >= ps.n) break;
+        for (int t = threadIdx.x; t < ps.p[q].tiles; t += TP_THREADS) f(ps.p[q], t, off + t);
+        off += ps.p[q].tiles;
+    }
+}
+__device__ __forceinline__ void tp_clear_lds(uint32_t* lds, int words) {
+    for (int t = threadIdx.x; t < words; t += TP_THREADS) lds[t] = 0;
+}
+// hist: this workgroup's records per tile -> where its run inside the tile's run starts (one global atomic per touched tile)
+template <int N>
+__device__ __forceinline__ void tp_reserve_runs(const TpProjSetT<N>& ps, uint32_t* hist) {
+    tp_for_tiles(ps, [&](const TpProj& pj, int t, int h) {
+        const uint32_t c = hist[h];
+        if (c) hist[h] = pj.start[t] + atomicAdd(&pj.cursor[t], c);
+    });
+}
+// hmax: the largest |gradient value| this workgroup placed in a tile (bits) -> the tile's maximum
+template <int N>
+__device__ __forceinline__ void tp_flush_max(const TpProjSetT<N>& ps, const uint32_t* hmax) {
+    tp_for_tiles(ps, [&](const TpProj& pj, int t, int h) {
+        if (hmax[h]) atomicMax(&pj.gmax[t], hmax[h]);
+    });
+}
+
+// A point's coordinate columns for the count kernel.  The per-grid path reads coords[i * cs + c] per projection: any
+// column pair of any row stride (plane_sample: cs = 2, columns 0 and 1).  The nine-projection sets sample columns 0..2
+// of rows with cs >= 3 (launch_triplane_backward_multi), and their count kernel keeps what tp_count9_kernel did: the row
+// is loaded once and the columns are picked from registers (3 loads per point instead of 18).  NOT MEASURED against the
+// plain form: kept because it is what the benchmark's path ran before; drop the specialisation if the plain form times
+// the same.
+template <int N>
+struct TpCoords {
+    const float* row;
+    __device__ __forceinline__ explicit TpCoords(const float* r) : row(r) {}
+    __device__ __forceinline__ float operator[](int c) const { return row[c]; }
+};
+template <>
+struct TpCoords<9> {
+    float x, y, z;
+    __device__ __forceinline__ explicit TpCoords(const float* r) : x(r[0]), y(r[1]), z(r[2]) {}
+    __device__ __forceinline__ float operator[](int c) const { return tp_pick(x, y, z, c); }
+};
+
 // pass 1: per-tile point counts (LDS histograms per workgroup, one global atomic per touched tile)
+template <int N>
 __global__ void __launch_bounds__(TP_THREADS)
-tp_count_kernel(int64_t V, const float* __restrict__ coords, int cs, TpProjSet ps) {
+tp_count_kernel(int64_t V, const float* __restrict__ coords, int cs, TpProjSetT<N> ps) {
     extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
-    const int total = ps.p[0].tiles + (ps.n > 1 ? ps.p[1].tiles + ps.p[2].tiles : 0);
-    for (int t = threadIdx.x; t < total; t += TP_THREADS) hist[t] = 0;
+    tp_clear_lds(hist, tp_total_tiles(ps));
     __syncthreads();
     for (int r = 0; r < TP_ROUNDS; ++r) {
         const int64_t i = (int64_t)blockIdx.x * TP_PER_WG + r * TP_THREADS + threadIdx.x;
         if (i >= V) break;
+        const TpCoords<N> pt(coords + i * cs);
         int off = 0;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            if (q >= ps.n) break;
+        for (int q = 0; q < ps.n; ++q) {
             const TpProj& pj = ps.p[q];
-            const int t = tp_tile_of(coords[i * cs + pj.cx], coords[i * cs + pj.cy], pj.A, pj.B, pj.tb);
+            const float gx = pt[pj.cx], gy = pt[pj.cy];
+            const int t = tp_tile_of(gx, gy, pj.A, pj.B, pj.tb);
             if (t >= 0) atomicAdd(&hist[off + t], 1u);
             off += pj.tiles;
         }
     }
     __syncthreads();
-    int off = 0;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        if (q >= ps.n) break;
-        for (int t = threadIdx.x; t < ps.p[q].tiles; t += TP_THREADS) {
-            const uint32_t c = hist[off + t];
-            if (c) atomicAdd(&ps.p[q].count[t], c);
-        }
-        off += ps.p[q].tiles;
-    }
+    tp_for_tiles(ps, [&](const TpProj& pj, int t, int h) {
+        const uint32_t c = hist[h];
+        if (c) atomicAdd(&pj.count[t], c);
+    });
 }
 
 // A tile's run is summed by ONE workgroup of pass 4 -- unless the tile is crowded: a scene is not a uniform cloud (a city
@@ -196,10 +251,11 @@ __device__ __forceinline__ void tp_scan_proj(const TpProj& pj, uint32_t* lds) {
         pj.split[0] = carry_l;
     }
 }
+template <int N>
 __global__ void __launch_bounds__(1024)
-tp_scan_kernel(TpProjSet ps) {
+tp_scan_kernel(TpProjSetT<N> ps) {
     __shared__ uint32_t lds[1024 / WAVE];
-    const TpProj pj = blockIdx.x == 0 ? ps.p[0] : (blockIdx.x == 1 ? ps.p[1] : ps.p[2]);
+    const TpProj pj = ps.p[blockIdx.x];
     tp_scan_proj(pj, lds);
 }
 
@@ -261,12 +317,14 @@ __device__ __forceinline__ uint32_t tp_abs_max_bits(const float* g) {
 template <int R, int NP, bool FAST>
 __global__ void __launch_bounds__(TP_THREADS)
 tp_scatter_kernel(int64_t V, const float* __restrict__ coords, int cs, const float* __restrict__ grad, int ld, int span0,
-                  TpProjSet ps) {
+                  TpProjSetT<3> ps) {
     constexpr int RT = R * NP, REC = tp_rec(RT);
     extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
+    // (= tp_total_tiles(ps): a per-grid set holds one projection or three.  Written out because the register allocation of
+    // 13 of this kernel's 42 instantiations follows the form of this line -- profiles/r09_triplane_one_pipeline.txt)
     const int total = ps.p[0].tiles + (ps.n > 1 ? ps.p[1].tiles + ps.p[2].tiles : 0);
     uint32_t* hmax = hist + total;        // per tile: the largest |gradient value| this workgroup placed there (bits)
-    for (int t = threadIdx.x; t < 2 * total; t += TP_THREADS) hist[t] = 0;
+    tp_clear_lds(hist, 2 * total);
     __syncthreads();
     int tl[TP_ROUNDS][3];
 #pragma unroll
@@ -288,19 +346,7 @@ tp_scatter_kernel(int64_t V, const float* __restrict__ coords, int cs, const flo
         }
     }
     __syncthreads();
-    {
-        int off = 0;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            if (q >= ps.n) break;
-            const TpProj& pj = ps.p[q];
-            for (int t = threadIdx.x; t < pj.tiles; t += TP_THREADS) {
-                const uint32_t c = hist[off + t];
-                if (c) hist[off + t] = pj.start[t] + atomicAdd(&pj.cursor[t], c);
-            }
-            off += pj.tiles;
-        }
-    }
+    tp_reserve_runs(ps, hist);
     __syncthreads();
     const int head = (4 - (span0 & 3)) & 3;       // floats before the span reaches 16-byte alignment (FAST only)
 #pragma unroll
@@ -338,64 +384,12 @@ tp_scatter_kernel(int64_t V, const float* __restrict__ coords, int cs, const flo
         }
     }
     __syncthreads();
-    {
-        int off = 0;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            if (q >= ps.n) break;
-            for (int t = threadIdx.x; t < ps.p[q].tiles; t += TP_THREADS)
-                if (hmax[off + t]) atomicMax(&ps.p[q].gmax[t], hmax[off + t]);
-            off += ps.p[q].tiles;
-        }
-    }
+    tp_flush_max(ps, hmax);
 }
 
 // ---- all grids of a step in ONE pass over the points (up to three grids = nine projections that sample the same
 // coordinates; FeaturePlanes: the attention grid with its planes stacked, R = 2 r, and one or two plain grids, R = r).
 // The [V, ld] gradient matrix and the coordinates are read once instead of once per grid, with whole 16-byte loads.
-struct TpProjSet9 {
-    TpProj p[9];
-    int n;          // 3 * number of grids
-};
-
-__device__ __forceinline__ float tp_pick(float x, float y, float z, int c) { return c == 0 ? x : (c == 1 ? y : z); }
-
-__global__ void __launch_bounds__(TP_THREADS)
-tp_count9_kernel(int64_t V, const float* __restrict__ coords, int cs, TpProjSet9 ps) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
-    int total = 0;
-    for (int q = 0; q < ps.n; ++q) total += ps.p[q].tiles;
-    for (int t = threadIdx.x; t < total; t += TP_THREADS) hist[t] = 0;
-    __syncthreads();
-    for (int r = 0; r < TP_ROUNDS; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * TP_PER_WG + r * TP_THREADS + threadIdx.x;
-        if (i >= V) break;
-        const float x = coords[i * cs], y = coords[i * cs + 1], z = coords[i * cs + 2];
-        int off = 0;
-        for (int q = 0; q < ps.n; ++q) {
-            const int t = tp_tile_of(tp_pick(x, y, z, ps.p[q].cx), tp_pick(x, y, z, ps.p[q].cy), ps.p[q].A, ps.p[q].B, ps.p[q].tb);
-            if (t >= 0) atomicAdd(&hist[off + t], 1u);
-            off += ps.p[q].tiles;
-        }
-    }
-    __syncthreads();
-    int off = 0;
-    for (int q = 0; q < ps.n; ++q) {
-        for (int t = threadIdx.x; t < ps.p[q].tiles; t += TP_THREADS) {
-            const uint32_t c = hist[off + t];
-            if (c) atomicAdd(&ps.p[q].count[t], c);
-        }
-        off += ps.p[q].tiles;
-    }
-}
-
-__global__ void __launch_bounds__(1024)
-tp_scan9_kernel(TpProjSet9 ps) {
-    __shared__ uint32_t lds[1024 / WAVE];
-    const TpProj pj = ps.p[blockIdx.x];
-    tp_scan_proj(pj, lds);
-}
-
 // grid g (0..2) has RTg channels per projection (0 = grid absent); its projection q owns columns
 // base_g + q * RTg .. + RTg of the span that starts at column span0 (a multiple of 4; rows 16-byte aligned)
 // DX (round 6): the gradient rows are not read but FORMED here.  The sampled matrix has one consumer, the BatchNorm-Linear of
@@ -407,14 +401,13 @@ tp_scan9_kernel(TpProjSet9 ps) {
 template <int RA, int RB, int RC, bool DX>
 __global__ void __launch_bounds__(TP_THREADS)
 tp_scatter9_kernel(int64_t V, const float* __restrict__ coords, int cs, const float* __restrict__ grad, int ld, int span0,
-                   TpProjSet9 ps, const float* __restrict__ nl_coef, const float* __restrict__ nl_dy, int nl_lddy,
+                   TpProjSetT<9> ps, const float* __restrict__ nl_coef, const float* __restrict__ nl_dy, int nl_lddy,
                    const float* __restrict__ nl_x, int nl_ldx) {
     constexpr int SPAN = 3 * (RA + RB + RC);
     extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
-    int total = 0;
-    for (int q = 0; q < ps.n; ++q) total += ps.p[q].tiles;
+    const int total = tp_total_tiles(ps);
     uint32_t* hmax = hist + total;        // (as tp_scatter_kernel)
-    for (int t = threadIdx.x; t < 2 * total; t += TP_THREADS) hist[t] = 0;
+    tp_clear_lds(hist, 2 * total);
     __syncthreads();
     for (int r = 0; r < TP_ROUNDS; ++r) {
         const int64_t i = (int64_t)blockIdx.x * TP_PER_WG + r * TP_THREADS + threadIdx.x;
@@ -428,16 +421,7 @@ tp_scatter9_kernel(int64_t V, const float* __restrict__ coords, int cs, const fl
         }
     }
     __syncthreads();
-    {
-        int off = 0;
-        for (int q = 0; q < ps.n; ++q) {
-            for (int t = threadIdx.x; t < ps.p[q].tiles; t += TP_THREADS) {
-                const uint32_t c = hist[off + t];
-                if (c) hist[off + t] = ps.p[q].start[t] + atomicAdd(&ps.p[q].cursor[t], c);
-            }
-            off += ps.p[q].tiles;
-        }
-    }
+    tp_reserve_runs(ps, hist);
     __syncthreads();
 #pragma unroll 1
     for (int r = 0; r < TP_ROUNDS; ++r) {
@@ -503,14 +487,7 @@ tp_scatter9_kernel(int64_t V, const float* __restrict__ coords, int cs, const fl
         if constexpr (RC > 0) place(std::integral_constant<int, RC>{}, 2, 3 * (RA + RB));
     }
     __syncthreads();
-    {
-        int off = 0;
-        for (int q = 0; q < ps.n; ++q) {
-            for (int t = threadIdx.x; t < ps.p[q].tiles; t += TP_THREADS)
-                if (hmax[off + t]) atomicMax(&ps.p[q].gmax[t], hmax[off + t]);
-            off += ps.p[q].tiles;
-        }
-    }
+    tp_flush_max(ps, hmax);
 }
 
 // pass 4, cell-centred.  The obvious kernel -- every point adds its 4 corners x R channels into an LDS copy of the
@@ -897,26 +874,41 @@ tp_border_sum_kernel(int A, int B, int tb, const uint32_t* __restrict__ tile_sta
 
 // ---- forward: out[v, col_p + r] = bilinear sample of plane p (zeros padding), weights and
 // accumulation order as torch's grid_sampler_2d (nw, ne, sw, se)
-template <int R>
-__device__ __forceinline__ void tp_sample_plane(const float* __restrict__ plane, int A, int B, float gx, float gy,
-                                                float* __restrict__ out) {
-    int a0, b0;
+// what the three plane layouts below share of a sample: which corners exist and what they weigh
+struct TpCorners {
+    int a0, pb;             // first row; first column of the column pair that is loaded
+    bool va0, va1;          // rows a0, a0 + 1 inside the plane
+    float wy0, wy1;         // weights of rows a0, a0 + 1
+    float we0, we1;         // weights of columns pb, pb + 1
+};
+__device__ __forceinline__ TpCorners tp_corners(float gx, float gy, int A, int B) {
+    TpCorners c;
+    int b0;
     float fa, fb;
-    tp_cell(gx, gy, A, B, a0, b0, fa, fb);
-    const bool va0 = a0 >= 0 && a0 < A, va1 = a0 + 1 >= 0 && a0 + 1 < A;
+    tp_cell(gx, gy, A, B, c.a0, b0, fa, fb);
+    c.va0 = c.a0 >= 0 && c.a0 < A;
+    c.va1 = c.a0 + 1 >= 0 && c.a0 + 1 < A;
     const bool vb0 = b0 >= 0 && b0 < B, vb1 = b0 + 1 >= 0 && b0 + 1 < B;
     // The two x-neighbours of a corner pair are adjacent in memory: one 8-byte load per (row, channel)
     // from the pair base pb = clamp(b0, 0, B-2); a corner outside the plane (zeros padding) or not
     // covered by the pair gets weight 0, so all 2*R loads are unconditional and in flight together.
     // (NaN coordinates fail every test -> weights 0 -> output 0, where torch propagates NaN; the
     // reference never samples NaN positions.)
-    const int pb = min(max(b0, 0), B - 2);
+    c.pb = min(max(b0, 0), B - 2);
     const float wx0 = vb0 ? 1.0f - fb : 0.0f, wx1 = vb1 ? fb : 0.0f;           // weights of columns b0, b0+1
-    const float we0 = b0 == pb ? wx0 : (b0 + 1 == pb ? wx1 : 0.0f);            // ... of columns pb, pb+1
-    const float we1 = b0 == pb + 1 ? wx0 : (b0 + 1 == pb + 1 ? wx1 : 0.0f);
-    const float wy0 = va0 ? 1.0f - fa : 0.0f, wy1 = va1 ? fa : 0.0f;
-    const float w00 = wy0 * we0, w01 = wy0 * we1, w10 = wy1 * we0, w11 = wy1 * we1;
-    const size_t n0 = (size_t)(va0 ? a0 : 0) * B + pb, n1 = (size_t)(va1 ? a0 + 1 : 0) * B + pb;
+    c.we0 = b0 == c.pb ? wx0 : (b0 + 1 == c.pb ? wx1 : 0.0f);                  // ... of columns pb, pb+1
+    c.we1 = b0 == c.pb + 1 ? wx0 : (b0 + 1 == c.pb + 1 ? wx1 : 0.0f);
+    c.wy0 = c.va0 ? 1.0f - fa : 0.0f;
+    c.wy1 = c.va1 ? fa : 0.0f;
+    return c;
+}
+
+template <int R>
+__device__ __forceinline__ void tp_sample_plane(const float* __restrict__ plane, int A, int B, float gx, float gy,
+                                                float* __restrict__ out) {
+    const TpCorners c = tp_corners(gx, gy, A, B);
+    const float w00 = c.wy0 * c.we0, w01 = c.wy0 * c.we1, w10 = c.wy1 * c.we0, w11 = c.wy1 * c.we1;
+    const size_t n0 = (size_t)(c.va0 ? c.a0 : 0) * B + c.pb, n1 = (size_t)(c.va1 ? c.a0 + 1 : 0) * B + c.pb;
     const size_t AB = (size_t)A * B;
     typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
     f2u v0[R], v1[R];
@@ -937,19 +929,10 @@ __device__ __forceinline__ void tp_sample_plane(const float* __restrict__ plane,
 template <int R>
 __device__ __forceinline__ void tp_sample_plane_cl(const float* __restrict__ plane, int A, int B, float gx, float gy,
                                                    float* __restrict__ out) {
-    int a0, b0;
-    float fa, fb;
-    tp_cell(gx, gy, A, B, a0, b0, fa, fb);
-    const bool va0 = a0 >= 0 && a0 < A, va1 = a0 + 1 >= 0 && a0 + 1 < A;
-    const bool vb0 = b0 >= 0 && b0 < B, vb1 = b0 + 1 >= 0 && b0 + 1 < B;
-    const int pb = min(max(b0, 0), B - 2);
-    const float wx0 = vb0 ? 1.0f - fb : 0.0f, wx1 = vb1 ? fb : 0.0f;
-    const float we0 = b0 == pb ? wx0 : (b0 + 1 == pb ? wx1 : 0.0f);
-    const float we1 = b0 == pb + 1 ? wx0 : (b0 + 1 == pb + 1 ? wx1 : 0.0f);
-    const float wy0 = va0 ? 1.0f - fa : 0.0f, wy1 = va1 ? fa : 0.0f;
-    const float w00 = wy0 * we0, w01 = wy0 * we1, w10 = wy1 * we0, w11 = wy1 * we1;
-    const float* p0 = plane + ((size_t)(va0 ? a0 : 0) * B + pb) * R;
-    const float* p1 = plane + ((size_t)(va1 ? a0 + 1 : 0) * B + pb) * R;
+    const TpCorners c = tp_corners(gx, gy, A, B);
+    const float w00 = c.wy0 * c.we0, w01 = c.wy0 * c.we1, w10 = c.wy1 * c.we0, w11 = c.wy1 * c.we1;
+    const float* p0 = plane + ((size_t)(c.va0 ? c.a0 : 0) * B + c.pb) * R;
+    const float* p1 = plane + ((size_t)(c.va1 ? c.a0 + 1 : 0) * B + c.pb) * R;
     float v0[2 * R], v1[2 * R];
 #pragma unroll
     for (int k = 0; k < 2 * R; ++k) {
@@ -966,20 +949,12 @@ __device__ __forceinline__ void tp_sample_plane_cl(const float* __restrict__ pla
 template <int R>
 __device__ __forceinline__ void tp_sample_plane_rp(const float* __restrict__ plane, int A, int B, float gx, float gy,
                                                    float* __restrict__ out) {
-    int a0, b0;
-    float fa, fb;
-    tp_cell(gx, gy, A, B, a0, b0, fa, fb);
-    const bool va0 = a0 >= 0 && a0 < A, va1 = a0 + 1 >= 0 && a0 + 1 < A;
-    const bool vb0 = b0 >= 0 && b0 < B, vb1 = b0 + 1 >= 0 && b0 + 1 < B;
-    const int pb = min(max(b0, 0), B - 2), pa = min(max(a0, 0), A - 2);
-    const float wx0 = vb0 ? 1.0f - fb : 0.0f, wx1 = vb1 ? fb : 0.0f;
-    const float we0 = b0 == pb ? wx0 : (b0 + 1 == pb ? wx1 : 0.0f);
-    const float we1 = b0 == pb + 1 ? wx0 : (b0 + 1 == pb + 1 ? wx1 : 0.0f);
-    const float wy0 = va0 ? 1.0f - fa : 0.0f, wy1 = va1 ? fa : 0.0f;
-    const float wr0 = a0 == pa ? wy0 : (a0 + 1 == pa ? wy1 : 0.0f);
-    const float wr1 = a0 == pa + 1 ? wy0 : (a0 + 1 == pa + 1 ? wy1 : 0.0f);
-    const float w00 = wr0 * we0, w01 = wr0 * we1, w10 = wr1 * we0, w11 = wr1 * we1;
-    const float* p = plane + ((size_t)pa * B + pb) * (2 * R);
+    const TpCorners c = tp_corners(gx, gy, A, B);
+    const int pa = min(max(c.a0, 0), A - 2);
+    const float wr0 = c.a0 == pa ? c.wy0 : (c.a0 + 1 == pa ? c.wy1 : 0.0f);       // weights of rows pa, pa+1
+    const float wr1 = c.a0 == pa + 1 ? c.wy0 : (c.a0 + 1 == pa + 1 ? c.wy1 : 0.0f);
+    const float w00 = wr0 * c.we0, w01 = wr0 * c.we1, w10 = wr1 * c.we0, w11 = wr1 * c.we1;
+    const float* p = plane + ((size_t)pa * B + c.pb) * (2 * R);
     float v[4 * R];
 #pragma unroll
     for (int k = 0; k < 4 * R; ++k) v[k] = p[k];          // (row pa, col pb) (row pa+1, col pb) (row pa, col pb+1) (row pa+1, col pb+1)
@@ -1147,25 +1122,49 @@ static char* tp_carve(TpProj& pj, int64_t V, int channels, char* scratch) {
 static inline unsigned tp_gather_grid(const TpProj& pj, int64_t V) { return (unsigned)(pj.tiles + tp_max_split_segments(V)); }
 
 constexpr int TP_HIST_MAX_TILES = 16384;   // 64 KB of LDS histogram (+ 64 KB of tile maxima in pass 3) per workgroup, over the projections of a pass
+// the most pass 3 asks for (hist + hmax).  Every scatter launch asks for this much, so the attribute is set at a kernel's
+// first launch on a device whatever the planes' size, and never again
+constexpr size_t TP_SCATTER_MAX_LDS = 2 * TP_HIST_MAX_TILES * 4;
 
-// more than the default 64 KB of dynamic LDS (gfx950 has 160 KB per CU); the attribute is per function and device
-static void tp_allow_lds(const void* fn, size_t bytes) {
-    if (bytes <= 65536) return;
-    static std::mutex mu;
-    static std::set<std::pair<int, const void*>> done;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    if (done.count({dev, fn})) return;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TP_HIST_MAX_TILES * 4) == hipSuccess) done.insert({dev, fn});
-    (void)hipGetLastError();      // a refused attribute shows up as a launch error
+// Fills projection pj (coordinate columns, plane size, gradient columns), carves its part of the scratch block and queues
+// what has to be zero before the passes run: its tile header (count, gmax) and its plane gradient(s) (gp1: NULL for none).
+static char* tp_setup_projection(TpProj& pj, int cx, int cy, int A, int B, int col0, int col1, int64_t V, int R, int planes,
+                                 float* gp0, float* gp1, char* scratch, ZeroList& zl, hipStream_t st) {
+    pj.cx = cx;
+    pj.cy = cy;
+    pj.A = A;
+    pj.B = B;
+    pj.col0 = col0;
+    pj.col1 = col1;
+    scratch = tp_carve(pj, V, R * planes, scratch);
+    zl.add(pj.count, (size_t)pj.tiles * TP_HEAD_ZEROED * 4, st);        // + gmax
+    zl.add(gp0, (size_t)R * A * B * 4, st);
+    zl.add(gp1, (size_t)R * A * B * 4, st);
+    return scratch;
+}
+// after the last projection: the partial sums of split tiles lie behind the projections' blocks, shared by all of them
+template <int N>
+static void tp_close_set(TpProjSetT<N>& ps, char* scratch) {
+    for (int q = 0; q < ps.n; ++q) ps.p[q].part = (long long*)scratch;
+    for (int q = ps.n; q < N; ++q) ps.p[q] = ps.p[0];
+}
+
+// passes 4, 4b and 5 of one projection
+template <int R, int NP>
+static void tp_gather_launch(const TpProj& pj, int64_t V, float* gp0, float* gp1, hipStream_t st) {
+    allow_dynamic_lds((const void*)tp_cell_gather_kernel<R, NP>, tpn_lds_bytes<R * NP>());
+    tp_cell_gather_kernel<R, NP><<<tp_gather_grid(pj, V), TPN_THREADS, tpn_lds_bytes<R * NP>(), st>>>(
+        pj.A, pj.B, pj.tb, pj.tiles, pj.start, pj.seg, pj.pfirst, pj.part, pj.gmax, pj.rec, gp0, gp1, pj.halo);
+    tp_split_finish_kernel<R, NP><<<dim3((unsigned)tp_max_split_tiles(V), R * NP), TPN_THREADS, 0, st>>>(
+        pj.A, pj.B, pj.tb, pj.split, pj.seg, pj.pfirst, pj.part, pj.gmax, gp0, gp1, pj.halo);
+    tp_border_sum_kernel<R, NP><<<dim3((unsigned)((pj.B + 255) / 256), (unsigned)pj.A), 256, 0, st>>>(
+        pj.A, pj.B, pj.tb, pj.start, pj.halo, gp0, gp1);
 }
 
 template <int R, int NP>
-static void tp_backward_launch(int64_t V, const float* coords, int cs, const float* grad, int ld, const TpProjSet& ps,
+static void tp_backward_launch(int64_t V, const float* coords, int cs, const float* grad, int ld, const TpProjSetT<3>& ps,
                                float* const* gp0, float* const* gp1, hipStream_t st) {
-    int total = 0;
-    for (int q = 0; q < ps.n; ++q) total += ps.p[q].tiles;
+    const int total = tp_total_tiles(ps);
     const unsigned nwg = (unsigned)((V + TP_PER_WG - 1) / TP_PER_WG);
     tp_count_kernel<<<nwg, TP_THREADS, (size_t)total * 4, st>>>(V, coords, cs, ps);
     tp_scan_kernel<<<ps.n, 1024, 0, st>>>(ps);
@@ -1174,31 +1173,13 @@ static void tp_backward_launch(int64_t V, const float* coords, int cs, const flo
     for (int q = 0; q < ps.n && fast; ++q)
         fast = ps.p[q].col0 == ps.p[0].col0 + q * R * NP && (NP == 1 || ps.p[q].col1 == ps.p[q].col0 + R);
     if (fast) {
-        tp_allow_lds((const void*)tp_scatter_kernel<R, NP, true>, (size_t)total * 8);
+        allow_dynamic_lds((const void*)tp_scatter_kernel<R, NP, true>, TP_SCATTER_MAX_LDS);
         tp_scatter_kernel<R, NP, true><<<nwg, TP_THREADS, (size_t)total * 8, st>>>(V, coords, cs, grad, ld, ps.p[0].col0, ps);
     } else {
-        tp_allow_lds((const void*)tp_scatter_kernel<R, NP, false>, (size_t)total * 8);
+        allow_dynamic_lds((const void*)tp_scatter_kernel<R, NP, false>, TP_SCATTER_MAX_LDS);
         tp_scatter_kernel<R, NP, false><<<nwg, TP_THREADS, (size_t)total * 8, st>>>(V, coords, cs, grad, ld, 0, ps);
     }
-    // more than the default 64 KB of dynamic LDS (gfx950 has 160 KB per CU): the attribute is per device
-    static bool big_lds[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !big_lds[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)tp_cell_gather_kernel<R, NP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)tpn_lds_bytes<R * NP>());
-        if (e == hipSuccess && dev >= 0 && dev < 64) big_lds[dev] = true;
-        (void)hipGetLastError();      // a refused attribute shows up as a launch error
-    }
-    for (int q = 0; q < ps.n; ++q) {
-        tp_cell_gather_kernel<R, NP><<<tp_gather_grid(ps.p[q], V), TPN_THREADS, tpn_lds_bytes<R * NP>(), st>>>(
-            ps.p[q].A, ps.p[q].B, ps.p[q].tb, ps.p[q].tiles, ps.p[q].start, ps.p[q].seg, ps.p[q].pfirst, ps.p[q].part,
-            ps.p[q].gmax, ps.p[q].rec, gp0[q], gp1[q], ps.p[q].halo);
-        tp_split_finish_kernel<R, NP><<<dim3((unsigned)tp_max_split_tiles(V), R * NP), TPN_THREADS, 0, st>>>(ps.p[q].A, ps.p[q].B, ps.p[q].tb, ps.p[q].split, ps.p[q].seg, ps.p[q].pfirst,
-                                                                              ps.p[q].part, ps.p[q].gmax, gp0[q], gp1[q], ps.p[q].halo);
-        tp_border_sum_kernel<R, NP><<<dim3((unsigned)((ps.p[q].B + 255) / 256), (unsigned)ps.p[q].A), 256, 0, st>>>(
-            ps.p[q].A, ps.p[q].B, ps.p[q].tb, ps.p[q].start, ps.p[q].halo, gp0[q], gp1[q]);
-    }
+    for (int q = 0; q < ps.n; ++q) tp_gather_launch<R, NP>(ps.p[q], V, gp0[q], gp1[q], st);
 }
 
 // nproj projections (1, or the 3 of a grid) x `planes` (1 or 2) planes each; cols0/cols1: first gradient column of the
@@ -1212,59 +1193,44 @@ static int tp_backward(int64_t V, const float* coords, int cs, int R, int planes
         const int rc = tp_backward(V, coords, cs, R, 1, nproj, pairs, sizes, grad, ld, cols0, cols0, gp0, gp0, scratch, st);
         return rc ? rc : tp_backward(V, coords, cs, R, 1, nproj, pairs, sizes, grad, ld, cols1, cols1, gp1, gp1, scratch, st);
     }
-    TpProjSet ps;
+    TpProjSetT<3> ps;
     ps.n = nproj;
     char* sc = (char*)scratch;
-    int total = 0;
     ZeroList zl;
-    for (int q = 0; q < nproj; ++q) {
-        TpProj& pj = ps.p[q];
-        pj.cx = pairs[q][0];
-        pj.cy = pairs[q][1];
-        pj.A = sizes[q][0];
-        pj.B = sizes[q][1];
-        pj.col0 = cols0[q];
-        pj.col1 = cols1[q];
-        sc = tp_carve(pj, V, R * planes, sc);
-        if (pj.tiles > TP_HIST_MAX_TILES) return 2;
-        total += pj.tiles;
-        zl.add(pj.count, (size_t)pj.tiles * TP_HEAD_ZEROED * 4, st);        // + gmax
-        zl.add(gp0[q], (size_t)R * pj.A * pj.B * 4, st);
-        if (planes == 2) zl.add(gp1[q], (size_t)R * pj.A * pj.B * 4, st);
-    }
+    for (int q = 0; q < nproj; ++q)
+        if (tp_tiles(sizes[q][0], sizes[q][1]) > (size_t)TP_HIST_MAX_TILES) return 2;
+    for (int q = 0; q < nproj; ++q)
+        sc = tp_setup_projection(ps.p[q], pairs[q][0], pairs[q][1], sizes[q][0], sizes[q][1], cols0[q], cols1[q], V, R, planes,
+                                 gp0[q], planes == 2 ? gp1[q] : nullptr, sc, zl, st);
     launch_zero(zl, st);
-    for (int q = 0; q < nproj; ++q) ps.p[q].part = (long long*)sc;
-    for (int q = nproj; q < 3; ++q) ps.p[q] = ps.p[0];
+    tp_close_set(ps, sc);
     if (V <= 0) return 0;
-    if (total > TP_HIST_MAX_TILES) {     // the three histograms do not fit one workgroup's LDS: one projection per pass
-        for (int q = 0; q < nproj; ++q) {
-            TpProjSet one;
-            one.n = 1;
-            one.p[0] = one.p[1] = one.p[2] = ps.p[q];
-#define SCR_TP_ONE(RR)                                                                                   \
-    case RR:                                                                                             \
-        if (planes == 2) tp_backward_launch<(RR <= 5 ? RR : 1), 2>(V, coords, cs, grad, ld, one, gp0 + q, gp1 + q, st); \
-        else tp_backward_launch<RR, 1>(V, coords, cs, grad, ld, one, gp0 + q, gp1 + q, st);              \
-        break;
-            switch (R) { SCR_TP_ONE(1) SCR_TP_ONE(2) SCR_TP_ONE(3) SCR_TP_ONE(4) SCR_TP_ONE(5) SCR_TP_ONE(6) SCR_TP_ONE(7) SCR_TP_ONE(8) SCR_TP_ONE(9) SCR_TP_ONE(10) SCR_TP_ONE(11) SCR_TP_ONE(12) SCR_TP_ONE(13) SCR_TP_ONE(14) SCR_TP_ONE(15) SCR_TP_ONE(16) }
-#undef SCR_TP_ONE
-        }
-        return 0;
-    }
+    auto run = [&](const TpProjSetT<3>& set, float* const* g0, float* const* g1) {
 #define SCR_TP_BWD(RR)                                                                                   \
     case RR:                                                                                             \
-        if (planes == 2) tp_backward_launch<(RR <= 5 ? RR : 1), 2>(V, coords, cs, grad, ld, ps, gp0, gp1, st); \
-        else tp_backward_launch<RR, 1>(V, coords, cs, grad, ld, ps, gp0, gp1, st);                       \
+        if (planes == 2) tp_backward_launch<(RR <= 5 ? RR : 1), 2>(V, coords, cs, grad, ld, set, g0, g1, st); \
+        else tp_backward_launch<RR, 1>(V, coords, cs, grad, ld, set, g0, g1, st);                        \
         break;
-    switch (R) { SCR_TP_BWD(1) SCR_TP_BWD(2) SCR_TP_BWD(3) SCR_TP_BWD(4) SCR_TP_BWD(5) SCR_TP_BWD(6) SCR_TP_BWD(7) SCR_TP_BWD(8) SCR_TP_BWD(9) SCR_TP_BWD(10) SCR_TP_BWD(11) SCR_TP_BWD(12) SCR_TP_BWD(13) SCR_TP_BWD(14) SCR_TP_BWD(15) SCR_TP_BWD(16) }
+        switch (R) { SCR_TP_BWD(1) SCR_TP_BWD(2) SCR_TP_BWD(3) SCR_TP_BWD(4) SCR_TP_BWD(5) SCR_TP_BWD(6) SCR_TP_BWD(7) SCR_TP_BWD(8) SCR_TP_BWD(9) SCR_TP_BWD(10) SCR_TP_BWD(11) SCR_TP_BWD(12) SCR_TP_BWD(13) SCR_TP_BWD(14) SCR_TP_BWD(15) SCR_TP_BWD(16) }
 #undef SCR_TP_BWD
+    };
+    if (tp_total_tiles(ps) <= TP_HIST_MAX_TILES) {
+        run(ps, gp0, gp1);
+        return 0;
+    }
+    for (int q = 0; q < nproj; ++q) {     // the three histograms do not fit one workgroup's LDS: one projection per pass
+        TpProjSetT<3> one;
+        one.n = 1;
+        one.p[0] = one.p[1] = one.p[2] = ps.p[q];
+        run(one, gp0 + q, gp1 + q);
+    }
     return 0;
 }
 
 // ---- all grids of a step at once (see tp_scatter9_kernel).  ngrids <= 3; grid g: R[g] channels per plane (the attention
 // grid arrives with its planes stacked), sizes X/Y/Z[g], first column col[g] of its 3 * R[g] gradient columns (xy, xz, yz
 // in this order); the columns of all grids are contiguous from col[0].  Returns 3 when the layout is not one the fused
-// pass handles (the caller falls back to one call per grid).
+// pass handles (the caller falls back to one call per grid); nothing has been enqueued then.
 size_t triplane_multi_scratch_bytes(int64_t V, int ngrids, const int* R, const int* X, const int* Y, const int* Z) {
     size_t b = 0;
     int widest = 1;
@@ -1273,24 +1239,6 @@ size_t triplane_multi_scratch_bytes(int64_t V, int ngrids, const int* R, const i
         widest = R[g] > widest ? R[g] : widest;
     }
     return b + tp_part_bytes(V, widest);
-}
-
-template <int RR, int NPX>
-static void tp_gather_launch(const TpProj& pj, int64_t V, float* gp, hipStream_t st) {
-    static bool big_lds[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !big_lds[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)tp_cell_gather_kernel<RR, NPX>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)tpn_lds_bytes<RR * NPX>());
-        if (e == hipSuccess && dev >= 0 && dev < 64) big_lds[dev] = true;
-        (void)hipGetLastError();
-    }
-    tp_cell_gather_kernel<RR, NPX><<<tp_gather_grid(pj, V), TPN_THREADS, tpn_lds_bytes<RR * NPX>(), st>>>(
-        pj.A, pj.B, pj.tb, pj.tiles, pj.start, pj.seg, pj.pfirst, pj.part, pj.gmax, pj.rec, gp, gp, pj.halo);
-    tp_split_finish_kernel<RR, NPX><<<dim3((unsigned)tp_max_split_tiles(V), RR * NPX), TPN_THREADS, 0, st>>>(pj.A, pj.B, pj.tb, pj.split, pj.seg, pj.pfirst, pj.part,
-                                                                                                       pj.gmax, gp, gp, pj.halo);
-    tp_border_sum_kernel<RR, NPX><<<dim3((unsigned)((pj.B + 255) / 256), (unsigned)pj.A), 256, 0, st>>>(pj.A, pj.B, pj.tb, pj.start, pj.halo, gp, gp);
 }
 
 // nl_coef (NULL: off): the gradient rows are formed from the BatchNorm-Linear's coefficients, its upstream gradient nl_dy
@@ -1311,43 +1259,34 @@ int launch_triplane_backward_multi(int64_t V, const float* coords, int cs, int n
     // (15: the attention grid's pair planes with the same-size plain grid's plane stacked on them, one record / gather per projection)
     const bool known = ((RA == 10 || RA == 5) && (RB == 0 || RB == 5) && (RC == 0 || RC == 5)) || (RA == 15 && (RB == 0 || RB == 5) && RC == 0);
     if (!known || (RC && !RB)) return 3;
-    TpProjSet9 ps;
+    size_t total = 0;
+    for (int g = 0; g < ngrids; ++g) total += tp_tiles(X[g], Y[g]) + tp_tiles(X[g], Z[g]) + tp_tiles(Y[g], Z[g]);
+    if (total > (size_t)TP_HIST_MAX_TILES) return 3;
+    TpProjSetT<9> ps;
     ZeroList zl;
     ps.n = 3 * ngrids;
     const int pairs[3][2] = {{1, 0}, {2, 0}, {2, 1}};
     char* sc = (char*)scratch;
-    int total = 0;
     for (int g = 0; g < ngrids; ++g) {
         const int sizes[3][2] = {{X[g], Y[g]}, {X[g], Z[g]}, {Y[g], Z[g]}};
-        for (int q = 0; q < 3; ++q) {
-            TpProj& pj = ps.p[3 * g + q];
-            pj.cx = pairs[q][0];
-            pj.cy = pairs[q][1];
-            pj.A = sizes[q][0];
-            pj.B = sizes[q][1];
-            pj.col0 = pj.col1 = col[g] + q * R[g];
-            sc = tp_carve(pj, V, R[g], sc);
-            total += pj.tiles;
-            zl.add(pj.count, (size_t)pj.tiles * TP_HEAD_ZEROED * 4, st);        // + gmax
-            zl.add(grad_planes[3 * g + q], (size_t)R[g] * pj.A * pj.B * 4, st);
-        }
+        for (int q = 0; q < 3; ++q)
+            sc = tp_setup_projection(ps.p[3 * g + q], pairs[q][0], pairs[q][1], sizes[q][0], sizes[q][1], col[g] + q * R[g],
+                                     col[g] + q * R[g], V, R[g], 1, grad_planes[3 * g + q], nullptr, sc, zl, st);
     }
     launch_zero(zl, st);
-    for (int q = 0; q < ps.n; ++q) ps.p[q].part = (long long*)sc;
-    for (int q = ps.n; q < 9; ++q) ps.p[q] = ps.p[0];
-    if (total > TP_HIST_MAX_TILES) return 3;
+    tp_close_set(ps, sc);
     if (V <= 0) return 0;
     const unsigned nwg = (unsigned)((V + TP_PER_WG - 1) / TP_PER_WG);
-    const size_t hb = (size_t)total * 4;
-    tp_count9_kernel<<<nwg, TP_THREADS, hb, st>>>(V, coords, cs, ps);
-    tp_scan9_kernel<<<ps.n, 1024, 0, st>>>(ps);
+    const size_t hb = total * 4;
+    tp_count_kernel<<<nwg, TP_THREADS, hb, st>>>(V, coords, cs, ps);
+    tp_scan_kernel<<<ps.n, 1024, 0, st>>>(ps);
 #define SCR_TP_S9(a, b, c)                                               \
     do {                                                                 \
         if (nl_coef) {                                                   \
-            tp_allow_lds((const void*)tp_scatter9_kernel<a, b, c, true>, 2 * hb);  \
+            allow_dynamic_lds((const void*)tp_scatter9_kernel<a, b, c, true>, TP_SCATTER_MAX_LDS);  \
             tp_scatter9_kernel<a, b, c, true><<<nwg, TP_THREADS, 2 * hb, st>>>(V, coords, cs, grad, ld, col[0], ps, nl_coef, nl_dy, nl_lddy, nl_x, nl_ldx); \
         } else {                                                         \
-            tp_allow_lds((const void*)tp_scatter9_kernel<a, b, c, false>, 2 * hb);  \
+            allow_dynamic_lds((const void*)tp_scatter9_kernel<a, b, c, false>, TP_SCATTER_MAX_LDS);  \
             tp_scatter9_kernel<a, b, c, false><<<nwg, TP_THREADS, 2 * hb, st>>>(V, coords, cs, grad, ld, col[0], ps, nullptr, nullptr, 0, nullptr, 0); \
         }                                                                \
     } while (0)
@@ -1361,9 +1300,11 @@ int launch_triplane_backward_multi(int64_t V, const float* coords, int cs, int n
 #undef SCR_TP_S9
     for (int g = 0; g < ngrids; ++g)
         for (int q = 0; q < 3; ++q) {
-            if (R[g] == 15) tp_gather_launch<15, 1>(ps.p[3 * g + q], V, grad_planes[3 * g + q], st);
-            else if (R[g] == 10) tp_gather_launch<10, 1>(ps.p[3 * g + q], V, grad_planes[3 * g + q], st);
-            else tp_gather_launch<5, 1>(ps.p[3 * g + q], V, grad_planes[3 * g + q], st);
+            const TpProj& pj = ps.p[3 * g + q];
+            float* gp = grad_planes[3 * g + q];
+            if (R[g] == 15) tp_gather_launch<15, 1>(pj, V, gp, gp, st);
+            else if (R[g] == 10) tp_gather_launch<10, 1>(pj, V, gp, gp, st);
+            else tp_gather_launch<5, 1>(pj, V, gp, gp, st);
         }
     return 0;
 }

@@ -55,8 +55,7 @@ def _backward_from(g, ind, cols, shapes):
     V, n = ind.shape[0], len(shapes)
     R, X, Y, Z = shapes[0][1], shapes[0][2], shapes[0][3], shapes[1][3]
     gp = [torch.empty(s, dtype=torch.float32, device=g.device) for s in shapes]
-    scratch = torch.empty(_C.scratch_size(_C.lib.scr_triplane_backward_scratch_bytes(V, X, Y, Z, R * (n // 3))), dtype=torch.uint8,
-                          device=g.device)
+    scratch = _C.scratch(_C.lib.scr_triplane_backward_scratch_bytes(V, X, Y, Z, R * (n // 3)), g.device)
     _C.check(_C.lib.scr_triplane_backward(V, ind.data_ptr(), ind.stride(0), R, X, Y, Z, n // 3, g.data_ptr(), g.stride(0),
                                           _C.host_array(cols), _C.ptr_array(gp), scratch.data_ptr(), _C.stream()))
     return gp

@@ -1121,6 +1121,47 @@ def test_all_grids_backward_in_one_pass(layout):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("R,n_planes", [(1, 3), (2, 6)])
+def test_plane_backward_one_projection_per_pass(R, n_planes):
+    """csrc/triplane.hip tp_backward: a grid whose three projections together have more tiles than one workgroup's LDS
+    histogram holds (TP_HIST_MAX_TILES = 16384) is bucketed one projection per pass.  2368^3 is the smallest cube over the
+    limit (3 x 74 x 74 = 16428 tiles) whose planes each stay under it.  Plain planes, and plain + attended planes (two
+    gradient blocks per projection); against F.grid_sample's backward, and bit for bit against a second run."""
+    import torch.nn.functional as F
+    from splatco_amd import triplane as tp
+    dev = torch.device("cuda:0")
+    # tied to csrc/triplane.hip: TP_HIST_MAX_TILES = 16384 tiles per pass, SCR_TP_TILE = 32 cells per tile edge.  With other
+    # values this shape may no longer reach the branch (nothing here can tell which branch ran): move S with them.
+    S, V = 2368, 20_000
+    assert 3 * ((S + 31) // 32) ** 2 > 16384 >= ((S + 31) // 32) ** 2
+    g = torch.Generator(device=dev).manual_seed(2368 + n_planes)
+    ind = torch.rand(V, 3, device=dev, generator=g) * 2.2 - 1.1
+    at = torch.randperm(V, device=dev, generator=g)[:300]
+    ind[at] = torch.randint(0, 2, (300, 3), device=dev, generator=g).float() * 2.0 - 1.0      # exact corners of the planes
+    planes = [(torch.randn(1, R, S, S, device=dev, generator=g) * 0.5).requires_grad_() for _ in range(n_planes)]
+    w = torch.randn(V, n_planes * R, device=dev, generator=g)
+
+    def run():
+        for p in planes:
+            p.grad = None
+        (tp.triplane_sample(ind, planes) * w).sum().backward()
+        return [p.grad for p in planes]
+
+    got = run()
+    assert all(torch.equal(a, b) for a, b in zip(got, run()))
+    pairs = ((1, 0), (2, 0), (2, 1))
+    for j, p in enumerate(planes):
+        p.grad = None
+        samp = F.grid_sample(p, ind[:, list(pairs[j % 3])].view(1, 1, V, 2), mode="bilinear", align_corners=True).flatten(0, 2).T
+        (samp * w[:, j * R:(j + 1) * R]).sum().backward()
+        scale = float(p.grad.abs().max())
+        err = float((got[j] - p.grad).abs().max())
+        print(f"plane {j}: max |ref| {scale:.4g}, max error {err:.3g}")
+        assert scale > 0 and err <= 5e-5 * scale + 1e-7, (j, err, scale)
+        p.grad = None
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("R,H,W", [(5, 70, 70), (2, 37, 91), (5, 200, 131)])
 def test_fused_plane_attention_matches_the_torch_module(R, H, W):
     """csrc/attention.hip against the torch TriPlaneAttention + chunk + cat chain it replaces (scene/grids.py:22-64,
