@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SCR_ABI_VERSION 29
+#define SCR_ABI_VERSION 30
 #define SCR_TILE 16 /* 16x16-pixel tiles: part of the result contract (tile rects, ranges, sort keys) */
 
 /* The 12 fields of GaussianRasterizationSettings, same order (gaussian_renderer/__init__.py:145-158).
@@ -66,6 +66,7 @@ size_t scr_geom_bytes(int64_t P, int32_t image_height, int32_t image_width); /* 
 size_t scr_binning_bytes(int64_t num_rendered, int64_t max_tile_instances);  /* per tile-instance lists */
 size_t scr_image_bytes(int32_t image_height, int32_t image_width);           /* final_T + n_contrib */
 size_t scr_backward_scratch_bytes(int64_t num_rendered);                     /* per-instance gradient records */
+size_t scr_backward_scratch_bytes_aux(int64_t num_rendered);                 /* the same + the per-instance depth sums of scr_backward_aux */
 
 /* ---- visible_filter: radii_out[P] int32 (> 0 <=> visible).  Either (scales, rotations) or cov3D_precomp. */
 int scr_visible_filter(int64_t P, const float* means3D, const float* scales, const float* rotations,
@@ -107,6 +108,17 @@ int scr_forward_run(int64_t P, int64_t num_rendered, int64_t max_tile_instances,
                     const scr_settings* settings, void* geom_buf, void* binning_buf, void* image_buf, float* out_color,
                     void* stream);
 
+/* ---- forward, phase 2, with the depth and opacity maps from the same pass (ABI 30).  out_depth / out_alpha are [H, W] fp32:
+ *   out_alpha = sum_i w_i,   out_depth = sum_i w_i z_i,   w_i = alpha_i T_i
+ * over exactly the contributors of out_color (same hit test, same T (1 - alpha) < 1e-4 stop, same n_contrib); z_i is the
+ * Gaussian's view-space depth ([x,y,z,1] * viewmatrix, third component -- the value of SCR_DBG_SPLAT_RECORDS[.][9]).  The
+ * background adds nothing to either map and the depth is NOT normalised: the expected depth of a pixel is
+ * out_depth / out_alpha where out_alpha > 0.  A colour that is not finite reaches neither map.  out_color, radii and the
+ * saved buffers are bit-identical to scr_forward_run's. */
+int scr_forward_run_aux(int64_t P, int64_t num_rendered, int64_t max_tile_instances, int64_t plan_flags,
+                        const scr_settings* settings, void* geom_buf, void* binning_buf, void* image_buf, float* out_color,
+                        float* out_depth, float* out_alpha, void* stream);
+
 /* ---- forward, both phases in one call when the caller's guess of the binning size was good enough.
  * Same as scr_forward_plan; then, if binning_buf is not NULL and binning_capacity_bytes >= scr_binning_bytes(I, max tile),
  * scr_forward_run on it without returning to the caller in between (the GPU otherwise idles for the caller's allocation and
@@ -116,6 +128,12 @@ int scr_forward_plan_run(int64_t P, int32_t M, const float* means3D, const float
                          const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
                          const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
                          void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color, void* stream);
+/* the same with the depth and opacity maps (see scr_forward_run_aux) */
+int scr_forward_plan_run_aux(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
+                             const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
+                             const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
+                             void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
+                             float* out_depth, float* out_alpha, void* stream);
 
 /* ---- backward.  dL_dcolor is [3,H,W].  Outputs (each may be NULL when its input was NULL):
  * dL_dmeans3D[P,3], dL_dmeans2D[P,3] (d/d NDC position, z = 0: the gradient SplatCo reads back
@@ -133,6 +151,21 @@ int scr_backward(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_flags,
                  float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
                  float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
                  void* stream);
+
+/* ---- backward of a loss on the colour image AND the maps of scr_forward_run_aux (ABI 30): every output is the gradient of
+ * the whole loss.  dL_ddepth / dL_dalpha are [H, W]; either may be NULL (that map took no part in the loss), with both NULL
+ * the call IS scr_backward.  dL_dcolor is always given (zeros when the image took no part).  The depth gradient reaches
+ * dL_dmeans3D through the view matrix, as the forward formed z.  scratch: scr_backward_scratch_bytes_aux (the records and,
+ * behind them, one float per instance).  Works on the saved buffers of either forward entry point; deterministic as
+ * scr_backward is. */
+int scr_backward_aux(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_flags, const float* means3D, const float* scales,
+                     const float* rotations, const float* cov3D_precomp, const float* shs,
+                     const scr_settings* settings, const int32_t* radii, void* geom_buf,
+                     const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
+                     const float* dL_dalpha, void* scratch,
+                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
+                     float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                     void* stream);
 
 /* ---- debug getters: copy the integer / float intermediates out of the opaque buffers (parity tests).
  * which: see SCR_DBG_*.  `out` is a device buffer of the stated element count. */

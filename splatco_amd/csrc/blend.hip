@@ -188,18 +188,23 @@ constexpr int FCHUNK = 64;  // list entries examined per round (one per lane)
 // SCR_PLAN_NONFINITE_COLOUR and the host picked this instantiation).  Such a colour must reach only the pixels its splat
 // contributes to, as it does where non-contributing splats are SKIPPED; blended with alpha 0 it would turn 0 * colour into
 // NaN for every pixel of every quadrant that stages the record.  The SAFE instantiation selects the colour sums instead.
-template <bool SAFE>
+// AUX: the depth map sum_i w_i z_i (w_i = alpha_i T_i over the contributors of the colour image, z_i = the view-space depth
+// of the splat record) and the accumulated opacity sum_i w_i = 1 - final T leave in the same pass: a sixth staged field
+// group carries z, one more accumulator per pixel, two more stores.  The background adds nothing to either map, and
+// neither sees a colour: a NaN colour (SAFE) cannot reach them.  With AUX false the kernel is the colour-only kernel.
+template <bool SAFE, bool AUX>
 __global__ void __launch_bounds__(64)
 blend_forward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict__ order, const unsigned long long* __restrict__ total,
                      const uint32_t* __restrict__ ranges,
                      const uint32_t* __restrict__ point_list, const uint8_t* __restrict__ qmask,
                      const float4* __restrict__ rec, const float* __restrict__ bg,
                      float* __restrict__ out_color, float* __restrict__ final_T,
-                     uint32_t* __restrict__ n_contrib) {
+                     uint32_t* __restrict__ n_contrib, float* __restrict__ out_depth, float* __restrict__ out_alpha) {
     // pair-interleaved staging: entry q holds splats 2q and 2q+1 field by field, so that one
     // ds_read_b128 lands (field of splat 2q, field of splat 2q+1) in adjacent registers and the
     // per-pixel arithmetic runs as packed fp32 (v_pk_fma_f32 & co: two splats per instruction)
-    __shared__ float4 sp[5][FCHUNK / 2];  // (mx,mx',my,my') (A,A',B,B') (C,C',o,o') (r,r',g,g') (b,b',j,j')
+    constexpr int NF = AUX ? 6 : 5;       // AUX: (z,z',-,-)
+    __shared__ float4 sp[NF][FCHUNK / 2];  // (mx,mx',my,my') (A,A',B,B') (C,C',o,o') (r,r',g,g') (b,b',j,j')
     // the four quadrant waves of a tile are consecutive slots of one XCD
     const int quad = (blockIdx.x / NUM_XCD) & 3;
     const int t = blend_tile((int)(blockIdx.x % NUM_XCD + (blockIdx.x / (4 * NUM_XCD)) * NUM_XCD), tiles, order, total);
@@ -213,6 +218,7 @@ blend_forward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict
     unsigned long long done = lanes(!inside);  // lane mask of finished pixels
     SCR_COUNT_DECL;
     float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
+    float D = 0.0f;     // AUX: sum w z
     float c099 = 0.99f;
     asm volatile("" : "+v"(c099));  // keep the clamp in a VGPR: VOP2 with a literal issues slower
     uint32_t last = 0;
@@ -221,7 +227,7 @@ blend_forward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict
     uint32_t m_next = 0, id_next = 0;           // chunk c+1's mask bit / id for this lane
     bool sel_cur = false;                       // chunk c: this lane holds a surviving splat
     float4 r0 = make_float4(0, 0, 0, 0), r1 = r0;
-    float r2x = 0.0f;
+    float r2x = 0.0f, r2y = 0.0f;
     auto load_mask_id = [&](uint32_t base, uint32_t& m, uint32_t& id) {
         uint32_t i = base + lane;
         bool have = i < n;
@@ -234,10 +240,11 @@ blend_forward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict
             r0 = rec[3 * (size_t)id];
             r1 = rec[3 * (size_t)id + 1];
             r2x = rec[3 * (size_t)id + 2].x;
+            if (AUX) r2y = rec[3 * (size_t)id + 2].y;      // the view-space depth
         }
     };
     // slots past a chunk's count are blended with alpha 0: they must hold finite numbers
-    for (int i = lane; i < 5 * (FCHUNK / 2); i += WAVE) (&sp[0][0])[i] = make_float4(0, 0, 0, 0);
+    for (int i = lane; i < NF * (FCHUNK / 2); i += WAVE) (&sp[0][0])[i] = make_float4(0, 0, 0, 0);
     uint32_t m0, id0;
     load_mask_id(0, m0, id0);
     gather(m0, id0);
@@ -259,6 +266,7 @@ blend_forward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict
             f2[h] = r1.x; f2[2 + h] = r1.y;
             f3[h] = r1.z; f3[2 + h] = r1.w;
             f4[h] = r2x;  f4[2 + h] = __uint_as_float(base + lane + 1);  // contributor number
+            if (AUX) ((float*)&sp[NF - 1][q])[h] = r2y;
         }
         // ---- put the next chunk's gathers and the one after's mask/id loads in flight
         gather(m_next, id_next);
@@ -271,12 +279,14 @@ blend_forward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict
             constexpr int NP = decltype(npairs)::value, NS = 2 * NP;
             v2f power[NP], al[NP];
             float4 p3[NP], p4[NP];
+            float2 p5[NP];
 #pragma unroll
             for (int h = 0; h < NP; ++h) {
                 const int q = (k >> 1) + h;  // pair index; slots past cnt hold stale data and are masked below
                 const float4 p0 = sp[0][q], p1 = sp[1][q], p2 = sp[2][q];
                 p3[h] = sp[3][q];
                 p4[h] = sp[4][q];
+                if (AUX) p5[h] = *(const float2*)&sp[NF - 1][q];
                 const v2f dx = v2f{p0.x, p0.y} - pxf, dy = v2f{p0.z, p0.w} - pyf;
                 const v2f A = {p1.x, p1.y}, B = {p1.z, p1.w}, Cq = {p2.x, p2.y}, o = {p2.z, p2.w};
                 // normative order: fma(dx, fma(A,dx,B*dy), (C*dy)*dy), both splats per instruction
@@ -333,6 +343,7 @@ blend_forward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict
                     C1 = __builtin_fmaf(cg, w, C1);
                     C2 = __builtin_fmaf(cb, w, C2);
                 }
+                if (AUX) D = __builtin_fmaf((u & 1) ? p5[h].y : p5[h].x, w, D);     // w = 0 where the splat takes no part; z is finite
                 T = T * (1.0f - a);
                 last = sel(live, __float_as_uint(cj), last);
             }
@@ -353,6 +364,10 @@ blend_forward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict
         out_color[2 * hw + pix] = __builtin_fmaf(T, bg[2], C2);
         final_T[pix] = T;
         n_contrib[pix] = last;
+        if (AUX) {
+            out_depth[pix] = D;
+            out_alpha[pix] = 1.0f - T;     // sum w: every blended splat takes w = alpha T out of T
+        }
     }
 }
 
@@ -418,12 +433,15 @@ constexpr int TCS = WAVE + 4;   // words per column of a wave's transposition bl
 struct PixState {
     float T, dLp0, dLp1, dLp2;
     float behind, last_alpha, d_last;
+    float dLd, dLa;     // AUX: dL/ddepth and dL/dalpha-map of the pixel
 };
 // SAFE (a colour that is not finite is among the call's Gaussians, see blend_forward_kernel): the colour term of a splat
 // that does not contribute to this pixel (`hit` clear; G = alpha = 0) is dropped by a select -- 0 * NaN is not 0, and the
 // reference skips such a splat altogether.
-template <bool SAFE>
-__device__ __forceinline__ void splat_pixel_grad(PixState& s, float T, float4 b, float cb, float G, float alpha,
+// AUX: the depth and opacity maps are two more channels of the same blend, with per-splat "colours" z and 1 and background
+// 0: they add z dL/ddepth + dL/dalpha-map to d and nothing to the start value of `behind`.
+template <bool SAFE, bool AUX>
+__device__ __forceinline__ void splat_pixel_grad(PixState& s, float T, float4 b, float cb, float z, float G, float alpha,
                                                  unsigned long long hit, float& Y, float& w) {
 #pragma clang fp contract(fast)
     // T = transmittance in front of this splat (group_transmittance)
@@ -432,6 +450,7 @@ __device__ __forceinline__ void splat_pixel_grad(PixState& s, float T, float4 b,
     // makes Inf - Inf of it)
     s.behind = SAFE ? s.last_alpha * s.d_last + (1.0f - s.last_alpha) * s.behind : s.last_alpha * (s.d_last - s.behind) + s.behind;
     float d = b.z * s.dLp0 + b.w * s.dLp1 + cb * s.dLp2;
+    if (AUX) d += z * s.dLd + s.dLa;
     if (SAFE) d = sel(hit, d, 0.0f);
     Y = G * (T * (d - s.behind));  // G = opacity * exp(power) here: the unclamped alpha times dL/dalpha (straight-through min(0.99, .))
     if (SAFE) Y = sel(hit, Y, 0.0f);     // `behind` is NaN once a NaN colour contributed to this pixel; a skipped splat takes nothing from it
@@ -469,12 +488,24 @@ __device__ __forceinline__ void store16_dword_aligned(void* p, float4 v) {
 }
 
 // ------------------------------------------------------------------ backward
+// what a lane keeps of the third part of a gathered splat record: blue, and with AUX the depth.  (A member that exists only
+// with AUX: a plain variable that the colour-only instantiation never reads still reorders its register moves.)
+template <bool AUX> struct RecTail { float x; };
+template <> struct RecTail<true> { float x, z; };
 constexpr int BCH = 64;  // list entries per round: one per lane of each wave
 constexpr int BWD_MIN_WAVES = 4;   // 128 VGPRs, 39.3 KB of LDS: four workgroups per CU; no spills
 constexpr int ACC_BUFS = 2;        // per-round sums double-buffered by round parity (one barrier per round)
 
-template <bool SAFE>       // see blend_forward_kernel / splat_pixel_grad
-__global__ void __launch_bounds__(256, BWD_MIN_WAVES)
+// AUX (gradients of the depth and opacity maps, see splat_pixel_grad): the per-splat sum  sum_pixels (alpha T) dL/ddepth  is
+// the fourth weighted sum of the alpha T columns.  It rides in the colour lanes' x-weighted companions, which are zero
+// otherwise, through the same column_fold (it comes out in the odd banks of the colour columns), takes one more LDS slot
+// per (wave, position), is added over the waves in the same fixed order by wave 3 -- idle in the colour-only combine -- and
+// goes to a float stream of its own at the record's Gaussian-major index (grad_z).  The opacity map's "colour" is the
+// constant 1: no sum of its own.  2 KB more LDS (41.3 KB) leave three workgroups per CU; the instantiation is compiled
+// for that occupancy.
+constexpr int BWD_MIN_WAVES_AUX = 3;
+template <bool SAFE, bool AUX>       // see blend_forward_kernel / splat_pixel_grad
+__global__ void __launch_bounds__(256, AUX ? BWD_MIN_WAVES_AUX : BWD_MIN_WAVES)
 blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict__ order, const unsigned long long* __restrict__ total,
                       const uint32_t* __restrict__ ranges,
                       const uint32_t* __restrict__ point_list, const uint32_t* __restrict__ gm_index,
@@ -483,9 +514,10 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
                       const float* __restrict__ bg, const float* __restrict__ final_T,
                       const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
                       GradRec* __restrict__ grad_rec, unsigned long long* __restrict__ cut_key, unsigned long long stamp,
-                      uint8_t* __restrict__ has_rec) {
+                      uint8_t* __restrict__ has_rec, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha,
+                      float* __restrict__ grad_z) {
     // wave-private compacted records of the round: [wave][field group][3 pad + position]; group 0/1 =
-    // the first 32 bytes of the splat record, group 2 = (blue, position in round, -, -).  A group of four
+    // the first 32 bytes of the splat record, group 2 = (blue, position in round, AUX: depth, -).  A group of four
     // reads slots k .. k+3 of each field group: one address register and immediate offsets.  The three
     // pad slots in front stay zero (a partial last group blends them with alpha 0).
     __shared__ float4 st[4][3][BCH + 4];
@@ -493,6 +525,7 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
     // until the wave has shifted them to the splat's centre, the record layout afterwards
     __shared__ float4 accA[ACC_BUFS][4][BCH], accB[ACC_BUFS][4][BCH];
     __shared__ float accC[ACC_BUFS][4][BCH];
+    __shared__ float accD[ACC_BUFS][4][BCH];     // AUX: sum (alpha T) dL/ddepth per position (unused, so not allocated, without)
     __shared__ __attribute__((aligned(16))) float tr[4][8 * TCS];    // the waves' transposition blocks (column_fold)
     __shared__ uint32_t wave_max[4];
     const int t = blend_tile((int)blockIdx.x, tiles, order, total);
@@ -518,21 +551,28 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
     }
     ps.behind = (bg[0] * ps.dLp0 + bg[1] * ps.dLp1) + bg[2] * ps.dLp2;
     ps.last_alpha = ps.d_last = 0.0f;
+    if (AUX) {      // either map may have taken no part in the loss (kernel-uniform)
+        ps.dLd = inside && dL_ddepth ? dL_ddepth[pix] : 0.0f;
+        ps.dLa = inside && dL_dalpha ? dL_dalpha[pix] : 0.0f;
+    }
     float c099 = 0.99f;
     asm volatile("" : "+v"(c099));  // keep the clamp in a VGPR: VOP2 with a literal issues slower
     SCR_COUNT_DECL;
     // the reducing role of this lane: column rcol of the transposition block (0-3: Y of the group's splats, 4-7: alpha T),
     // pixel column rx of the quadrant; its weights for the eight pixels (rx, y)
     const int rcol = lane >> 3, rx = lane & 7;
-    float wgt[3][8];
+    constexpr int WZ = AUX ? 3 : 0;      // AUX: row WZ = dL/ddepth in the alpha T columns, 0 in the Y columns
+    float wgt[AUX ? 4 : 3][8];
 #pragma unroll
     for (int y = 0; y < 8; ++y) {
         wgt[0][y] = 1.0f; wgt[1][y] = (float)y; wgt[2][y] = (float)(y * y);
+        if (AUX) wgt[WZ][y] = 0.0f;
         if (rcol >= 4) {
             const bool in = qx0 + rx < W && qy0 + y < H;
             const size_t q = (size_t)(qy0 + y) * W + (size_t)(qx0 + rx);
 #pragma unroll
             for (int c = 0; c < 3; ++c) wgt[c][y] = in ? dL_dpix[c * hw + q] : 0.0f;
+            if (AUX) wgt[WZ][y] = in && dL_ddepth ? dL_ddepth[q] : 0.0f;
         }
     }
     const float xw = rcol < 4 ? (float)rx : 0.0f;
@@ -543,6 +583,7 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
     // from a colour column's even bank
     const int rkind = rcol >= 4 ? 2 : (lane >> 2) & 1;
     const bool rstore = (lane & 3) == 0 && (rcol < 4 || ((lane >> 2) & 1) == 0);
+    const bool rstore_z = AUX && (lane & 3) == 0 && rcol >= 4 && ((lane >> 2) & 1) == 1;     // a colour column's odd bank
     const int rcu = rcol & 3;                                    // the column's splat of the group
     // (lane masks in SGPR pairs: the list position of the column's splat is selected from the four the group's record reads
     // broadcast anyway -- an LDS read of its own would be a second exposed round trip per group)
@@ -595,14 +636,16 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
         const uint2 b = gm_base[id];      // deep lists: 8 B per Gaussian (scatter_kernel), index of its rect walk's origin + rect width
         return b.x + tile_y * b.y + tile_x;
     };
-    if (!cut && wave < 3)
-        for (int ci = nround - 1; ci > live_top; --ci) {     // all-zero records (waves 0..2 write one part each)
+    if (!cut && (AUX || wave < 3))
+        for (int ci = nround - 1; ci > live_top; --ci) {     // all-zero records (waves 0..2 write one part each; AUX: wave 3 the depth sum)
             const uint32_t i = (uint32_t)ci * BCH + lane;
             if (i < n && qmask[lo + i] != 0) {     // mask 0: no record (see the combine below)
-                GradRec& gr = grad_rec[gm_of(lo + i, point_list[lo + i])];
+                const uint32_t gmi = gm_of(lo + i, point_list[lo + i]);
+                GradRec& gr = grad_rec[gmi];
                 if (wave == 0) store16_dword_aligned(&gr.a, make_float4(0, 0, 0, 0));
                 else if (wave == 1) store16_dword_aligned(&gr.b, make_float4(0, 0, 0, 0));
-                else gr.c = 0.0f;
+                else if (!AUX || wave == 2) gr.c = 0.0f;
+                else grad_z[gmi] = 0.0f;
             }
         }
 
@@ -612,7 +655,7 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
     uint32_t m_cur = 0, slot_cur = 0, id_cur = 0;     // round ci (records in r0/r1/r2x)
     bool sel_cur = false;
     float4 r0 = make_float4(0, 0, 0, 0), r1 = r0;
-    float r2x = 0.0f;
+    RecTail<AUX> r2 = {};
     auto load_meta = [&](int ci, uint32_t& m, uint32_t& id, uint32_t& slot) {
         const uint32_t i = (uint32_t)ci * BCH + lane;
         const bool have = ci >= 0 && i < n;
@@ -629,7 +672,8 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
         if (sel_cur) {
             r0 = rec[3 * (size_t)id];
             r1 = rec[3 * (size_t)id + 1];
-            r2x = rec[3 * (size_t)id + 2].x;
+            r2.x = rec[3 * (size_t)id + 2].x;
+            if constexpr (AUX) r2.z = rec[3 * (size_t)id + 2].y;      // the view-space depth
         }
     };
     if (live_top >= 0) {
@@ -648,7 +692,9 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
             const uint32_t pos = lanes_below(bal);
             st[wave][0][pos + 3] = r0;
             st[wave][1][pos + 3] = r1;
-            st[wave][2][pos + 3] = make_float4(r2x, __uint_as_float((uint32_t)lane), 0.0f, 0.0f);
+            float r2z = 0.0f;
+            if constexpr (AUX) r2z = r2.z;
+            st[wave][2][pos + 3] = make_float4(r2.x, __uint_as_float((uint32_t)lane), r2z, 0.0f);
         }
         const uint32_t m_this = m_cur, slot_this = slot_cur, id_this = id_cur;
         gather(ci - 1, m_next, id_next, slot_next);
@@ -668,11 +714,13 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
             // all four records first (one LDS round trip per group instead of four)
             float4 ra[4], rb[4];
             float2 rc[4];
+            float rz[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int u = 0; u < 4; ++u) {  // entry k - u lives in slot k - u + 3
                 ra[u] = st[wave][0][k + 3 - u];
                 rb[u] = st[wave][1][k + 3 - u];
                 rc[u] = *(const float2*)&st[wave][2][k + 3 - u];
+                if (AUX) rz[u] = st[wave][2][k + 3 - u].z;
             }
             float Gs[4], al[4], om[4], Tu[4];
 #pragma unroll
@@ -713,7 +761,7 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
                     Y[u] = Wt[u] = 0.0f;
                     continue;
                 }
-                splat_pixel_grad<SAFE>(ps, Tu[u], rb[u], rc[u].x, Gs[u], al[u], hits[u], Y[u], Wt[u]);
+                splat_pixel_grad<SAFE, AUX>(ps, Tu[u], rb[u], rc[u].x, rz[u], Gs[u], al[u], hits[u], Y[u], Wt[u]);
             }
             // (a group none of whose splats reaches any pixel of the quadrant -- 0.1 % of them at the benchmark density -- goes
             // through the same path with zeros: a wave-uniform skip cost every group five scalar instructions)
@@ -746,7 +794,17 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
                     o2 = __builtin_fmaf(wgt[2][y + 1], v[y + 1], o2);
                 }
                 s0 = e0 + o0; s1 = e1 + o1; s2 = e2 + o2;
-                const float t0 = xw * s0, t1 = xw * t0, t2 = xw * s1;      // x S0, x^2 S0, x S1 (colour lanes: 0)
+                float t0 = xw * s0;
+                if (AUX) {      // the fourth sum of the alpha T columns, same two half-chains; the Y columns' weights are 0
+                    float e3 = wgt[WZ][0] * v[0], o3 = wgt[WZ][1] * v[1];
+#pragma unroll
+                    for (int y = 2; y < 8; y += 2) {
+                        e3 = __builtin_fmaf(wgt[WZ][y], v[y], e3);
+                        o3 = __builtin_fmaf(wgt[WZ][y + 1], v[y + 1], o3);
+                    }
+                    t0 = __builtin_fmaf(xw, s0, e3 + o3);     // Y lanes: x S0 + 0; colour lanes: 0 S0 + the depth sum
+                }
+                const float t1 = xw * t0, t2 = xw * s1;      // x S0, x^2 S0, x S1 (colour lanes: 0)
                 column_fold(s0, s1, s2, t0, t1, t2);
             }
             // column rcol & 3 is splat u of the group, entry k - u of the wave's list; every listed position is written
@@ -755,6 +813,10 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
                 *(float*)(rdst0 + par * PAR_A + jw * 16u) = s0;
                 *(float*)(rdst1 + par * PAR_A + jw * 16u) = s1;
                 *(float*)(rdst2 + par * rpar2 + jw * rstride2) = s2;
+            }
+            if (AUX && rstore_z && (!TAIL || k - rcu >= 0)) {
+                const uint32_t jw = sel(rcu3, jj[3], sel(rcu2, jj[2], sel(rcu1, jj[1], jj[0])));
+                accD[par][wave][jw] = s0;
             }
         };
         int k = cnt - 1;
@@ -801,6 +863,15 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
                 if (has_rec) has_rec[id_this] = 1;      // deep lists (kernel-uniform): this Gaussian has something to sum
             }
         }
+        if (AUX && wave == 3 && base + lane < n && m_this != 0) {     // the depth sum of the same entries, same order
+            const uint32_t i = base + lane;
+            float r = 0.0f;
+            if (((m_this >> 0) & 1u) && i < wmax0) r += accD[par][0][lane];
+            if (((m_this >> 1) & 1u) && i < wmax1) r += accD[par][1][lane];
+            if (((m_this >> 2) & 1u) && i < wmax2) r += accD[par][2][lane];
+            if (((m_this >> 3) & 1u) && i < wmax3) r += accD[par][3][lane];
+            grad_z[slot_this] = r;
+        }
     }
     SCR_COUNT_SUB_FLUSH(14, 15);
     SCR_COUNT_FLUSH(lane);
@@ -817,29 +888,35 @@ static int blend_slots_per_xcd(const Grid& g) {
 }
 
 void launch_blend_forward(const KSettings& ks, const GeomView& gv, const BinView& bv, const ImgView& iv,
-                          float* out_color, bool longest_first, bool safe, hipStream_t st) {
+                          float* out_color, float* out_depth, float* out_alpha, bool longest_first, bool safe,
+                          hipStream_t st) {
     Grid g(ks.H, ks.W);
     // gv.tile_count has been consumed by the plan scan: with longest_first it holds from here on every XCD's tiles,
     // longest list first, and total[2] says so to this launch and to the backward one
     if (longest_first)
         tile_order_kernel<<<NUM_XCD, 1024, 0, st>>>(g.tiles, g.gx, gv.ranges, gv.tile_count, gv.total + 2, gv.total + 4);
-    auto kernel = safe ? blend_forward_kernel<true> : blend_forward_kernel<false>;
+    const bool aux = out_depth != nullptr;      // both maps or neither (capi.hip)
+    auto kernel = aux ? (safe ? blend_forward_kernel<true, true> : blend_forward_kernel<false, true>)
+                      : (safe ? blend_forward_kernel<true, false> : blend_forward_kernel<false, false>);
     kernel<<<(unsigned)blend_slots_per_xcd(g) * NUM_XCD * 4, 64, 0, st>>>(
         ks.W, ks.H, g.gx, g.tiles, gv.tile_count, gv.total, gv.ranges, bv.point_list, bv.qmask, gv.rec, ks.bg, out_color, iv.final_T,
-        iv.n_contrib);
+        iv.n_contrib, out_depth, out_alpha);
 }
 
 void launch_blend_backward(const KSettings& ks, const GeomView& gv, const BinView& bv, const ImgView& iv,
-                           const float* dL_dcolor, GradRec* grad_rec, unsigned long long stamp, bool deep, bool flags,
-                           bool safe, hipStream_t st) {
+                           const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha, GradRec* grad_rec,
+                           float* grad_z, unsigned long long stamp, bool deep, bool flags, bool safe, hipStream_t st) {
     Grid g(ks.H, ks.W);
     const bool gm_from_base = deep;
     if (flags) { ZeroList z; z.add(gv.has_rec, ((size_t)gv.P + 3) / 4 * 4, st); launch_zero(z, st); }   // (the array is padded to 256 bytes)
-    auto kernel = safe ? blend_backward_kernel<true> : blend_backward_kernel<false>;
+    const bool aux = grad_z != nullptr;      // the depth / opacity maps took part in the loss
+    auto kernel = aux ? (safe ? blend_backward_kernel<true, true> : blend_backward_kernel<false, true>)
+                      : (safe ? blend_backward_kernel<true, false> : blend_backward_kernel<false, false>);
     kernel<<<(unsigned)blend_slots_per_xcd(g) * NUM_XCD, 256, 0, st>>>(
         ks.W, ks.H, g.gx, g.tiles, gv.tile_count, gv.total, gv.ranges, bv.point_list, gm_from_base ? nullptr : bv.gm_index, gv.gm_base,
         bv.qmask, gv.rec, ks.bg,
-        iv.final_T, iv.n_contrib, dL_dcolor, grad_rec, iv.cut_key, stamp, flags ? gv.has_rec : nullptr);
+        iv.final_T, iv.n_contrib, dL_dcolor, grad_rec, iv.cut_key, stamp, flags ? gv.has_rec : nullptr, dL_ddepth, dL_dalpha,
+        grad_z);
 }
 
 }  // namespace scr

@@ -183,7 +183,8 @@ const char* scr_last_error(void) { return g_err; }
 size_t scr_geom_bytes(int64_t P, int32_t H, int32_t W) { return geom_view(nullptr, P, H, W).bytes; }
 size_t scr_binning_bytes(int64_t I, int64_t max_tile) { return bin_view(nullptr, I, max_tile).bytes; }
 size_t scr_image_bytes(int32_t H, int32_t W) { return img_view(nullptr, H, W).bytes; }
-size_t scr_backward_scratch_bytes(int64_t I) { return align_up((size_t)(I > 0 ? I : 1) * sizeof(GradRec)); }
+size_t scr_backward_scratch_bytes(int64_t I) { return grad_rec_bytes(I); }
+size_t scr_backward_scratch_bytes_aux(int64_t I) { return grad_rec_bytes(I) + grad_z_bytes(I); }
 
 int scr_visible_filter(int64_t P, const float* means3D, const float* scales, const float* rotations,
                        const float* cov3D_precomp, const scr_settings* settings, int32_t* radii_out,
@@ -290,17 +291,29 @@ int scr_forward_plan(int64_t P, int32_t M, const float* means3D, const float* sc
     return rc ? rc : plan_wait(settings, geom_buf, P, seq, plan_host, (hipStream_t)stream);
 }
 
+// out_depth / out_alpha: both NULL (the colour-only entry points) or both given (the *_aux ones)
 static int forward_run_impl(int64_t P, int64_t I, int64_t max_tile, int64_t plan_flags, const scr_settings* settings, void* geom_buf,
-                            void* binning_buf, void* image_buf, float* out_color, void* stream, bool scatter_done);
+                            void* binning_buf, void* image_buf, float* out_color, float* out_depth, float* out_alpha,
+                            void* stream, bool scatter_done);
 
 int scr_forward_run(int64_t P, int64_t I, int64_t max_tile, int64_t plan_flags, const scr_settings* settings, void* geom_buf,
                     void* binning_buf, void* image_buf, float* out_color, void* stream) {
     SCR_MARK_FN;
-    return forward_run_impl(P, I, max_tile, plan_flags, settings, geom_buf, binning_buf, image_buf, out_color, stream, false);
+    return forward_run_impl(P, I, max_tile, plan_flags, settings, geom_buf, binning_buf, image_buf, out_color, nullptr, nullptr,
+                            stream, false);
+}
+
+int scr_forward_run_aux(int64_t P, int64_t I, int64_t max_tile, int64_t plan_flags, const scr_settings* settings, void* geom_buf,
+                        void* binning_buf, void* image_buf, float* out_color, float* out_depth, float* out_alpha, void* stream) {
+    SCR_MARK_FN;
+    if (!out_depth || !out_alpha) return fail("out_depth / out_alpha is NULL");
+    return forward_run_impl(P, I, max_tile, plan_flags, settings, geom_buf, binning_buf, image_buf, out_color, out_depth, out_alpha,
+                            stream, false);
 }
 
 static int forward_run_impl(int64_t P, int64_t I, int64_t max_tile, int64_t plan_flags, const scr_settings* settings, void* geom_buf,
-                            void* binning_buf, void* image_buf, float* out_color, void* stream, bool scatter_done) {
+                            void* binning_buf, void* image_buf, float* out_color, float* out_depth, float* out_alpha,
+                            void* stream, bool scatter_done) {
     if (check_settings(settings)) return 1;
     if (plan_flags & ~(int64_t)(SCR_PLAN_NONFINITE_COLOUR | SCR_PLAN_LARGE_RECTS)) return fail("plan_flags %lld: not a value scr_forward_plan returned", (long long)plan_flags);
     if (!geom_buf || !binning_buf || !image_buf || !out_color) return fail("NULL buffer");
@@ -317,17 +330,45 @@ static int forward_run_impl(int64_t P, int64_t I, int64_t max_tile, int64_t plan
         { ProfScope ps_(SCR_PROF_TILE_SORT, st); launch_tile_sort(ks, gv, bv, max_tile, !deep_lists(I, Grid(ks.H, ks.W).tiles), st); }
         CHECK_LAUNCH("tile_sort_kernel", settings->debug, st);
     }
-    { ProfScope ps_(SCR_PROF_BLEND_FORWARD, st); launch_blend_forward(ks, gv, bv, iv, out_color, 2 * max_tile * (int64_t)Grid(ks.H, ks.W).tiles > 3 * I,
+    { ProfScope ps_(SCR_PROF_BLEND_FORWARD, st); launch_blend_forward(ks, gv, bv, iv, out_color, out_depth, out_alpha, 2 * max_tile * (int64_t)Grid(ks.H, ks.W).tiles > 3 * I,
                                                                       (plan_flags & SCR_PLAN_NONFINITE_COLOUR) != 0, st); }
     CHECK_LAUNCH("blend_forward_kernel", settings->debug, st);
     return 0;
 }
+
+static int forward_plan_run_impl(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
+                                 const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
+                                 const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
+                                 void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
+                                 float* out_depth, float* out_alpha, void* stream);
 
 int scr_forward_plan_run(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
                          const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
                          const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
                          void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color, void* stream) {
     SCR_MARK_FN;
+    return forward_plan_run_impl(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
+                                 radii_out, plan_host, binning_buf, binning_capacity_bytes, image_buf, out_color, nullptr, nullptr,
+                                 stream);
+}
+
+int scr_forward_plan_run_aux(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
+                             const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
+                             const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
+                             void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
+                             float* out_depth, float* out_alpha, void* stream) {
+    SCR_MARK_FN;
+    if (binning_buf && image_buf && out_color && (!out_depth || !out_alpha)) return fail("out_depth / out_alpha is NULL");
+    return forward_plan_run_impl(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
+                                 radii_out, plan_host, binning_buf, binning_capacity_bytes, image_buf, out_color, out_depth, out_alpha,
+                                 stream);
+}
+
+static int forward_plan_run_impl(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
+                                 const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
+                                 const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
+                                 void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
+                                 float* out_depth, float* out_alpha, void* stream) {
     if (!plan_host) return fail("plan_host is NULL");
     plan_host[2] = 0;
     hipStream_t st = (hipStream_t)stream;
@@ -363,11 +404,21 @@ int scr_forward_plan_run(int64_t P, int32_t M, const float* means3D, const float
         }
         return 0;                                  // caller allocates, then scr_forward_run
     }
-    rc = forward_run_impl(P, plan_host[0], plan_host[1], plan_host[3], settings, geom_buf, binning_buf, image_buf, out_color, stream, scattered);
+    rc = forward_run_impl(P, plan_host[0], plan_host[1], plan_host[3], settings, geom_buf, binning_buf, image_buf, out_color, out_depth,
+                          out_alpha, stream, scattered);
     if (rc) return rc;
     plan_host[2] = 1;
     return 0;
 }
+
+static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
+                         const float* rotations, const float* cov3D_precomp, const float* shs,
+                         const scr_settings* settings, const int32_t* radii, void* geom_buf,
+                         const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
+                         const float* dL_dalpha, void* scratch,
+                         float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
+                         float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                         void* stream);
 
 int scr_backward(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
                  const float* rotations, const float* cov3D_precomp, const float* shs,
@@ -377,6 +428,34 @@ int scr_backward(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const floa
                  float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
                  void* stream) {
     SCR_MARK_FN;
+    return backward_impl(P, M, I, plan_flags, means3D, scales, rotations, cov3D_precomp, shs, settings, radii, geom_buf, binning_buf,
+                         image_buf, dL_dcolor, nullptr, nullptr, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dsh, dL_dopacity,
+                         dL_dscales, dL_drotations, dL_dcov3D, stream);
+}
+
+int scr_backward_aux(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
+                     const float* rotations, const float* cov3D_precomp, const float* shs,
+                     const scr_settings* settings, const int32_t* radii, void* geom_buf,
+                     const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
+                     const float* dL_dalpha, void* scratch,
+                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
+                     float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                     void* stream) {
+    SCR_MARK_FN;
+    return backward_impl(P, M, I, plan_flags, means3D, scales, rotations, cov3D_precomp, shs, settings, radii, geom_buf, binning_buf,
+                         image_buf, dL_dcolor, dL_ddepth, dL_dalpha, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dsh, dL_dopacity,
+                         dL_dscales, dL_drotations, dL_dcov3D, stream);
+}
+
+// dL_ddepth / dL_dalpha both NULL: the colour-only kernels, whichever entry point was called
+static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
+                         const float* rotations, const float* cov3D_precomp, const float* shs,
+                         const scr_settings* settings, const int32_t* radii, void* geom_buf,
+                         const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
+                         const float* dL_dalpha, void* scratch,
+                         float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
+                         float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                         void* stream) {
     if (check_settings(settings)) return 1;
     if (P == 0) return 0;
     if (plan_flags & ~(int64_t)(SCR_PLAN_NONFINITE_COLOUR | SCR_PLAN_LARGE_RECTS)) return fail("plan_flags %lld: not a value scr_forward_plan returned", (long long)plan_flags);
@@ -393,6 +472,8 @@ int scr_backward(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const floa
     // a value no earlier call of this process used (and that uninitialised memory is unlikely to hold): see blend.hip
     static std::atomic<unsigned long long> stamp_counter{0x5ca1ab1e00000000ull};
     const unsigned long long stamp = ++stamp_counter;
+    // the depth sums lie behind the records (scr_backward_scratch_bytes_aux)
+    float* const grad_z = (I > 0 && (dL_ddepth || dL_dalpha)) ? (float*)((char*)scratch + grad_rec_bytes(I)) : nullptr;
     if (settings->debug) {      // the flags the caller carried from scr_forward_plan against the ones the forward left in geom_buf
         unsigned long long dev_flags = 0;
         HIP_TRY(hipMemcpyAsync(&dev_flags, gv.total + 3, 8, hipMemcpyDeviceToHost, st));
@@ -404,16 +485,16 @@ int scr_backward(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const floa
         // records 32.. of large rects are cleared whatever plan_flags says: the kernel reads the forward's verdict from
         // geom_buf and leaves at once when there are none (2 us), so a stale argument cannot make preprocess_backward sum
         // uninitialised scratch
-        launch_zero_far_records(P, gv, (GradRec*)scratch, st);
+        launch_zero_far_records(P, gv, (GradRec*)scratch, grad_z, st);
         CHECK_LAUNCH("zero_far_records_kernel", settings->debug, st);
         { ProfScope ps_(SCR_PROF_BLEND_BACKWARD, st);
-          launch_blend_backward(ks, gv, bv, iv, dL_dcolor, (GradRec*)scratch, stamp, deep_lists(I, Grid(ks.H, ks.W).tiles),
+          launch_blend_backward(ks, gv, bv, iv, dL_dcolor, dL_ddepth, dL_dalpha, (GradRec*)scratch, grad_z, stamp, deep_lists(I, Grid(ks.H, ks.W).tiles),
                                 record_flags(I, Grid(ks.H, ks.W).tiles), (plan_flags & SCR_PLAN_NONFINITE_COLOUR) != 0, st); }
         CHECK_LAUNCH("blend_backward_kernel", settings->debug, st);
     }
     { ProfScope ps_(SCR_PROF_PREPROCESS_BACKWARD, st);
       launch_preprocess_backward(P, M, means3D, scales, rotations, cov3D_precomp, shs, ks, radii, gv, bv,
-                                 (const GradRec*)scratch, iv.cut_key, stamp, record_flags(I, Grid(ks.H, ks.W).tiles), dL_dmeans3D, dL_dmeans2D, shs ? nullptr : dL_dcolors,
+                                 (const GradRec*)scratch, grad_z, iv.cut_key, stamp, record_flags(I, Grid(ks.H, ks.W).tiles), dL_dmeans3D, dL_dmeans2D, shs ? nullptr : dL_dcolors,
                                  shs ? dL_dsh : nullptr, dL_dopacity, cov3D_precomp ? nullptr : dL_dscales,
                                  cov3D_precomp ? nullptr : dL_drotations, cov3D_precomp ? dL_dcov3D : nullptr, st); }
     CHECK_LAUNCH("preprocess_backward_kernel", settings->debug, st);

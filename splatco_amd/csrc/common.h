@@ -140,6 +140,11 @@ inline __host__ BinView bin_view(void* base, int64_t I, int64_t max_tile_instanc
 struct __attribute__((packed, aligned(4))) GradQuad { float x, y, z, w; };
 struct __attribute__((packed, aligned(4))) GradRec { GradQuad a, b; float c; };
 static_assert(sizeof(GradRec) == 36, "36-byte gradient records");
+// With gradients of the depth / opacity maps (the *_aux entry points) a second stream lies behind the records: one float per
+// instance at the same Gaussian-major index, sum_pixels (alpha T) dL/ddepth.  It is written, zeroed and skipped exactly where
+// the record of the same index is, so every verdict of the record readers (live_bits, cut keys, has_rec) holds for it.
+inline __host__ size_t grad_rec_bytes(int64_t I) { return align_up((size_t)(I > 0 ? I : 1) * sizeof(GradRec)); }
+inline __host__ size_t grad_z_bytes(int64_t I) { return align_up((size_t)(I > 0 ? I : 1) * sizeof(float)); }
 
 // ---- image buffer ----
 struct ImgView {
@@ -328,7 +333,7 @@ struct ZeroList {
     void add(void* ptr, size_t bytes, hipStream_t st);
 };
 void launch_zero(const ZeroList& z, hipStream_t st);      // launches nothing for an empty list
-void launch_zero_far_records(int64_t P, const GeomView& gv, GradRec* grad_rec, hipStream_t st);
+void launch_zero_far_records(int64_t P, const GeomView& gv, GradRec* grad_rec, float* grad_z, hipStream_t st);
 inline void ZeroList::add(void* ptr, size_t bytes, hipStream_t st) {
     if (!ptr || !bytes) return;
     if (full()) { launch_zero(*this, st); count = 0; }
@@ -366,15 +371,16 @@ void launch_scatter(int64_t P, const KSettings& ks, const GeomView& gv, const Bi
 void launch_tile_sort(const KSettings& ks, const GeomView& gv, const BinView& bv, int64_t max_tile_instances,
                       bool with_gm_index, hipStream_t st);
 void launch_blend_forward(const KSettings& ks, const GeomView& gv, const BinView& bv, const ImgView& iv,
-                          float* out_color, bool longest_first, bool safe, hipStream_t st);
+                          float* out_color, float* out_depth, float* out_alpha, bool longest_first, bool safe,
+                          hipStream_t st);
 void launch_blend_backward(const KSettings& ks, const GeomView& gv, const BinView& bv, const ImgView& iv,
-                           const float* dL_dcolor, GradRec* grad_rec, unsigned long long stamp, bool deep, bool flags,
-                           bool safe, hipStream_t st);
+                           const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha, GradRec* grad_rec,
+                           float* grad_z, unsigned long long stamp, bool deep, bool flags, bool safe, hipStream_t st);
 void launch_preprocess_backward(int64_t P, int M, const float* means3D, const float* scales,
                                 const float* rotations, const float* cov3D, const float* shs,
                                 const KSettings& ks, const int32_t* radii, const GeomView& gv,
-                                const BinView& bv, const GradRec* grad_rec, const unsigned long long* cut_key,
-                                unsigned long long stamp, bool deep, float* dL_dmeans3D,
+                                const BinView& bv, const GradRec* grad_rec, const float* grad_z,
+                                const unsigned long long* cut_key, unsigned long long stamp, bool deep, float* dL_dmeans3D,
                                 float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh, float* dL_dopacity,
                                 float* dL_dscales, float* dL_drotations, float* dL_dcov3D, hipStream_t st);
 

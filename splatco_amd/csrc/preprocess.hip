@@ -321,6 +321,10 @@ preprocess_kernel(int64_t P, int M, const float* __restrict__ means3D, const flo
 // ------------------------------------------------------------------ backward: reduce + chain
 // One thread per Gaussian.  Sums its per-instance gradient records in tile order (fixed order ->
 // bit-reproducible), then differentiates the projection (recomputed from the inputs).
+// AUX: the depth map took part in the loss.  The Gaussian's depth sums (grad_z, one float per record, same index, same
+// verdicts) add up to dL/dz of its view-space depth, which reaches the mean through the view matrix's third column --
+// z = ((V[2] x + V[6] y) + V[10] z) + V[14] in project().
+template <bool AUX>
 __global__ void __launch_bounds__(PRE_BLOCK, 1)
 preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
                            const float* __restrict__ scales, const float* __restrict__ rotations,
@@ -333,7 +337,8 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
                            float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dmeans2D,
                            float* __restrict__ dL_dcolors, float* __restrict__ dL_dsh,
                            float* __restrict__ dL_dopacity, float* __restrict__ dL_dscales,
-                           float* __restrict__ dL_drotations, float* __restrict__ dL_dcov3D) {
+                           float* __restrict__ dL_drotations, float* __restrict__ dL_dcov3D,
+                           const float* __restrict__ grad_z) {
     int64_t i = (int64_t)blockIdx.x * PRE_BLOCK + threadIdx.x;
     if (i >= P) return;
     float gm[3] = {0, 0, 0}, gm2[3] = {0, 0, 0}, gcol[3] = {0, 0, 0}, gop = 0, gs[3] = {0, 0, 0},
@@ -354,6 +359,7 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
         uint32_t n = tiles_touched[i];
         uint32_t off = point_offsets[i] - n;
         float sx = 0, sy = 0, sxx = 0, sxy = 0, syy = 0;  // moments of Y = opacity G dL/dalpha over the footprint
+        float sz = 0;                                     // AUX: dL/d(view-space depth)
         // this Gaussian's records are contiguous, in tile order (the row-major walk of its tile rect); four at a time so
         // that twelve record loads are in flight per thread -- the loop is otherwise one memory latency per record --
         // summed in order.  A tile's list entries behind every pixel's last contributor have NO record: the blend backward
@@ -362,6 +368,7 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
         // for the verdict before asking for the record would put two dependent round trips where there is one -- and the
         // bytes of missing records are dropped by a select, never used in arithmetic.
         const GradRec* gr = grad_rec + off;
+        const float* gz = AUX ? grad_z + off : nullptr;
         const unsigned long long mykey = ((unsigned long long)__float_as_uint(r2.y) << 32) | (uint32_t)i;
         const uint32_t rlo = __float_as_uint(r2.z), rhi = __float_as_uint(r2.w);
         const int gxt = (ks.W + TILE - 1) / TILE, rx0 = (int)(rlo & 0xffffu), rx1 = (int)(rhi & 0xffffu);
@@ -384,6 +391,7 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
             syy += ok ? q.b.x : 0.0f; gop += ok ? q.b.y : 0.0f; gcol[0] += ok ? q.b.z : 0.0f; gcol[1] += ok ? q.b.w : 0.0f;
             gcol[2] += ok ? q.c : 0.0f;
         };
+        auto addz = [&](float z, bool ok) { sz += ok ? z : 0.0f; };
         // The loads stay unconditional and four in flight per thread; the bytes of a record that was never written (dead
         // instance, or behind its tile's cut) are dropped by the select in add(), never used in arithmetic.  Measured at
         // cfg1 against the 0.0735 ms of summing every record: a predicated load per record 0.103 ms (the compiler closes
@@ -397,38 +405,59 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
         if (any_cut) {                      // wave-uniform: some tile of this call left entries without records
             for (; k + 4 <= nb; k += 4) {
                 GradRec q[4];
+                float z[4] = {0, 0, 0, 0};
                 unsigned long long ck[4];
                 bool live[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { ck[j] = cut_key[next_tile(live[j])]; q[j] = *SCR_PB_SRC(live[j], gr + k + j); }
+                for (int j = 0; j < 4; ++j) {
+                    ck[j] = cut_key[next_tile(live[j])];
+                    q[j] = *SCR_PB_SRC(live[j], gr + k + j);
+                    if (AUX) z[j] = gz[k + j];
+                }
 #pragma unroll
-                for (int j = 0; j < 4; ++j) add(q[j], live[j] && mykey < ck[j]);
+                for (int j = 0; j < 4; ++j) {
+                    add(q[j], live[j] && mykey < ck[j]);
+                    if (AUX) addz(z[j], live[j] && mykey < ck[j]);
+                }
             }
             for (; k < nb; ++k) {
                 bool live;
                 const unsigned long long ck = cut_key[next_tile(live)];
                 const GradRec q = *SCR_PB_SRC(live, gr + k);
                 add(q, live && mykey < ck);
+                if (AUX) addz(gz[k], live && mykey < ck);
             }
         } else {                            // every live instance has its record (the benchmark density): no look-ups
             for (; k + 4 <= nb; k += 4) {
                 GradRec q[4];
+                float z[4] = {0, 0, 0, 0};
                 bool live[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { next_tile(live[j]); q[j] = *SCR_PB_SRC(live[j], gr + k + j); }
+                for (int j = 0; j < 4; ++j) {
+                    next_tile(live[j]);
+                    q[j] = *SCR_PB_SRC(live[j], gr + k + j);
+                    if (AUX) z[j] = gz[k + j];
+                }
 #pragma unroll
-                for (int j = 0; j < 4; ++j) add(q[j], live[j]);
+                for (int j = 0; j < 4; ++j) {
+                    add(q[j], live[j]);
+                    if (AUX) addz(z[j], live[j]);
+                }
             }
             for (; k < nb; ++k) {
                 bool live;
                 next_tile(live);
                 add(*SCR_PB_SRC(live, gr + k), live);
+                if (AUX) addz(gz[k], live);
             }
         }
         // tiles 32.. of a large rect: their records were zeroed before the blend backward ran (zero_far_records_kernel; the
         // plan flag SCR_PLAN_LARGE_RECTS told the host) and are summed as they are -- no second evaluation of the blend
         // backward's "does this instance get a record" decision that would have to agree with it bit for bit
-        for (; k < n; ++k) add(gr[k], true);
+        for (; k < n; ++k) {
+            add(gr[k], true);
+            if (AUX) addz(gz[k], true);
+        }
         // the per-splat constants the blend kernel left out.  The moments are of Y = opacity * G * dL/dalpha, i.e.
         // dL/dG already: dG/dmean = -G Q d with Q = (-2A, -B, -2C), dG/dQ = -G/2 d d^T (Qxy counted once: factor 1);
         // dL/dopacity = sum G dL/dalpha = (sum Y) / opacity -- a non-zero sum means some pixel passed
@@ -497,6 +526,10 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
 #pragma unroll
         for (int cc = 0; cc < 3; ++cc)
             gm[cc] += g_hx * Pm[cc * 4 + 0] + g_hy * Pm[cc * 4 + 1] + g_hw * Pm[cc * 4 + 3];
+        if (AUX) {
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) gm[cc] += sz * V[cc * 4 + 2];
+        }
         // SH colour path
         if (shs && dL_dsh) {
             float d0[3] = {means3D[3 * i] - ks.campos[0], means3D[3 * i + 1] - ks.campos[1],
@@ -654,15 +687,16 @@ void launch_preprocess(int64_t P, int M, const float* means3D, const float* scal
 void launch_preprocess_backward(int64_t P, int M, const float* means3D, const float* scales,
                                 const float* rotations, const float* cov3D, const float* shs,
                                 const KSettings& ks, const int32_t* radii, const GeomView& gv,
-                                const BinView& bv, const GradRec* grad_rec, const unsigned long long* cut_key,
-                                unsigned long long stamp, bool deep, float* dL_dmeans3D,
+                                const BinView& bv, const GradRec* grad_rec, const float* grad_z,
+                                const unsigned long long* cut_key, unsigned long long stamp, bool deep, float* dL_dmeans3D,
                                 float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh, float* dL_dopacity,
                                 float* dL_dscales, float* dL_drotations, float* dL_dcov3D, hipStream_t st) {
     if (P <= 0) return;
-    preprocess_backward_kernel<<<nblk(P, PRE_BLOCK), PRE_BLOCK, 0, st>>>(
+    auto kernel = grad_z ? preprocess_backward_kernel<true> : preprocess_backward_kernel<false>;
+    kernel<<<nblk(P, PRE_BLOCK), PRE_BLOCK, 0, st>>>(
         P, M, means3D, scales, rotations, cov3D, shs, ks, radii, gv.tiles_touched, gv.point_offsets, gv.live_bits,
         deep ? gv.has_rec : nullptr, gv.clamped, gv.rec, grad_rec, cut_key, stamp, Grid(ks.H, ks.W).tiles, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dsh, dL_dopacity,
-        dL_dscales, dL_drotations, dL_dcov3D);
+        dL_dscales, dL_drotations, dL_dcov3D, grad_z);
 }
 
 // ---- gradient records 32.. of every Gaussian whose rect has more than 32 tiles: cleared before the blend backward writes
@@ -670,7 +704,8 @@ void launch_preprocess_backward(int64_t P, int M, const float* means3D, const fl
 // per store instruction.  Launched by every backward; leaves at once unless the forward raised SCR_PLAN_LARGE_RECTS.
 __global__ void __launch_bounds__(256) zero_far_records_kernel(int64_t P, const unsigned long long* __restrict__ total,
                                                                const uint32_t* __restrict__ tiles_touched,
-                                                               const uint32_t* __restrict__ point_offsets, uint32_t* __restrict__ rec_words) {
+                                                               const uint32_t* __restrict__ point_offsets, uint32_t* __restrict__ rec_words,
+                                                               float* __restrict__ grad_z) {
     // the forward's own verdict, where it left it on the device (geom_buf): nothing here depends on what the caller passed
     // back as plan_flags -- a stale or zero argument cannot leave uninitialised records for preprocess_backward to sum
     if ((total[3] & (unsigned long long)SCR_PLAN_LARGE_RECTS) == 0ull) return;
@@ -688,13 +723,15 @@ __global__ void __launch_bounds__(256) zero_far_records_kernel(int64_t P, const 
             const uint32_t n_s = (uint32_t)__shfl((int)n, src, WAVE), end_s = (uint32_t)__shfl((int)end, src, WAVE);
             const size_t w0 = (size_t)(end_s - n_s + 32u) * GRAD_F, w1 = (size_t)end_s * GRAD_F;      // dwords
             for (size_t w = w0 + lane; w < w1; w += WAVE) rec_words[w] = 0u;
+            if (grad_z)      // the depth sums of the same records (kernel-uniform)
+                for (size_t w = (size_t)(end_s - n_s + 32u) + lane; w < (size_t)end_s; w += WAVE) grad_z[w] = 0.0f;
         }
     }
 }
-void launch_zero_far_records(int64_t P, const GeomView& gv, GradRec* grad_rec, hipStream_t st) {
+void launch_zero_far_records(int64_t P, const GeomView& gv, GradRec* grad_rec, float* grad_z, hipStream_t st) {
     if (P <= 0) return;
     const int64_t want = (P + 255) / 256;
-    zero_far_records_kernel<<<(unsigned)(want < 2048 ? want : 2048), 256, 0, st>>>(P, gv.total, gv.tiles_touched, gv.point_offsets, (uint32_t*)grad_rec);
+    zero_far_records_kernel<<<(unsigned)(want < 2048 ? want : 2048), 256, 0, st>>>(P, gv.total, gv.tiles_touched, gv.point_offsets, (uint32_t*)grad_rec, grad_z);
 }
 
 // ---- ZeroList: blockIdx.y = buffer, blockIdx.x = 16 KB piece of it

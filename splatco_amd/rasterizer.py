@@ -6,6 +6,8 @@ Autograd contract: differentiable w.r.t. means3D, colors_precomp 
 scales + rotations | cov3D_precomp; `means2D` receives the NDC-space mean gradient although its
 value is unused (read back through .grad at scene/gaussian_model.py:779); radii is int32 and
 non-differentiable.  Saved state is per call, so the mv live graphs of train.py:171-240 coexist.
+With return_aux=True the same pass also returns the depth map sum_i w_i z_i and the accumulated opacity sum_i w_i
+(w_i = alpha_i T_i, z_i the view-space depth; background excluded, depth not normalised), both differentiable.
 PyTorch is used for device memory and streams only.
 """
 from typing import NamedTuple
@@ -69,7 +71,7 @@ class _CSettings:
 
 class RasterState:
     """Per-call saved buffers (opaque to Python) + what the debug getters need."""
-    __slots__ = ("P", "M", "I", "max_tile", "flags", "cs", "geom", "binning", "image", "radii")
+    __slots__ = ("P", "M", "I", "max_tile", "flags", "cs", "geom", "binning", "image", "radii", "aux")
 
     def debug(self, which):
         """Integer / float intermediates for the parity tests (SCR_DBG_* selectors)."""
@@ -96,8 +98,9 @@ SPECULATE = os.environ.get("SPLATCO_SPECULATIVE_BINNING", "1") != "0"
 _plan_guess = {}           # (device, H, W) -> (P, instances, largest tile) of the last forward at that resolution: sizes the speculative binning buffer
 
 
-def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, shs, colors_precomp):
-    """plan + run through the C-ABI.  Returns (color, radii, RasterState)."""
+def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, shs, colors_precomp, aux=False):
+    """plan + run through the C-ABI.  Returns (color, radii, RasterState).  aux: the blend also writes the depth and
+    opacity maps, two [H, W] tensors left in RasterState.aux for the caller to take."""
     dev = means3D.device
     P = means3D.shape[0]
     M = 0 if shs is None else shs.shape[1]
@@ -107,6 +110,12 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
     st.image = _C.scratch(_C.lib.scr_image_bytes(cs.H, cs.W), dev)
     radii = torch.empty(P, dtype=torch.int32, device=dev)      # every entry is written by preprocess_kernel
     color = torch.empty(3, cs.H, cs.W, dtype=torch.float32, device=dev)
+    st.aux = None
+    if aux:
+        st.aux = (torch.empty(cs.H, cs.W, dtype=torch.float32, device=dev), torch.empty(cs.H, cs.W, dtype=torch.float32, device=dev))
+    maps = () if st.aux is None else (st.aux[0].data_ptr(), st.aux[1].data_ptr())
+    plan_run, run = ((_C.lib.scr_forward_plan_run_aux, _C.lib.scr_forward_run_aux) if aux else
+                     (_C.lib.scr_forward_plan_run, _C.lib.scr_forward_run))
     plan = (C.c_int64 * 4)(0, 0, 0, 0)   # (tile instances, largest per-tile instance count, phase 2 already ran, plan flags)
     # The binning buffer's size is only known after the plan phase.  A guess from the previous call of this size (the
     # instance count of a training loop moves by a few per cent per step) lets both phases go out in ONE call: the GPU
@@ -119,10 +128,10 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
             scale = 1.06 * P / guess[0]
             cap = _C.lib.scr_binning_bytes(min(int(guess[1] * scale) + 4096, (1 << 32) - 2), max(int(guess[2] * 1.25), guess[2] + 64))
             spec = _C.scratch(cap, dev)
-        _C.check(_C.lib.scr_forward_plan_run(P, M, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D_precomp),
-                                             _C.ptr(opacities), _C.ptr(shs), _C.ptr(colors_precomp), cs.ref(),
-                                             st.geom.data_ptr(), _C.ptr(radii), plan, None if spec is None else spec.data_ptr(),
-                                             0 if spec is None else spec.numel(), st.image.data_ptr(), color.data_ptr(), _C.stream()))
+        _C.check(plan_run(P, M, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D_precomp),
+                          _C.ptr(opacities), _C.ptr(shs), _C.ptr(colors_precomp), cs.ref(),
+                          st.geom.data_ptr(), _C.ptr(radii), plan, None if spec is None else spec.data_ptr(),
+                          0 if spec is None else spec.numel(), st.image.data_ptr(), color.data_ptr(), *maps, _C.stream()))
         st.I, st.max_tile, st.flags = int(plan[0]), int(plan[1]), int(plan[3])
         _plan_guess[key] = (P, st.I, st.max_tile)
         if plan[2]:
@@ -130,8 +139,8 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
         else:
             del spec
             st.binning = _C.scratch(_C.lib.scr_binning_bytes(st.I, st.max_tile), dev)
-            _C.check(_C.lib.scr_forward_run(P, st.I, st.max_tile, st.flags, cs.ref(), st.geom.data_ptr(), st.binning.data_ptr(),
-                                            st.image.data_ptr(), color.data_ptr(), _C.stream()))
+            _C.check(run(P, st.I, st.max_tile, st.flags, cs.ref(), st.geom.data_ptr(), st.binning.data_ptr(),
+                         st.image.data_ptr(), color.data_ptr(), *maps, _C.stream()))
     st.radii = radii
     return color, radii, st
 
@@ -153,7 +162,7 @@ def _debug_dump(path, raster_settings, **tensors):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
+                raster_settings, return_aux=False):
         cs = _CSettings(raster_settings)
         # no zero tensors for outputs that received no gradient: autograd filled an int32 [P] "gradient" of radii with
         # zeros before every backward (88 M elements at configs[4]); backward() treats a missing dL/dcolor as zero
@@ -171,10 +180,13 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.state = None
             ctx.shapes = (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
             ctx.mark_non_differentiable(radii)
+            if return_aux:      # the background adds nothing to either map
+                zero = torch.zeros(cs.H, cs.W, dtype=torch.float32, device=means3D.device)
+                return color, radii, zero, torch.zeros_like(zero)
             return color, radii
         try:
             color, radii, st = rasterize_forward(cs, means3D, opacities, scales, rotations, cov3Ds_precomp, sh,
-                                                 colors_precomp)
+                                                 colors_precomp, **({"aux": True} if return_aux else {}))
         except RuntimeError as e:
             if raster_settings.debug:
                 raise RuntimeError(str(e) + _debug_dump("snapshot_fw.dump", raster_settings, means3D=means3D, sh=sh,
@@ -186,18 +198,26 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.save_for_backward(means3D, scales, rotations, cov3Ds_precomp, sh, colors_precomp, opacities)
         ctx.m2d_shape = tuple(means2D.shape)
         ctx.mark_non_differentiable(radii)
+        if return_aux:
+            (depth, alpha), st.aux = st.aux, None      # the state keeps what the backward needs, not the outputs
+            return color, radii, depth, alpha
         return color, radii
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii):
+    def backward(ctx, grad_out_color, _grad_radii, grad_out_depth=None, grad_out_alpha=None):
         st = ctx.state
         if st is None:
-            return tuple(None if t is None else torch.zeros_like(t) for t in ctx.shapes) + (None,)
-        if grad_out_color is None:      # the image took no part in the loss: every gradient is zero
-            return (None,) * 9
+            return tuple(None if t is None else torch.zeros_like(t) for t in ctx.shapes) + (None, None)
+        if grad_out_color is None and grad_out_depth is None and grad_out_alpha is None:
+            return (None,) * 10      # no output took part in the loss: every gradient is zero
         means3D, scales, rotations, cov3D, sh, colors, opacities = ctx.saved_tensors
         dev, P, cs = means3D.device, st.P, st.cs
-        g = _dev_f32(grad_out_color, "grad_out_color")
+        # with a gradient for one of the maps the blend backward carries two more channels (scr_backward_aux); without, this
+        # is the colour-only backward whichever forward ran.  A missing dL/dcolor is zeros then: the kernels always read it
+        aux = grad_out_depth is not None or grad_out_alpha is not None
+        g = (_dev_f32(grad_out_color, "grad_out_color") if grad_out_color is not None
+             else torch.zeros(3, cs.H, cs.W, dtype=torch.float32, device=dev))
+        g_depth, g_alpha = _dev_f32(grad_out_depth, "grad_out_depth"), _dev_f32(grad_out_alpha, "grad_out_alpha")
         # All per-Gaussian PARAMETER gradients are carved from ONE arena, adjacent (means2D, a per-view statistic, is a
         # tensor of its own): when the operator's inputs are leaves their .grad tensors
         # alias the arena, and multiview.allreduce_gradients reduces it in place without packing copies.
@@ -214,32 +234,37 @@ class _RasterizeGaussians(torch.autograd.Function):
         if g_sh is not None:
             g_sh = g_sh.view(P, st.M, 3)
         del arena, parts
-        scratch = _C.scratch(_C.lib.scr_backward_scratch_bytes(st.I), dev)
+        scratch = _C.scratch((_C.lib.scr_backward_scratch_bytes_aux if aux else _C.lib.scr_backward_scratch_bytes)(st.I), dev)
+        head = (P, st.M, st.I, st.flags, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D),
+                _C.ptr(sh), cs.ref(), st.radii.data_ptr(), st.geom.data_ptr(), st.binning.data_ptr(), st.image.data_ptr(),
+                g.data_ptr())
+        outs = (scratch.data_ptr(), g_means3D.data_ptr(), g_means2D.data_ptr(), _C.ptr(g_col), _C.ptr(g_sh),
+                g_op.data_ptr(), _C.ptr(g_scales), _C.ptr(g_rot), _C.ptr(g_cov), _C.stream())
         try:
           with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_backward(P, st.M, st.I, st.flags, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D),
-                                         _C.ptr(sh), cs.ref(), st.radii.data_ptr(), st.geom.data_ptr(),
-                                         st.binning.data_ptr(), st.image.data_ptr(), g.data_ptr(), scratch.data_ptr(),
-                                         g_means3D.data_ptr(), g_means2D.data_ptr(), _C.ptr(g_col), _C.ptr(g_sh),
-                                         g_op.data_ptr(), _C.ptr(g_scales), _C.ptr(g_rot), _C.ptr(g_cov), _C.stream()))
+            if aux:
+                _C.check(_C.lib.scr_backward_aux(*head, _C.ptr(g_depth), _C.ptr(g_alpha), *outs))
+            else:
+                _C.check(_C.lib.scr_backward(*head, *outs))
         except RuntimeError as e:
             if ctx.raster_settings.debug:
                 raise RuntimeError(str(e) + _debug_dump("snapshot_bw.dump", ctx.raster_settings, means3D=means3D, sh=sh,
                                                         colors_precomp=colors, opacities=opacities, scales=scales,
                                                         rotations=rotations, cov3Ds_precomp=cov3D, radii=st.radii,
-                                                        grad_out_color=g)) from e
+                                                        grad_out_color=g, grad_out_depth=g_depth,
+                                                        grad_out_alpha=g_alpha)) from e
             raise
         g_op = g_op.reshape(opacities.shape)
         if ctx.m2d_shape != (P, 3):
             g_means2D = g_means2D[:, :ctx.m2d_shape[1]].reshape(ctx.m2d_shape) if len(ctx.m2d_shape) == 2 else None
-        # order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings
-        return g_means3D, g_means2D, g_sh, g_col, g_op, g_scales, g_rot, g_cov, None
+        # order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, return_aux
+        return g_means3D, g_means2D, g_sh, g_col, g_op, g_scales, g_rot, g_cov, None, None
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
+                        raster_settings, return_aux=False):
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings)
+                                     cov3Ds_precomp, raster_settings, bool(return_aux))
 
 
 class GaussianRasterizer(nn.Module):
@@ -261,7 +286,9 @@ class GaussianRasterizer(nn.Module):
             return out.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, return_aux=False):
+        """(image, radii); with return_aux=True (image, radii, depth, alpha): the [H, W] maps sum_i w_i z_i and sum_i w_i over
+        the image's contributors (module docstring), differentiable like the image."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise ValueError('GaussianRasterizer: pass either shs or colors_precomp (one of them, not both, not neither)')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -271,7 +298,7 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians(
             means3D, means2D, empty if shs is None else shs, empty if colors_precomp is None else colors_precomp,
             opacities, empty if scales is None else scales, empty if rotations is None else rotations,
-            empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings)
+            empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, return_aux)
 
     def visible_filter(self, means3D, scales=None, rotations=None, cov3D_precomp=None):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \

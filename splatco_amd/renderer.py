@@ -183,8 +183,9 @@ def keep_grad(screenspace_points):
         screenspace_points.retain_grad()
 
 
-def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False):
-    """gaussian_renderer/__init__.py:118-188.  Background tensor must be on the GPU."""
+def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False, aux=False):
+    """gaussian_renderer/__init__.py:118-188.  Background tensor must be on the GPU.  aux=True: the result also holds
+    "depth" and "alpha", the rasterizer's [H, W] depth and accumulated-opacity maps (GaussianRasterizer.forward)."""
     is_training = pc.get_color_mlp.training
     with _C_stage("generate_neural_gaussians"):
         out = generate_neural_gaussians(viewpoint_camera, pc, visible_mask, is_training=is_training)
@@ -197,10 +198,13 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
         keep_grad(screenspace_points)
     rasterizer = GaussianRasterizer(raster_settings=_settings(viewpoint_camera, bg_color, scaling_modifier, pipe.debug))
     with _C_stage("rasterize"):
-        rendered_image, radii = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
-                                           opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None)
+        rendered_image, radii, *maps = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
+                                                  opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None,
+                                                  **({"return_aux": True} if aux else {}))
     res = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
            "radii": radii}
+    if aux:
+        res["depth"], res["alpha"] = maps
     if is_training:
         res.update({"selection_mask": out[6], "neural_opacity": out[5], "scaling": scaling})
     return res
