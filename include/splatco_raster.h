@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SCR_ABI_VERSION 30
+#define SCR_ABI_VERSION 31
 #define SCR_TILE 16 /* 16x16-pixel tiles: part of the result contract (tile rects, ranges, sort keys) */
 
 /* The 12 fields of GaussianRasterizationSettings, same order (gaussian_renderer/__init__.py:145-158).
@@ -67,6 +67,7 @@ size_t scr_binning_bytes(int64_t num_rendered, int64_t max_tile_instances);  /* 
 size_t scr_image_bytes(int32_t image_height, int32_t image_width);           /* final_T + n_contrib */
 size_t scr_backward_scratch_bytes(int64_t num_rendered);                     /* per-instance gradient records */
 size_t scr_backward_scratch_bytes_aux(int64_t num_rendered);                 /* the same + the per-instance depth sums of scr_backward_aux */
+size_t scr_backward_scratch_bytes_camera(int64_t num_rendered, int64_t P);   /* the same + one 128-byte row per 256 Gaussians (scr_backward_camera) */
 
 /* ---- visible_filter: radii_out[P] int32 (> 0 <=> visible).  Either (scales, rotations) or cov3D_precomp. */
 int scr_visible_filter(int64_t P, const float* means3D, const float* scales, const float* rotations,
@@ -166,6 +167,27 @@ int scr_backward_aux(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_fl
                      float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
                      float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
                      void* stream);
+
+/* ---- backward with the camera's gradients (ABI 31).  scr_backward_aux plus three outputs in front of `stream`:
+ *   dL_dviewmatrix[16], dL_dprojmatrix[16]  in the layout of scr_settings' matrices (row-vector convention, X[4 c + j]),
+ *   dL_dcampos[3]                           through the SH view direction; zeros with colors_precomp (shs NULL).
+ * The two matrices are independent inputs, as the forward reads them: viewmatrix through the view-space mean (columns 0..2:
+ * depth cull aside, the covariance projection's Jacobian and rotation, the depth map), projmatrix through the screen-space
+ * mean (columns 0, 1, 3).  Columns the forward never reads get exact zeros.  Culled Gaussians add nothing; the sort, the
+ * culls, the tile rects and the blend's thresholds are constants, and a clamped Jacobian (t.x / t.z or t.y / t.z outside
+ * 1.3 tan fov) passes nothing to that component of the view-space mean, as in dL_dmeans3D.  Each of the three may be NULL
+ * (not wanted); with all three NULL the call IS scr_backward_aux.  Every given output is written, with zeros when P == 0 or
+ * num_rendered == 0.  The per-Gaussian outputs are bit-identical to scr_backward_aux's.  Deterministic: the sums over the
+ * Gaussians are formed in a fixed order (per 256-Gaussian workgroup, then over the workgroups' rows by one more kernel),
+ * without floating-point atomics.  scratch: scr_backward_scratch_bytes_camera(num_rendered, P). */
+int scr_backward_camera(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_flags, const float* means3D, const float* scales,
+                        const float* rotations, const float* cov3D_precomp, const float* shs,
+                        const scr_settings* settings, const int32_t* radii, void* geom_buf,
+                        const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
+                        const float* dL_dalpha, void* scratch,
+                        float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
+                        float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                        float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream);
 
 /* ---- debug getters: copy the integer / float intermediates out of the opaque buffers (parity tests).
  * which: see SCR_DBG_*.  `out` is a device buffer of the stated element count. */

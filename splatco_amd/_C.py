@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SPLATCO_RASTER_LIB", os.path.join(_HERE, "csrc", "lib
 
 PLAN_NONFINITE_COLOUR, PLAN_LARGE_RECTS = 1, 2      # SCR_PLAN_*
 PROF_COUNT = 20
-ABI_VERSION = 30
+ABI_VERSION = 31
 FLIP_MAX_RADIUS = 16                                # SCR_FLIP_MAX_RADIUS
 
 (DBG_TILES_TOUCHED, DBG_POINT_OFFSETS, DBG_RANGES, DBG_POINT_LIST, DBG_N_CONTRIB, DBG_FINAL_T, DBG_SPLAT_RECORDS, DBG_QMASK,
@@ -62,6 +62,7 @@ SIGNATURES = [
     ("scr_image_bytes", sz, i32, i32),
     ("scr_backward_scratch_bytes", sz, i64),
     ("scr_backward_scratch_bytes_aux", sz, i64),
+    ("scr_backward_scratch_bytes_camera", sz, i64, i64),
     ("scr_visible_filter", i32, i64, vp, vp, vp, vp, P(Settings), vp, vp),
     ("scr_mark_visible", i32, i64, vp, vp, vp, vp),
     ("scr_forward_plan", i32, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp),
@@ -71,6 +72,7 @@ SIGNATURES = [
     ("scr_forward_plan_run_aux", i32, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp, sz, *[vp] * 5),
     ("scr_backward", i32, i64, i32, i64, i64, *[vp] * 5, P(Settings), *[vp] * 15),
     ("scr_backward_aux", i32, i64, i32, i64, i64, *[vp] * 5, P(Settings), *[vp] * 17),
+    ("scr_backward_camera", i32, i64, i32, i64, i64, *[vp] * 5, P(Settings), *[vp] * 20),
     ("scr_debug_force_deep_lists", i32, i32),
     ("scr_debug_get", i32, i32, i64, i64, i32, i32, *[vp] * 5),
     ("scr_tpa_scratch_bytes", sz, i32, i32, i32),

@@ -71,6 +71,30 @@ def make_camera(R, T, FoVx, FoVy, width, height, uid=0, trans=(0.0, 0.0, 0.0), s
                    full.contiguous(), center.contiguous(), uid, znear, zfar)
 
 
+def pose_tensors(cam, xi, dtype=torch.float32):
+    """(world_view_transform, full_proj_transform, camera_center) of `cam` moved by the twist xi = (omega, v) [6] in the
+    camera frame, W2C' = exp([[omega]x v; 0 0]) W2C, as differentiable functions of xi evaluated in `dtype` on xi's device
+    (scene/cameras.py:54-58: wvt = W2C'^T, full = wvt @ P^T, centre = inverse(wvt)[3, :3])."""
+    xi = xi.to(dtype)
+    w, v = xi[:3], xi[3:]
+    zero = xi.new_zeros(())
+    twist = torch.stack([torch.stack([zero, -w[2], w[1], v[0]]), torch.stack([w[2], zero, -w[0], v[1]]),
+                         torch.stack([-w[1], w[0], zero, v[2]]), xi.new_zeros(4)])
+    w2c = torch.linalg.matrix_exp(twist) @ cam.world_view_transform.to(xi.device, dtype).transpose(0, 1)
+    wvt = w2c.transpose(0, 1)
+    proj = get_projection_matrix(cam.znear, cam.zfar, cam.FoVx, cam.FoVy).to(xi.device, dtype).transpose(0, 1)
+    return wvt, wvt @ proj, torch.linalg.inv(wvt)[3, :3]
+
+
+def pose_delta_camera(cam, xi):
+    """`cam` with its pose moved by the twist xi = (omega, v) [6] (camera frame): a MiniCam whose three tensors are
+    differentiable float32 functions of xi on xi's device (pose_tensors).  At xi = 0 they are the camera's own (wvt
+    exactly, the other two to rounding).  For pose refinement: GaussianRasterizer / render() pass the gradient of the image
+    and the maps back through these tensors into xi.grad."""
+    wvt, full, center = pose_tensors(cam, xi)
+    return MiniCam(cam.image_width, cam.image_height, cam.FoVx, cam.FoVy, wvt, full, center, cam.uid, cam.znear, cam.zfar)
+
+
 def look_at_camera(eye, target, up, FoVx, width, height, uid=0):
     """Convenience: a camera at `eye` looking at `target` (COLMAP convention: +z forward,
     +y down), FoVy from the aspect ratio."""

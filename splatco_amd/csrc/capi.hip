@@ -185,6 +185,7 @@ size_t scr_binning_bytes(int64_t I, int64_t max_tile) { return bin_view(nullptr,
 size_t scr_image_bytes(int32_t H, int32_t W) { return img_view(nullptr, H, W).bytes; }
 size_t scr_backward_scratch_bytes(int64_t I) { return grad_rec_bytes(I); }
 size_t scr_backward_scratch_bytes_aux(int64_t I) { return grad_rec_bytes(I) + grad_z_bytes(I); }
+size_t scr_backward_scratch_bytes_camera(int64_t I, int64_t P) { return grad_rec_bytes(I) + grad_z_bytes(I) + camera_partials_bytes(P); }
 
 int scr_visible_filter(int64_t P, const float* means3D, const float* scales, const float* rotations,
                        const float* cov3D_precomp, const scr_settings* settings, int32_t* radii_out,
@@ -418,7 +419,7 @@ static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, co
                          const float* dL_dalpha, void* scratch,
                          float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
                          float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                         void* stream);
+                         float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream);
 
 int scr_backward(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
                  const float* rotations, const float* cov3D_precomp, const float* shs,
@@ -430,7 +431,7 @@ int scr_backward(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const floa
     SCR_MARK_FN;
     return backward_impl(P, M, I, plan_flags, means3D, scales, rotations, cov3D_precomp, shs, settings, radii, geom_buf, binning_buf,
                          image_buf, dL_dcolor, nullptr, nullptr, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dsh, dL_dopacity,
-                         dL_dscales, dL_drotations, dL_dcov3D, stream);
+                         dL_dscales, dL_drotations, dL_dcov3D, nullptr, nullptr, nullptr, stream);
 }
 
 int scr_backward_aux(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
@@ -444,10 +445,25 @@ int scr_backward_aux(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const 
     SCR_MARK_FN;
     return backward_impl(P, M, I, plan_flags, means3D, scales, rotations, cov3D_precomp, shs, settings, radii, geom_buf, binning_buf,
                          image_buf, dL_dcolor, dL_ddepth, dL_dalpha, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dsh, dL_dopacity,
-                         dL_dscales, dL_drotations, dL_dcov3D, stream);
+                         dL_dscales, dL_drotations, dL_dcov3D, nullptr, nullptr, nullptr, stream);
 }
 
-// dL_ddepth / dL_dalpha both NULL: the colour-only kernels, whichever entry point was called
+int scr_backward_camera(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
+                        const float* rotations, const float* cov3D_precomp, const float* shs,
+                        const scr_settings* settings, const int32_t* radii, void* geom_buf,
+                        const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
+                        const float* dL_dalpha, void* scratch,
+                        float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
+                        float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                        float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream) {
+    SCR_MARK_FN;
+    return backward_impl(P, M, I, plan_flags, means3D, scales, rotations, cov3D_precomp, shs, settings, radii, geom_buf, binning_buf,
+                         image_buf, dL_dcolor, dL_ddepth, dL_dalpha, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dsh, dL_dopacity,
+                         dL_dscales, dL_drotations, dL_dcov3D, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, stream);
+}
+
+// dL_ddepth / dL_dalpha both NULL: the colour-only kernels, whichever entry point was called; the three camera outputs all
+// NULL: the kernels without the camera sums
 static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
                          const float* rotations, const float* cov3D_precomp, const float* shs,
                          const scr_settings* settings, const int32_t* radii, void* geom_buf,
@@ -455,9 +471,16 @@ static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, co
                          const float* dL_dalpha, void* scratch,
                          float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
                          float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                         void* stream) {
+                         float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream) {
     if (check_settings(settings)) return 1;
-    if (P == 0) return 0;
+    if (P < 0) return fail("P < 0");
+    const bool camera = dL_dviewmatrix || dL_dprojmatrix || dL_dcampos;
+    if (P == 0) {      // no Gaussian, no kernel: the camera's gradients are zeros, not what the caller's memory held
+        if (dL_dviewmatrix) HIP_TRY(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float), (hipStream_t)stream));
+        if (dL_dprojmatrix) HIP_TRY(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float), (hipStream_t)stream));
+        if (dL_dcampos) HIP_TRY(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float), (hipStream_t)stream));
+        return 0;
+    }
     if (plan_flags & ~(int64_t)(SCR_PLAN_NONFINITE_COLOUR | SCR_PLAN_LARGE_RECTS)) return fail("plan_flags %lld: not a value scr_forward_plan returned", (long long)plan_flags);
     if (!geom_buf || !binning_buf || !image_buf || !dL_dcolor || !scratch) return fail("NULL buffer");
     if (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity) return fail("NULL argument");
@@ -474,6 +497,8 @@ static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, co
     const unsigned long long stamp = ++stamp_counter;
     // the depth sums lie behind the records (scr_backward_scratch_bytes_aux)
     float* const grad_z = (I > 0 && (dL_ddepth || dL_dalpha)) ? (float*)((char*)scratch + grad_rec_bytes(I)) : nullptr;
+    // the camera sums' rows lie behind both (scr_backward_scratch_bytes_camera reserves the depth sums whether used or not)
+    float* const cam_partials = camera ? (float*)((char*)scratch + grad_rec_bytes(I) + grad_z_bytes(I)) : nullptr;
     if (settings->debug) {      // the flags the caller carried from scr_forward_plan against the ones the forward left in geom_buf
         unsigned long long dev_flags = 0;
         HIP_TRY(hipMemcpyAsync(&dev_flags, gv.total + 3, 8, hipMemcpyDeviceToHost, st));
@@ -496,8 +521,12 @@ static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, co
       launch_preprocess_backward(P, M, means3D, scales, rotations, cov3D_precomp, shs, ks, radii, gv, bv,
                                  (const GradRec*)scratch, grad_z, iv.cut_key, stamp, record_flags(I, Grid(ks.H, ks.W).tiles), dL_dmeans3D, dL_dmeans2D, shs ? nullptr : dL_dcolors,
                                  shs ? dL_dsh : nullptr, dL_dopacity, cov3D_precomp ? nullptr : dL_dscales,
-                                 cov3D_precomp ? nullptr : dL_drotations, cov3D_precomp ? dL_dcov3D : nullptr, st); }
+                                 cov3D_precomp ? nullptr : dL_drotations, cov3D_precomp ? dL_dcov3D : nullptr, cam_partials, st); }
     CHECK_LAUNCH("preprocess_backward_kernel", settings->debug, st);
+    if (camera) {      // I == 0 included: every row is zero then, and so is every output
+        launch_camera_grad_finish(P, cam_partials, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, st);
+        CHECK_LAUNCH("camera_grad_finish_kernel", settings->debug, st);
+    }
     return 0;
 }
 

@@ -382,7 +382,12 @@ void launch_preprocess_backward(int64_t P, int M, const float* means3D, const fl
                                 const BinView& bv, const GradRec* grad_rec, const float* grad_z,
                                 const unsigned long long* cut_key, unsigned long long stamp, bool deep, float* dL_dmeans3D,
                                 float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh, float* dL_dopacity,
-                                float* dL_dscales, float* dL_drotations, float* dL_dcov3D, hipStream_t st);
+                                float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* cam_partials,
+                                hipStream_t st);
+// camera gradients (preprocess.hip): one 32-float row per preprocess-backward workgroup, summed by one more small kernel
+size_t camera_partials_bytes(int64_t P);
+void launch_camera_grad_finish(int64_t P, const float* cam_partials, float* dL_dview, float* dL_dproj, float* dL_dcampos,
+                               hipStream_t st);
 
 void launch_expand_count(int64_t n, const float* neural_opacity, uint32_t* wg_count, unsigned long long* total,
                          unsigned long long* mailbox, unsigned long long seq, hipStream_t st);

@@ -319,12 +319,40 @@ preprocess_kernel(int64_t P, int M, const float* __restrict__ means3D, const flo
 }
 
 // ------------------------------------------------------------------ backward: reduce + chain
+// Sum of each of the CAM_VALUES per-thread values over the PRE_BLOCK threads of the workgroup, in a fixed order: the lanes of
+// a wave by a shuffle tree, then the waves in ascending order (binning.hip's wave_sum scheme).  Every thread must call it.
+constexpr int CAM_VALUES = 27, CAM_ROW = 32;
+__device__ __forceinline__ void cam_workgroup_sum(const float* v, float* __restrict__ row) {
+    __shared__ float wave_part[PRE_BLOCK / WAVE][CAM_ROW];
+#pragma unroll
+    for (int k = 0; k < CAM_VALUES; ++k) {
+        float s = v[k];
+#pragma unroll
+        for (int d = WAVE / 2; d > 0; d >>= 1) s += __shfl_down(s, d, WAVE);
+        if ((threadIdx.x & (WAVE - 1)) == 0) wave_part[threadIdx.x / WAVE][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < CAM_ROW) {
+        float tot = 0.0f;
+        if (threadIdx.x < CAM_VALUES) {
+#pragma unroll
+            for (int w = 0; w < PRE_BLOCK / WAVE; ++w) tot += wave_part[w][threadIdx.x];
+        }
+        row[threadIdx.x] = tot;
+    }
+}
+
 // One thread per Gaussian.  Sums its per-instance gradient records in tile order (fixed order ->
 // bit-reproducible), then differentiates the projection (recomputed from the inputs).
 // AUX: the depth map took part in the loss.  The Gaussian's depth sums (grad_z, one float per record, same index, same
 // verdicts) add up to dL/dz of its view-space depth, which reaches the mean through the view matrix's third column --
 // z = ((V[2] x + V[6] y) + V[10] z) + V[14] in project().
-template <bool AUX>
+// POSE: the camera takes part in the loss.  Each thread also forms its Gaussian's 27 contributions to dL/dviewmatrix (12:
+// rows 0..3 x columns 0..2), dL/dprojmatrix (12: rows 0..3 x columns 0, 1, 3) and dL/dcampos (3) from the factors of the chain
+// below; the workgroup adds them up in a fixed order (lanes of a wave by shuffles, the four waves through LDS) and leaves one
+// row of CAM_ROW floats in cam_partials[blockIdx.x], which camera_grad_finish_kernel sums.  EVERY thread of the workgroup
+// takes part: a thread past the end works on the last Gaussian's (valid) addresses, counts as invisible and stores nothing.
+template <bool AUX, bool POSE>
 __global__ void __launch_bounds__(PRE_BLOCK, 1)
 preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
                            const float* __restrict__ scales, const float* __restrict__ rotations,
@@ -338,12 +366,18 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
                            float* __restrict__ dL_dcolors, float* __restrict__ dL_dsh,
                            float* __restrict__ dL_dopacity, float* __restrict__ dL_dscales,
                            float* __restrict__ dL_drotations, float* __restrict__ dL_dcov3D,
-                           const float* __restrict__ grad_z) {
+                           const float* __restrict__ grad_z, float* __restrict__ cam_partials) {
     int64_t i = (int64_t)blockIdx.x * PRE_BLOCK + threadIdx.x;
-    if (i >= P) return;
+    bool inb = true;
+    if (POSE) {
+        inb = i < P;
+        if (!inb) i = P - 1;
+    } else if (i >= P) return;
+    float cg[POSE ? CAM_VALUES : 1] = {};
     float gm[3] = {0, 0, 0}, gm2[3] = {0, 0, 0}, gcol[3] = {0, 0, 0}, gop = 0, gs[3] = {0, 0, 0},
           gq[4] = {0, 0, 0, 0}, g6[6] = {0, 0, 0, 0, 0, 0};
     bool vis = radii[i] > 0;
+    if (POSE && !inb) vis = false;
     // deep lists (kernel-uniform pointer): a Gaussian without a single gradient record -- behind every pixel's last contributor
     // in all of its tiles, most of them at 20 M anchors -- has zero gradients: it is treated like an invisible one (its
     // inputs are not even read; the chain below would multiply them by sums that are all zero)
@@ -530,6 +564,23 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
 #pragma unroll
             for (int cc = 0; cc < 3; ++cc) gm[cc] += sz * V[cc * 4 + 2];
         }
+        if (POSE) {
+            // t_j = p . V[.][j] + V[3][j], T = J W with W[j][c] = V[c][j], hom_j = p . M[.][j] + M[3][j]
+            const float pm[3] = {means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]};
+            const float J00 = fx / tz, J02 = -(fx * tx) / tz2, J11 = fy / tz, J12 = -(fy * ty) / tz2;
+            const float gv[3] = {g_t[0], g_t[1], AUX ? g_t[2] + sz : g_t[2]};
+            const float gh[3] = {g_hx, g_hy, g_hw};
+#pragma unroll
+            for (int cc = 0; cc < 3; ++cc) {
+                cg[3 * cc + 0] = pm[cc] * gv[0] + gT[0][cc] * J00;
+                cg[3 * cc + 1] = pm[cc] * gv[1] + gT[1][cc] * J11;
+                cg[3 * cc + 2] = pm[cc] * gv[2] + (gT[0][cc] * J02 + gT[1][cc] * J12);
+                cg[9 + cc] = gv[cc];
+#pragma unroll
+                for (int j = 0; j < 3; ++j) cg[12 + 3 * cc + j] = pm[cc] * gh[j];
+                cg[21 + cc] = gh[cc];
+            }
+        }
         // SH colour path
         if (shs && dL_dsh) {
             float d0[3] = {means3D[3 * i] - ks.campos[0], means3D[3 * i + 1] - ks.campos[1],
@@ -595,6 +646,10 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
             float dotv = d0[0] * gdir[0] + d0[1] * gdir[1] + d0[2] * gdir[2];
 #pragma unroll
             for (int cc = 0; cc < 3; ++cc) gm[cc] += (n2 * gdir[cc] - d0[cc] * dotv) * inv3;
+            if (POSE) {      // the direction is mean - campos: the camera centre gets the opposite of the mean's share
+#pragma unroll
+                for (int cc = 0; cc < 3; ++cc) cg[24 + cc] = -((n2 * gdir[cc] - d0[cc] * dotv) * inv3);
+            }
         }
         // Sigma3D -> scale, quaternion
         if (!cov3D) {
@@ -633,24 +688,68 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
             gq[3] = 2.0f * (-2.0f * z * gR[0][0] - r * gR[0][1] + x * gR[0][2] + r * gR[1][0] -
                             2.0f * z * gR[1][1] + y * gR[1][2] + x * gR[2][0] + y * gR[2][1]);
         }
-    } else if (shs && dL_dsh) {
+    } else if (shs && dL_dsh && (!POSE || inb)) {
         for (int k = 0; k < 3 * M; ++k) dL_dsh[(size_t)i * 3 * M + k] = 0.0f;
     }
+    if (!POSE || inb) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        dL_dmeans3D[3 * i + k] = gm[k];
-        dL_dmeans2D[3 * i + k] = gm2[k];
-        if (dL_dcolors) dL_dcolors[3 * i + k] = gcol[k];
-        if (dL_dscales) dL_dscales[3 * i + k] = gs[k];
+        for (int k = 0; k < 3; ++k) {
+            dL_dmeans3D[3 * i + k] = gm[k];
+            dL_dmeans2D[3 * i + k] = gm2[k];
+            if (dL_dcolors) dL_dcolors[3 * i + k] = gcol[k];
+            if (dL_dscales) dL_dscales[3 * i + k] = gs[k];
+        }
+        dL_dopacity[i] = gop;
+        if (dL_drotations) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dL_drotations[4 * i + k] = gq[k];
+        }
+        if (dL_dcov3D) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) dL_dcov3D[6 * i + k] = g6[k];
+        }
     }
-    dL_dopacity[i] = gop;
-    if (dL_drotations) {
+    if constexpr (POSE) cam_workgroup_sum(cg, cam_partials + (size_t)blockIdx.x * CAM_ROW);
+}
+
+// ---- dL/dviewmatrix [16], dL/dprojmatrix [16], dL/dcampos [3] from the workgroups' rows (preprocess_backward_kernel<., true>).
+// One workgroup: thread t adds column t % 32 of the rows r = t / 32 (mod 32) in ascending order, in double; the 32 slices are
+// added in ascending order by the threads that write.  Fixed order, no atomics: the same bits every time.  Columns the
+// forward never reads (viewmatrix[.][3], projmatrix[.][2]) are written as zeros; each output may be NULL.
+constexpr int CAM_FINISH_THREADS = 1024;
+__global__ void __launch_bounds__(CAM_FINISH_THREADS)
+camera_grad_finish_kernel(int64_t rows, const float* __restrict__ partials, float* __restrict__ dL_dview,
+                          float* __restrict__ dL_dproj, float* __restrict__ dL_dcampos) {
+    constexpr int SLICES = CAM_FINISH_THREADS / CAM_ROW;
+    __shared__ double part[SLICES][CAM_ROW];
+    const int col = threadIdx.x % CAM_ROW, slice = threadIdx.x / CAM_ROW;
+    double acc = 0.0;
+    int64_t r = slice;
+    for (; r + 7 * SLICES < rows; r += 8 * SLICES) {      // eight loads in flight: the walk is one latency per round
+        float x[8];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) dL_drotations[4 * i + k] = gq[k];
+        for (int j = 0; j < 8; ++j) x[j] = partials[(r + j * SLICES) * CAM_ROW + col];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc += (double)x[j];
     }
-    if (dL_dcov3D) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) dL_dcov3D[6 * i + k] = g6[k];
+    for (; r < rows; r += SLICES) acc += (double)partials[r * CAM_ROW + col];
+    part[slice][col] = acc;
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t >= 35) return;
+    auto total = [&](int k) {
+        double s = 0.0;
+        for (int w = 0; w < SLICES; ++w) s += part[w][k];
+        return (float)s;
+    };
+    if (t < 16) {               // viewmatrix[c][j]: value 3 c + j, column 3 unread
+        const int c = t >> 2, j = t & 3;
+        if (dL_dview) dL_dview[t] = j < 3 ? total(3 * c + j) : 0.0f;
+    } else if (t < 32) {        // projmatrix[c][j]: value 12 + 3 c + (0, 1, -, 2)[j], column 2 unread
+        const int c = (t - 16) >> 2, j = t & 3;
+        if (dL_dproj) dL_dproj[t - 16] = j != 2 ? total(12 + 3 * c + (j == 3 ? 2 : j)) : 0.0f;
+    } else if (dL_dcampos) {
+        dL_dcampos[t - 32] = total(24 + (t - 32));
     }
 }
 
@@ -690,13 +789,23 @@ void launch_preprocess_backward(int64_t P, int M, const float* means3D, const fl
                                 const BinView& bv, const GradRec* grad_rec, const float* grad_z,
                                 const unsigned long long* cut_key, unsigned long long stamp, bool deep, float* dL_dmeans3D,
                                 float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh, float* dL_dopacity,
-                                float* dL_dscales, float* dL_drotations, float* dL_dcov3D, hipStream_t st) {
+                                float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* cam_partials,
+                                hipStream_t st) {
     if (P <= 0) return;
-    auto kernel = grad_z ? preprocess_backward_kernel<true> : preprocess_backward_kernel<false>;
+    auto kernel = cam_partials ? (grad_z ? preprocess_backward_kernel<true, true> : preprocess_backward_kernel<false, true>)
+                               : (grad_z ? preprocess_backward_kernel<true, false> : preprocess_backward_kernel<false, false>);
     kernel<<<nblk(P, PRE_BLOCK), PRE_BLOCK, 0, st>>>(
         P, M, means3D, scales, rotations, cov3D, shs, ks, radii, gv.tiles_touched, gv.point_offsets, gv.live_bits,
         deep ? gv.has_rec : nullptr, gv.clamped, gv.rec, grad_rec, cut_key, stamp, Grid(ks.H, ks.W).tiles, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dsh, dL_dopacity,
-        dL_dscales, dL_drotations, dL_dcov3D, grad_z);
+        dL_dscales, dL_drotations, dL_dcov3D, grad_z, cam_partials);
+}
+
+size_t camera_partials_bytes(int64_t P) { return align_up((size_t)(P > 0 ? nblk(P, PRE_BLOCK) : 1) * CAM_ROW * sizeof(float)); }
+
+void launch_camera_grad_finish(int64_t P, const float* cam_partials, float* dL_dview, float* dL_dproj, float* dL_dcampos,
+                               hipStream_t st) {
+    camera_grad_finish_kernel<<<1, CAM_FINISH_THREADS, 0, st>>>(P > 0 ? (int64_t)nblk(P, PRE_BLOCK) : 0, cam_partials, dL_dview,
+                                                                 dL_dproj, dL_dcampos);
 }
 
 // ---- gradient records 32.. of every Gaussian whose rect has more than 32 tiles: cleared before the blend backward writes

@@ -8,6 +8,12 @@ value is unused (read back through .grad at scene/gaussian_model.py:779); radii 
 non-differentiable.  Saved state is per call, so the mv live graphs of train.py:171-240 coexist.
 With return_aux=True the same pass also returns the depth map sum_i w_i z_i and the accumulated opacity sum_i w_i
 (w_i = alpha_i T_i, z_i the view-space depth; background excluded, depth not normalised), both differentiable.
+The camera is differentiable too: when raster_settings.viewmatrix, .projmatrix or .campos requires grad (and gradient mode is
+on) the backward also returns dL/dviewmatrix, dL/dprojmatrix [4, 4] and dL/dcampos [3] (scr_backward_camera), each in the
+shape of the tensor given and only for those that require grad.  The two matrices are independent inputs, as the kernels
+read them: a full projection built in torch from the view matrix gets the composed gradient from autograd.  Columns the
+forward never reads (viewmatrix[:, 3], projmatrix[:, 2]) get exact zeros, campos gets zeros with colors_precomp.  tanfovx /
+tanfovy stay Python floats.  Without such a tensor nothing changes: the same entry points, kernels and bits.
 PyTorch is used for device memory and streams only.
 """
 from typing import NamedTuple
@@ -162,7 +168,9 @@ def _debug_dump(path, raster_settings, **tensors):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, return_aux=False):
+                raster_settings, return_aux=False, *camera):
+        # camera: () or (viewmatrix, projmatrix, campos) -- the tensors of raster_settings once more, as inputs autograd sees
+        ctx.camera = [(tuple(t.shape), t.dtype) for t in camera]
         cs = _CSettings(raster_settings)
         # no zero tensors for outputs that received no gradient: autograd filled an int32 [P] "gradient" of radii with
         # zeros before every backward (88 M elements at configs[4]); backward() treats a missing dL/dcolor as zero
@@ -206,10 +214,14 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out_color, _grad_radii, grad_out_depth=None, grad_out_alpha=None):
         st = ctx.state
+        # the camera tensors' gradients: asked of the kernel only where the tensor requires grad, None for the rest
+        want_cam = [bool(w) for w in ctx.needs_input_grad[10:]]
         if st is None:
-            return tuple(None if t is None else torch.zeros_like(t) for t in ctx.shapes) + (None, None)
+            zeros_cam = tuple(torch.zeros(shape, dtype=dt, device=ctx.shapes[0].device) if w else None
+                              for (shape, dt), w in zip(ctx.camera, want_cam))
+            return tuple(None if t is None else torch.zeros_like(t) for t in ctx.shapes) + (None, None) + zeros_cam
         if grad_out_color is None and grad_out_depth is None and grad_out_alpha is None:
-            return (None,) * 10      # no output took part in the loss: every gradient is zero
+            return (None,) * (10 + len(ctx.camera))      # no output took part in the loss: every gradient is zero
         means3D, scales, rotations, cov3D, sh, colors, opacities = ctx.saved_tensors
         dev, P, cs = means3D.device, st.P, st.cs
         # with a gradient for one of the maps the blend backward carries two more channels (scr_backward_aux); without, this
@@ -234,15 +246,23 @@ class _RasterizeGaussians(torch.autograd.Function):
         if g_sh is not None:
             g_sh = g_sh.view(P, st.M, 3)
         del arena, parts
-        scratch = _C.scratch((_C.lib.scr_backward_scratch_bytes_aux if aux else _C.lib.scr_backward_scratch_bytes)(st.I), dev)
+        g_cam = ()
+        if any(want_cam):      # [16 | 16 | 3]: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos, row-major like the settings' tensors
+            cam_buf = torch.empty(35, dtype=torch.float32, device=dev)
+            g_cam = tuple(cam_buf[lo:hi] if w else None for (lo, hi), w in zip(((0, 16), (16, 32), (32, 35)), want_cam))
+            scratch = _C.scratch(_C.lib.scr_backward_scratch_bytes_camera(st.I, P), dev)
+        else:
+            scratch = _C.scratch((_C.lib.scr_backward_scratch_bytes_aux if aux else _C.lib.scr_backward_scratch_bytes)(st.I), dev)
         head = (P, st.M, st.I, st.flags, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D),
                 _C.ptr(sh), cs.ref(), st.radii.data_ptr(), st.geom.data_ptr(), st.binning.data_ptr(), st.image.data_ptr(),
                 g.data_ptr())
         outs = (scratch.data_ptr(), g_means3D.data_ptr(), g_means2D.data_ptr(), _C.ptr(g_col), _C.ptr(g_sh),
-                g_op.data_ptr(), _C.ptr(g_scales), _C.ptr(g_rot), _C.ptr(g_cov), _C.stream())
+                g_op.data_ptr(), _C.ptr(g_scales), _C.ptr(g_rot), _C.ptr(g_cov), *(_C.ptr(t) for t in g_cam), _C.stream())
         try:
           with torch.cuda.device(dev):
-            if aux:
+            if g_cam:
+                _C.check(_C.lib.scr_backward_camera(*head, _C.ptr(g_depth), _C.ptr(g_alpha), *outs))
+            elif aux:
                 _C.check(_C.lib.scr_backward_aux(*head, _C.ptr(g_depth), _C.ptr(g_alpha), *outs))
             else:
                 _C.check(_C.lib.scr_backward(*head, *outs))
@@ -257,14 +277,21 @@ class _RasterizeGaussians(torch.autograd.Function):
         g_op = g_op.reshape(opacities.shape)
         if ctx.m2d_shape != (P, 3):
             g_means2D = g_means2D[:, :ctx.m2d_shape[1]].reshape(ctx.m2d_shape) if len(ctx.m2d_shape) == 2 else None
-        # order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, return_aux
-        return g_means3D, g_means2D, g_sh, g_col, g_op, g_scales, g_rot, g_cov, None, None
+        # the camera gradients in the shape (and dtype) of the tensors given: autograd needs no more of a strided view
+        g_cam = tuple(None if t is None else t.reshape(shape).to(dt) for t, (shape, dt) in zip(g_cam, ctx.camera))
+        if len(g_cam) < len(ctx.camera):
+            g_cam = (None,) * len(ctx.camera)
+        # order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, return_aux, camera
+        return (g_means3D, g_means2D, g_sh, g_col, g_op, g_scales, g_rot, g_cov, None, None) + g_cam
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, return_aux=False):
+    camera = (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
+    if not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in camera)):
+        camera = ()      # the default: the camera is a constant, nothing about the call changes
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, bool(return_aux))
+                                     cov3Ds_precomp, raster_settings, bool(return_aux), *camera)
 
 
 class GaussianRasterizer(nn.Module):

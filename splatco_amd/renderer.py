@@ -40,7 +40,11 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
     The mask / compaction / post-processing block (:68-111) is the single HIP op of splatco_amd.expand
     (device tensors only, no CPU path).  expand: test hook -- a callable with expand_compact's signature
     (tests/torch_restatements.py holds the torch op chain the kernel is checked against).  fused_heads=False keeps
-    the MLP heads as rocBLAS GEMMs (the checker of csrc/mlp_heads.hip)."""
+    the MLP heads as rocBLAS GEMMs (the checker of csrc/mlp_heads.hip).
+    The camera centre is a CONSTANT here: the anchors' view direction ob_view is formed from camera_center.detach(), in the
+    fused heads kernel and in the torch chain alike.  A camera that requires grad (cameras.pose_delta_camera) gets its
+    gradient through the rasterizer operator only; for every other camera nothing changes."""
+    campos = viewpoint_camera.camera_center.detach()
     if visible_mask is None:
         visible_mask = torch.ones(pc.get_anchor.shape[0], dtype=torch.bool, device=pc.get_anchor.device)
     # `t[visible_mask]` four times (:23-29) = four mask->index conversions (each a host sync) and
@@ -89,7 +93,7 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
     if use_fused and not isinstance(pc.feat_planes, _parts_capable()):
         # someone else's feature planes (e.g. the reference's own GaussianModel): geo_fea arrives concatenated
         geo_fea = pc.feat_planes.inference(anchor, g_fea, 0)
-        neural_opacity, color, scale_rot = _mh.mlp_heads(pc, feat, anchor, viewpoint_camera.camera_center, geo_fea)
+        neural_opacity, color, scale_rot = _mh.mlp_heads(pc, feat, anchor, campos, geo_fea)
         ob_view = None
     elif use_fused:
         # the three heads as ONE fp32-MFMA kernel per direction (csrc/mlp_heads.hip): x = cat(feat, ob_view, geo_fea)
@@ -99,11 +103,11 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
             geo_a, geo_b = pc.feat_planes.inference(anchor, g_fea, 0, parts=True, presampled=presampled)
         else:
             geo_a, geo_b = pc.feat_planes.inference(anchor, g_fea, 0, parts=True)
-        neural_opacity, color, scale_rot = _mh.mlp_heads(pc, feat, anchor, viewpoint_camera.camera_center, geo_a, geo_b)
+        neural_opacity, color, scale_rot = _mh.mlp_heads(pc, feat, anchor, campos, geo_a, geo_b)
         ob_view = None
     else:
         geo_fea = pc.feat_planes.inference(anchor, g_fea, 0)
-        ob_view = anchor - viewpoint_camera.camera_center
+        ob_view = anchor - campos
         ob_dist = ob_view.norm(dim=1, keepdim=True)
         ob_view = ob_view / ob_dist
     if ob_view is None:
@@ -185,7 +189,10 @@ def keep_grad(screenspace_points):
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False, aux=False):
     """gaussian_renderer/__init__.py:118-188.  Background tensor must be on the GPU.  aux=True: the result also holds
-    "depth" and "alpha", the rasterizer's [H, W] depth and accumulated-opacity maps (GaussianRasterizer.forward)."""
+    "depth" and "alpha", the rasterizer's [H, W] depth and accumulated-opacity maps (GaussianRasterizer.forward).
+    A camera whose world_view_transform / full_proj_transform / camera_center require grad (cameras.pose_delta_camera)
+    receives the gradient of the image and the maps through the rasterizer operator: projection, covariance projection and
+    depth.  The camera's path through the MLP heads (the anchors' view direction) is not differentiated."""
     is_training = pc.get_color_mlp.training
     with _C_stage("generate_neural_gaussians"):
         out = generate_neural_gaussians(viewpoint_camera, pc, visible_mask, is_training=is_training)
