@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SCR_ABI_VERSION 31
+#define SCR_ABI_VERSION 32
 #define SCR_TILE 16 /* 16x16-pixel tiles: part of the result contract (tile rects, ranges, sort keys) */
 
 /* The 12 fields of GaussianRasterizationSettings, same order (gaussian_renderer/__init__.py:145-158).
@@ -91,6 +91,8 @@ int scr_mark_visible(int64_t P, const float* means3D, const float* viewmatrix, u
  * contribute to; the fast blend kernels carry non-contributing splats with alpha 0 (0 * NaN would spread), so calls
  * with this bit run the kernels' select-based instantiations and give the reference's result, NaN for NaN. */
 enum { SCR_PLAN_NONFINITE_COLOUR = 1,
+       SCR_PLAN_ANTIALIASED = 4,    /* the forward ran in the antialiased mode (scr_forward_plan_mode): the splat records carry
+                                     * opacity * h.  The backward's kernels take THIS bit from geom_buf too (see below). */
        SCR_PLAN_LARGE_RECTS = 2 };  /* some Gaussian's tile rect has more than 32 tiles: scr_backward clears the gradient
                                      * records of its further tiles before the blend backward fills in the ones it writes.
                                      * The backward takes THIS bit from geom_buf (where the forward left it), not from its
@@ -103,8 +105,26 @@ int scr_forward_plan(int64_t P, int32_t M, const float* means3D, const float* sc
                      const float* shs, const float* colors_precomp, const scr_settings* settings,
                      void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream);
 
+/* ---- forward with a mode word (ABI 32).  mode = 0 IS scr_forward_plan; an unknown bit fails before anything is launched.
+ * SCR_MODE_ANTIALIASED: the opacity compensation of Mip-Splatting (upstream 3DGS `antialiasing`, gsplat
+ * rasterize_mode="antialiased").  The operator adds 0.3 px^2 to the diagonal of every projected covariance; in this mode a
+ * splat's opacity is scaled so that its integrated opacity stays what it was before that dilation:
+ *   det0 = a0 c0 - b b   (the 2-D covariance before the dilation),   det = (a0 + 0.3)(c0 + 0.3) - b b,
+ *   h = sqrt(max(0.000025, det0 / det)),   record opacity (SCR_DBG_SPLAT_RECORDS[.][5]) = opacities[i] * h
+ * in binary32, in this order, without contraction.  A negative or NaN ratio (rank-deficient covariance) falls on the floor,
+ * h = 0.005.  Nothing else changes: radii, tile rects, tiles_touched, the culls, the sort and every other record field are
+ * bit-identical to mode 0, and every later kernel reads the opacity from the record.  The call raises SCR_PLAN_ANTIALIASED
+ * in the plan flags (plan_host[3] and geom_buf); scr_forward_run[_aux] take such a state as any other. */
+enum { SCR_MODE_ANTIALIASED = 1 };
+int scr_forward_plan_mode(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales,
+                          const float* rotations, const float* cov3D_precomp, const float* opacities,
+                          const float* shs, const float* colors_precomp, const scr_settings* settings,
+                          void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream);
+
 /* ---- forward, phase 2: per-tile bucketing, depth sort, front-to-back blend.
- * out_color is [3, H, W] fp32.  geom_buf / binning_buf / image_buf must be kept for scr_backward. */
+ * out_color is [3, H, W] fp32.  geom_buf / binning_buf / image_buf must be kept for scr_backward.
+ * Follows the mode of the plan phase that filled geom_buf (the records carry the compensated opacity); the
+ * SCR_PLAN_ANTIALIASED bit of plan_flags is accepted and changes nothing here. */
 int scr_forward_run(int64_t P, int64_t num_rendered, int64_t max_tile_instances, int64_t plan_flags,
                     const scr_settings* settings, void* geom_buf, void* binning_buf, void* image_buf, float* out_color,
                     void* stream);
@@ -135,6 +155,13 @@ int scr_forward_plan_run_aux(int64_t P, int32_t M, const float* means3D, const f
                              const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
                              void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
                              float* out_depth, float* out_alpha, void* stream);
+/* the same with a mode word (ABI 32; see scr_forward_plan_mode).  out_depth and out_alpha both NULL: no maps
+ * (scr_forward_plan_run); both given: scr_forward_plan_run_aux; one of them alone fails.  mode = 0 IS those two. */
+int scr_forward_plan_run_mode(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
+                              const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
+                              const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
+                              void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
+                              float* out_depth, float* out_alpha, void* stream);
 
 /* ---- backward.  dL_dcolor is [3,H,W].  Outputs (each may be NULL when its input was NULL):
  * dL_dmeans3D[P,3], dL_dmeans2D[P,3] (d/d NDC position, z = 0: the gradient SplatCo reads back
@@ -144,7 +171,16 @@ int scr_forward_plan_run_aux(int64_t P, int32_t M, const float* means3D, const f
  * (one 36-byte gradient record per (Gaussian, tile) instance; the entries of a tile's list behind every pixel's last
  * contributor get none -- the tile's cut key in the image buffer, written by the backward, tells which).
  * geom_buf and image_buf are WRITTEN (per-Gaussian record flags, per-tile cut keys): one backward at a time per forward
- * state; the forward's results in them are left intact, so the backward can be repeated.  plan_flags: plan_host[3]. */
+ * state; the forward's results in them are left intact, so the backward can be repeated.  plan_flags: plan_host[3].
+ * Antialiased mode (ABI 32): the backward follows the SCR_PLAN_ANTIALIASED flag the forward left in geom_buf.  Then
+ * g = dL/d(opacity h) comes from the blend, dL_dopacity = g h, and where the clamp of h passed (det0 / det > 0.000025)
+ * dL/dr = g o / (2 h) enters dL/da, dL/db, dL/dc of the 2-D covariance in front of the chain -- so it reaches dL_dmeans3D,
+ * dL_dscales, dL_drotations, dL_dcov3D (and scr_backward_camera's sums) like every other term; on the floor nothing is added.
+ * The input opacity is not an argument of the backward: o is formed as the record's opacity divided by h, h recomputed from
+ * the inputs as the forward did.  The bit of the plan_flags ARGUMENT only picks the kernel instantiation that can do this; it
+ * then looks at geom_buf's flag itself.  A stale argument cannot give plausible wrong numbers: with the bit wrongly set the
+ * results are the right ones; with the bit wrongly clear every gradient the kernel writes is NaN.  With settings->debug
+ * the argument is compared with geom_buf's word and a mismatch fails. */
 int scr_backward(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_flags, const float* means3D, const float* scales,
                  const float* rotations, const float* cov3D_precomp, const float* shs,
                  const scr_settings* settings, const int32_t* radii, void* geom_buf,
@@ -158,7 +194,7 @@ int scr_backward(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_flags,
  * the call IS scr_backward.  dL_dcolor is always given (zeros when the image took no part).  The depth gradient reaches
  * dL_dmeans3D through the view matrix, as the forward formed z.  scratch: scr_backward_scratch_bytes_aux (the records and,
  * behind them, one float per instance).  Works on the saved buffers of either forward entry point; deterministic as
- * scr_backward is. */
+ * scr_backward is, and follows the antialiased flag in geom_buf as scr_backward does. */
 int scr_backward_aux(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_flags, const float* means3D, const float* scales,
                      const float* rotations, const float* cov3D_precomp, const float* shs,
                      const scr_settings* settings, const int32_t* radii, void* geom_buf,
@@ -179,7 +215,8 @@ int scr_backward_aux(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_fl
  * (not wanted); with all three NULL the call IS scr_backward_aux.  Every given output is written, with zeros when P == 0 or
  * num_rendered == 0.  The per-Gaussian outputs are bit-identical to scr_backward_aux's.  Deterministic: the sums over the
  * Gaussians are formed in a fixed order (per 256-Gaussian workgroup, then over the workgroups' rows by one more kernel),
- * without floating-point atomics.  scratch: scr_backward_scratch_bytes_camera(num_rendered, P). */
+ * without floating-point atomics.  scratch: scr_backward_scratch_bytes_camera(num_rendered, P).
+ * Follows the antialiased flag in geom_buf as scr_backward does: the camera sums include the compensation's share. */
 int scr_backward_camera(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_flags, const float* means3D, const float* scales,
                         const float* rotations, const float* cov3D_precomp, const float* shs,
                         const scr_settings* settings, const int32_t* radii, void* geom_buf,

@@ -16,9 +16,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # developer override for A/B experiments with variant builds of the same library
 LIB_PATH = os.environ.get("SPLATCO_RASTER_LIB", os.path.join(_HERE, "csrc", "libsplatco_raster.so"))
 
-PLAN_NONFINITE_COLOUR, PLAN_LARGE_RECTS = 1, 2      # SCR_PLAN_*
+PLAN_NONFINITE_COLOUR, PLAN_LARGE_RECTS, PLAN_ANTIALIASED = 1, 2, 4      # SCR_PLAN_*
+MODE_ANTIALIASED = 1                                # SCR_MODE_* (scr_forward_plan_mode / scr_forward_plan_run_mode)
 PROF_COUNT = 20
-ABI_VERSION = 31
+ABI_VERSION = 32
 FLIP_MAX_RADIUS = 16                                # SCR_FLIP_MAX_RADIUS
 
 (DBG_TILES_TOUCHED, DBG_POINT_OFFSETS, DBG_RANGES, DBG_POINT_LIST, DBG_N_CONTRIB, DBG_FINAL_T, DBG_SPLAT_RECORDS, DBG_QMASK,
@@ -66,10 +67,12 @@ SIGNATURES = [
     ("scr_visible_filter", i32, i64, vp, vp, vp, vp, P(Settings), vp, vp),
     ("scr_mark_visible", i32, i64, vp, vp, vp, vp),
     ("scr_forward_plan", i32, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp),
+    ("scr_forward_plan_mode", i32, i64, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp),
     ("scr_forward_run", i32, i64, i64, i64, i64, P(Settings), *[vp] * 5),
     ("scr_forward_run_aux", i32, i64, i64, i64, i64, P(Settings), *[vp] * 7),
     ("scr_forward_plan_run", i32, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp, sz, vp, vp, vp),
     ("scr_forward_plan_run_aux", i32, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp, sz, *[vp] * 5),
+    ("scr_forward_plan_run_mode", i32, i64, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp, sz, *[vp] * 5),
     ("scr_backward", i32, i64, i32, i64, i64, *[vp] * 5, P(Settings), *[vp] * 15),
     ("scr_backward_aux", i32, i64, i32, i64, i64, *[vp] * 5, P(Settings), *[vp] * 17),
     ("scr_backward_camera", i32, i64, i32, i64, i64, *[vp] * 5, P(Settings), *[vp] * 20),

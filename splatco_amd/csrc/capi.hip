@@ -219,7 +219,8 @@ int scr_mark_visible(int64_t P, const float* means3D, const float* viewmatrix, u
 static int plan_enqueue(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
                         const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
                         const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host, hipStream_t st,
-                        unsigned long long& seq_out) {
+                        unsigned long long& seq_out, int64_t mode) {
+    if (mode & ~(int64_t)SCR_MODE_ANTIALIASED) return fail("mode %lld: unknown bit (SCR_MODE_ANTIALIASED = %d is the only one)", (long long)mode, (int)SCR_MODE_ANTIALIASED);
     if (check_settings(settings)) return 1;
     if (P < 0) return fail("P < 0");
     if (!plan_host) return fail("plan_host is NULL");
@@ -241,7 +242,7 @@ static int plan_enqueue(int64_t P, int32_t M, const float* means3D, const float*
     { ZeroList z; z.add(gv.tile_count, (size_t)g.tiles * 4, st); z.add(gv.total + 3, 8, st); launch_zero(z, st); }
     { ProfScope ps_(SCR_PROF_PREPROCESS, st);
       launch_preprocess(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, ks, gv,
-                        radii_out, st); }
+                        radii_out, (mode & SCR_MODE_ANTIALIASED) != 0, st); }
     CHECK_LAUNCH("preprocess_kernel", settings->debug, st);
     // The two counts come back through a small pinned, device-visible mailbox (one per host thread, created on
     // first use): the scan kernel posts them with a sequence stamp and this thread spins on the stamp.  A blocking
@@ -281,15 +282,32 @@ static int plan_wait(const scr_settings* settings, void* geom_buf, int64_t P, un
     return 0;
 }
 
+static int forward_plan_impl(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales,
+                             const float* rotations, const float* cov3D_precomp, const float* opacities,
+                             const float* shs, const float* colors_precomp, const scr_settings* settings,
+                             void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream) {
+    unsigned long long seq = 0;
+    const int rc = plan_enqueue(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
+                                radii_out, plan_host, (hipStream_t)stream, seq, mode);
+    return rc ? rc : plan_wait(settings, geom_buf, P, seq, plan_host, (hipStream_t)stream);
+}
+
 int scr_forward_plan(int64_t P, int32_t M, const float* means3D, const float* scales,
                      const float* rotations, const float* cov3D_precomp, const float* opacities,
                      const float* shs, const float* colors_precomp, const scr_settings* settings,
                      void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream) {
     SCR_MARK_FN;
-    unsigned long long seq = 0;
-    const int rc = plan_enqueue(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
-                                radii_out, plan_host, (hipStream_t)stream, seq);
-    return rc ? rc : plan_wait(settings, geom_buf, P, seq, plan_host, (hipStream_t)stream);
+    return forward_plan_impl(0, P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
+                             radii_out, plan_host, stream);
+}
+
+int scr_forward_plan_mode(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales,
+                          const float* rotations, const float* cov3D_precomp, const float* opacities,
+                          const float* shs, const float* colors_precomp, const scr_settings* settings,
+                          void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream) {
+    SCR_MARK_FN;
+    return forward_plan_impl(mode, P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
+                             radii_out, plan_host, stream);
 }
 
 // out_depth / out_alpha: both NULL (the colour-only entry points) or both given (the *_aux ones)
@@ -316,7 +334,7 @@ static int forward_run_impl(int64_t P, int64_t I, int64_t max_tile, int64_t plan
                             void* binning_buf, void* image_buf, float* out_color, float* out_depth, float* out_alpha,
                             void* stream, bool scatter_done) {
     if (check_settings(settings)) return 1;
-    if (plan_flags & ~(int64_t)(SCR_PLAN_NONFINITE_COLOUR | SCR_PLAN_LARGE_RECTS)) return fail("plan_flags %lld: not a value scr_forward_plan returned", (long long)plan_flags);
+    if (plan_flags & ~(int64_t)(SCR_PLAN_NONFINITE_COLOUR | SCR_PLAN_LARGE_RECTS | SCR_PLAN_ANTIALIASED)) return fail("plan_flags %lld: not a value scr_forward_plan returned", (long long)plan_flags);
     if (!geom_buf || !binning_buf || !image_buf || !out_color) return fail("NULL buffer");
     hipStream_t st = (hipStream_t)stream;
     KSettings ks = ksettings(settings);
@@ -341,7 +359,7 @@ static int forward_plan_run_impl(int64_t P, int32_t M, const float* means3D, con
                                  const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
                                  const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
                                  void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
-                                 float* out_depth, float* out_alpha, void* stream);
+                                 float* out_depth, float* out_alpha, void* stream, int64_t mode);
 
 int scr_forward_plan_run(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
                          const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
@@ -350,7 +368,7 @@ int scr_forward_plan_run(int64_t P, int32_t M, const float* means3D, const float
     SCR_MARK_FN;
     return forward_plan_run_impl(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
                                  radii_out, plan_host, binning_buf, binning_capacity_bytes, image_buf, out_color, nullptr, nullptr,
-                                 stream);
+                                 stream, 0);
 }
 
 int scr_forward_plan_run_aux(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
@@ -362,20 +380,32 @@ int scr_forward_plan_run_aux(int64_t P, int32_t M, const float* means3D, const f
     if (binning_buf && image_buf && out_color && (!out_depth || !out_alpha)) return fail("out_depth / out_alpha is NULL");
     return forward_plan_run_impl(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
                                  radii_out, plan_host, binning_buf, binning_capacity_bytes, image_buf, out_color, out_depth, out_alpha,
-                                 stream);
+                                 stream, 0);
+}
+
+int scr_forward_plan_run_mode(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
+                              const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
+                              const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
+                              void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
+                              float* out_depth, float* out_alpha, void* stream) {
+    SCR_MARK_FN;
+    if ((out_depth != nullptr) != (out_alpha != nullptr)) return fail("out_depth / out_alpha: give both maps or neither");
+    return forward_plan_run_impl(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
+                                 radii_out, plan_host, binning_buf, binning_capacity_bytes, image_buf, out_color, out_depth, out_alpha,
+                                 stream, mode);
 }
 
 static int forward_plan_run_impl(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
                                  const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
                                  const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
                                  void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
-                                 float* out_depth, float* out_alpha, void* stream) {
+                                 float* out_depth, float* out_alpha, void* stream, int64_t mode) {
     if (!plan_host) return fail("plan_host is NULL");
     plan_host[2] = 0;
     hipStream_t st = (hipStream_t)stream;
     unsigned long long seq = 0;
     int rc = plan_enqueue(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
-                          radii_out, plan_host, st, seq);
+                          radii_out, plan_host, st, seq, mode);
     if (rc) return rc;
     // The scatter kernel goes out BEFORE this thread has seen the instance count: it needs nothing the host knows (the
     // keys are the first array of the binning buffer whatever the count), only room -- and checks on the device that the
@@ -481,7 +511,7 @@ static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, co
         if (dL_dcampos) HIP_TRY(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float), (hipStream_t)stream));
         return 0;
     }
-    if (plan_flags & ~(int64_t)(SCR_PLAN_NONFINITE_COLOUR | SCR_PLAN_LARGE_RECTS)) return fail("plan_flags %lld: not a value scr_forward_plan returned", (long long)plan_flags);
+    if (plan_flags & ~(int64_t)(SCR_PLAN_NONFINITE_COLOUR | SCR_PLAN_LARGE_RECTS | SCR_PLAN_ANTIALIASED)) return fail("plan_flags %lld: not a value scr_forward_plan returned", (long long)plan_flags);
     if (!geom_buf || !binning_buf || !image_buf || !dL_dcolor || !scratch) return fail("NULL buffer");
     if (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity) return fail("NULL argument");
     if (shs ? !dL_dsh : !dL_dcolors) return fail("colour gradient output missing");
@@ -521,7 +551,8 @@ static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, co
       launch_preprocess_backward(P, M, means3D, scales, rotations, cov3D_precomp, shs, ks, radii, gv, bv,
                                  (const GradRec*)scratch, grad_z, iv.cut_key, stamp, record_flags(I, Grid(ks.H, ks.W).tiles), dL_dmeans3D, dL_dmeans2D, shs ? nullptr : dL_dcolors,
                                  shs ? dL_dsh : nullptr, dL_dopacity, cov3D_precomp ? nullptr : dL_dscales,
-                                 cov3D_precomp ? nullptr : dL_drotations, cov3D_precomp ? dL_dcov3D : nullptr, cam_partials, st); }
+                                 cov3D_precomp ? nullptr : dL_drotations, cov3D_precomp ? dL_dcov3D : nullptr, cam_partials,
+                                 (plan_flags & SCR_PLAN_ANTIALIASED) != 0, st); }
     CHECK_LAUNCH("preprocess_backward_kernel", settings->debug, st);
     if (camera) {      // I == 0 included: every row is zero then, and so is every output
         launch_camera_grad_finish(P, cam_partials, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, st);

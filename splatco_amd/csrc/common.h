@@ -363,7 +363,7 @@ void launch_filter(int64_t P, const float* means3D, const float* scales, const f
 void launch_mark_visible(int64_t P, const float* means3D, const float* view, uint8_t* out, hipStream_t st);
 void launch_preprocess(int64_t P, int M, const float* means3D, const float* scales, const float* rotations,
                        const float* cov3D, const float* opacities, const float* shs, const float* colors,
-                       const KSettings& ks, const GeomView& gv, int32_t* radii, hipStream_t st);
+                       const KSettings& ks, const GeomView& gv, int32_t* radii, bool antialiased, hipStream_t st);
 void launch_plan_scans(int64_t P, const KSettings& ks, const GeomView& gv, unsigned long long* mailbox,
                        unsigned long long seq, hipStream_t st);
 void launch_scatter(int64_t P, const KSettings& ks, const GeomView& gv, const BinView& bv, unsigned long long cap_instances,
@@ -383,7 +383,7 @@ void launch_preprocess_backward(int64_t P, int M, const float* means3D, const fl
                                 const unsigned long long* cut_key, unsigned long long stamp, bool deep, float* dL_dmeans3D,
                                 float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh, float* dL_dopacity,
                                 float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* cam_partials,
-                                hipStream_t st);
+                                bool antialiased, hipStream_t st);
 // camera gradients (preprocess.hip): one 32-float row per preprocess-backward workgroup, summed by one more small kernel
 size_t camera_partials_bytes(int64_t P);
 void launch_camera_grad_finish(int64_t P, const float* cam_partials, float* dL_dview, float* dL_dproj, float* dL_dcampos,

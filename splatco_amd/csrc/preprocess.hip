@@ -24,6 +24,7 @@ struct Proj {
     bool clx, cly;
     float T[2][3];      // J * W
     float a, b, c;      // dilated 2D covariance
+    float a0, c0;       // its diagonal before the dilation (the antialiased mode's det0 = a0 c0 - b b)
 };
 
 __device__ __forceinline__ void xform3(const float* __restrict__ M, float x, float y, float z, int i,
@@ -93,9 +94,24 @@ __device__ __forceinline__ void cov2d(Proj& ps, float fx, float fy, float tanfov
 #pragma unroll
         for (int c = 0; c < 3; ++c)
             U[r][c] = (ps.T[r][0] * S[0][c] + ps.T[r][1] * S[1][c]) + ps.T[r][2] * S[2][c];
-    ps.a = ((U[0][0] * ps.T[0][0] + U[0][1] * ps.T[0][1]) + U[0][2] * ps.T[0][2]) + 0.3f;
+    const float a0 = ((U[0][0] * ps.T[0][0] + U[0][1] * ps.T[0][1]) + U[0][2] * ps.T[0][2]);
+    ps.a = a0 + 0.3f;
     ps.b = ((U[0][0] * ps.T[1][0] + U[0][1] * ps.T[1][1]) + U[0][2] * ps.T[1][2]);
-    ps.c = ((U[1][0] * ps.T[1][0] + U[1][1] * ps.T[1][1]) + U[1][2] * ps.T[1][2]) + 0.3f;
+    const float c0 = ((U[1][0] * ps.T[1][0] + U[1][1] * ps.T[1][1]) + U[1][2] * ps.T[1][2]);
+    ps.c = c0 + 0.3f;
+    ps.a0 = a0;      // the values before the dilation, kept as computed (never a - 0.3f)
+    ps.c0 = c0;
+}
+
+// Antialiased mode (opacity compensation of the dilation): h = sqrt(max(0.000025, det(Sigma2D) / det(Sigma2D + 0.3 I))), the
+// factor of the opacity that keeps a splat's integrated opacity what it was before the dilation.  r is left for the
+// backward: r > AA_FLOOR tells that the clamp passed.  A negative r (rank-deficient Sigma) or a NaN falls on the floor
+// (fmaxf returns its other operand for a NaN).  NORMATIVE: this order, no contraction.
+constexpr float AA_FLOOR = 0.000025f;
+__device__ __forceinline__ float aa_factor(const Proj& ps, float det, float& r) {
+    const float det0 = ps.a0 * ps.c0 - ps.b * ps.b;
+    r = det0 / det;
+    return sqrtf(fmaxf(AA_FLOOR, r));
 }
 
 struct Foot {  // screen-space footprint
@@ -226,7 +242,10 @@ __device__ __forceinline__ void sh_to_rgb(int deg, const float* __restrict__ sh,
 // LDS histogram of all tiles (ds_add_u32) and then issues ONE global atomic per tile it touched
 // (LDS_HIST; ~2.5x fewer global atomics at the benchmark density, far fewer for coherent scenes
 // and large splats).  Images with more than LDS_HIST_MAX_TILES tiles count directly in global memory.
-template <bool LDS_HIST>
+// AA: the antialiased mode -- the record carries opacity * h (aa_factor) instead of the opacity; nothing else in the record
+// and no integer output depends on it.  The instantiation also raises SCR_PLAN_ANTIALIASED in the plan flags, from where
+// the backward takes the mode.
+template <bool LDS_HIST, bool AA>
 __global__ void __launch_bounds__(BIN_THREADS)
 preprocess_kernel(int64_t P, int M, const float* __restrict__ means3D, const float* __restrict__ scales,
                   const float* __restrict__ rotations, const float* __restrict__ cov3D,
@@ -241,6 +260,7 @@ preprocess_kernel(int64_t P, int M, const float* __restrict__ means3D, const flo
         for (int t = threadIdx.x; t < tiles; t += BIN_THREADS) hist[t] = 0;
         __syncthreads();
     }
+    if (AA && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(plan_flags, (unsigned long long)SCR_PLAN_ANTIALIASED);
     const int gx = (ks.W + TILE - 1) / TILE;
     uint32_t tsum = 0;
     for (int r = 0; r < BIN_ROUNDS; ++r) {
@@ -282,7 +302,12 @@ preprocess_kernel(int64_t P, int M, const float* __restrict__ means3D, const flo
             uint32_t rhi = (uint32_t)ft.rmaxx | ((uint32_t)ft.rmaxy << 16);
             // blend-ready conic: A = -Qxx/2, B = -Qxy, C = -Qyy/2 (exact scalings of Q)
             rec[3 * i + 0] = make_float4(ft.mx, ft.my, -0.5f * Qxx, -Qxy);
-            rec[3 * i + 1] = make_float4(-0.5f * Qyy, opacities[i], rgb[0], rgb[1]);
+            float op = opacities[i];
+            if (AA) {
+                float r_;
+                op = op * aa_factor(ps, a * c - b * b, r_);
+            }
+            rec[3 * i + 1] = make_float4(-0.5f * Qyy, op, rgb[0], rgb[1]);
             rec[3 * i + 2] = make_float4(rgb[2], ps.t[2], __uint_as_float(rlo), __uint_as_float(rhi));
             radii[i] = ft.radius;
             for (int ty = ft.rminy; ty < ft.rmaxy; ++ty)
@@ -352,7 +377,14 @@ __device__ __forceinline__ void cam_workgroup_sum(const float* v, float* __restr
 // below; the workgroup adds them up in a fixed order (lanes of a wave by shuffles, the four waves through LDS) and leaves one
 // row of CAM_ROW floats in cam_partials[blockIdx.x], which camera_grad_finish_kernel sums.  EVERY thread of the workgroup
 // takes part: a thread past the end works on the last Gaussian's (valid) addresses, counts as invisible and stores nothing.
-template <bool AUX, bool POSE>
+// AA: the forward may have run in the antialiased mode, record opacity = o h (aa_factor).  Whether it did is read from the
+// plan flags the forward left in geom_buf (plan_word), never from an argument of the host: with the bit clear this
+// instantiation computes what the others do.  With the bit set, gop / op below is g = dL/d(o h); then dL/do = g h and, where
+// the clamp passed (r > AA_FLOOR), dL/dr = g o / (2 h) with o = (o h) / h is added to dL/da, dL/db, dL/dc in front of the
+// chain, which carries it to the means, the covariance inputs, the clamped-Jacobian rule and POSE's sums.  On the floor
+// nothing is added.  The instantiations without AA cannot differentiate an antialiased forward: if they meet the bit (a
+// caller handed scr_backward stale plan_flags) every gradient they write is NaN -- loud, not a plausible wrong number.
+template <bool AUX, bool POSE, bool AA>
 __global__ void __launch_bounds__(PRE_BLOCK, 1)
 preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
                            const float* __restrict__ scales, const float* __restrict__ rotations,
@@ -366,7 +398,9 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
                            float* __restrict__ dL_dcolors, float* __restrict__ dL_dsh,
                            float* __restrict__ dL_dopacity, float* __restrict__ dL_dscales,
                            float* __restrict__ dL_drotations, float* __restrict__ dL_dcov3D,
-                           const float* __restrict__ grad_z, float* __restrict__ cam_partials) {
+                           const float* __restrict__ grad_z, float* __restrict__ cam_partials,
+                           const unsigned long long* __restrict__ plan_word) {
+    const bool aa_fwd = (plan_word[0] & (unsigned long long)SCR_PLAN_ANTIALIASED) != 0ull;      // kernel-uniform
     int64_t i = (int64_t)blockIdx.x * PRE_BLOCK + threadIdx.x;
     bool inb = true;
     if (POSE) {
@@ -509,6 +543,19 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
         float dL_da = d2 * (-c * c * gQxx + b * c * gQxy - b * b * gQyy);
         float dL_db = d2 * (2.0f * b * c * gQxx - (det + 2.0f * b * b) * gQxy + 2.0f * a * b * gQyy);
         float dL_dc = d2 * (-b * b * gQxx + a * b * gQxy - a * a * gQyy);
+        if (AA && aa_fwd) {
+            float r;
+            const float h = aa_factor(ps, det, r);
+            if (r > AA_FLOOR) {      // dr/da = (c0 det - det0 c) / det^2, dr/dc = (a0 det - det0 a) / det^2, dr/db = 2 b (det0 - det) / det^2
+                const float o = op / h;
+                const float gr = gop * o / (2.0f * h);
+                const float det0 = ps.a0 * ps.c0 - b * b;
+                dL_da += gr * ((ps.c0 * det - det0 * c) * d2);
+                dL_db += gr * ((2.0f * b * (det0 - det)) * d2);
+                dL_dc += gr * ((ps.a0 * det - det0 * a) * d2);
+            }
+            gop = gop * h;
+        }
         const float* cv = ps.cov;
         float S[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
         float gS[3][3];
@@ -691,6 +738,33 @@ preprocess_backward_kernel(int64_t P, int M, const float* __restrict__ means3D,
     } else if (shs && dL_dsh && (!POSE || inb)) {
         for (int k = 0; k < 3 * M; ++k) dL_dsh[(size_t)i * 3 * M + k] = 0.0f;
     }
+    if (AA && aa_fwd) {
+        // An exact zero leaves with a positive sign.  The chain forms -0 from all-zero sums (2 cA 0 with cA < 0), while the
+        // deep-list variant writes +0 for a Gaussian without a record (has_rec): in this mode the two agree bit for bit in
+        // every output below (dL_dsh, stored coefficient by coefficient above, keeps the chain's signed zeros).
+        // x + 0.0f is x for every other value (no fast-math: the compiler keeps the addition)
+        gop += 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { gm[k] += 0.0f; gm2[k] += 0.0f; gs[k] += 0.0f; gcol[k] += 0.0f; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gq[k] += 0.0f;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) g6[k] += 0.0f;
+    }
+    if (!AA && aa_fwd) {      // stale plan_flags at the host (see above)
+        const float nan = __uint_as_float(0x7fc00000u);
+        gop = nan;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) gm[k] = gm2[k] = gs[k] = nan;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gq[k] = nan;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) g6[k] = nan;
+        if (POSE) {
+#pragma unroll
+            for (int k = 0; k < CAM_VALUES; ++k) cg[k] = nan;
+        }
+    }
     if (!POSE || inb) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -769,18 +843,16 @@ void launch_mark_visible(int64_t P, const float* means3D, const float* view, uin
 
 void launch_preprocess(int64_t P, int M, const float* means3D, const float* scales, const float* rotations,
                        const float* cov3D, const float* opacities, const float* shs, const float* colors,
-                       const KSettings& ks, const GeomView& gv, int32_t* radii, hipStream_t st) {
+                       const KSettings& ks, const GeomView& gv, int32_t* radii, bool antialiased, hipStream_t st) {
     if (P <= 0) return;
     Grid g(ks.H, ks.W);
-    allow_dynamic_lds((const void*)preprocess_kernel<true>, LDS_HIST_MAX_TILES * 4);
-    if (g.tiles <= LDS_HIST_MAX_TILES)
-        preprocess_kernel<true><<<nblk(P, BIN_GPW), BIN_THREADS, (size_t)g.tiles * 4, st>>>(
-            P, M, means3D, scales, rotations, cov3D, opacities, shs, colors, ks, g.tiles, gv.rec, gv.tiles_touched,
-            shs ? gv.clamped : nullptr, gv.block_sums, gv.tile_count, radii, gv.total + 3);
-    else
-        preprocess_kernel<false><<<nblk(P, BIN_GPW), BIN_THREADS, 0, st>>>(
-            P, M, means3D, scales, rotations, cov3D, opacities, shs, colors, ks, g.tiles, gv.rec, gv.tiles_touched,
-            shs ? gv.clamped : nullptr, gv.block_sums, gv.tile_count, radii, gv.total + 3);
+    const bool lds = g.tiles <= LDS_HIST_MAX_TILES;
+    auto kernel = lds ? (antialiased ? preprocess_kernel<true, true> : preprocess_kernel<true, false>)
+                      : (antialiased ? preprocess_kernel<false, true> : preprocess_kernel<false, false>);
+    if (lds) allow_dynamic_lds((const void*)kernel, LDS_HIST_MAX_TILES * 4);
+    kernel<<<nblk(P, BIN_GPW), BIN_THREADS, lds ? (size_t)g.tiles * 4 : 0, st>>>(
+        P, M, means3D, scales, rotations, cov3D, opacities, shs, colors, ks, g.tiles, gv.rec, gv.tiles_touched,
+        shs ? gv.clamped : nullptr, gv.block_sums, gv.tile_count, radii, gv.total + 3);
 }
 
 void launch_preprocess_backward(int64_t P, int M, const float* means3D, const float* scales,
@@ -790,14 +862,18 @@ void launch_preprocess_backward(int64_t P, int M, const float* means3D, const fl
                                 const unsigned long long* cut_key, unsigned long long stamp, bool deep, float* dL_dmeans3D,
                                 float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh, float* dL_dopacity,
                                 float* dL_dscales, float* dL_drotations, float* dL_dcov3D, float* cam_partials,
-                                hipStream_t st) {
+                                bool antialiased, hipStream_t st) {
     if (P <= 0) return;
-    auto kernel = cam_partials ? (grad_z ? preprocess_backward_kernel<true, true> : preprocess_backward_kernel<false, true>)
-                               : (grad_z ? preprocess_backward_kernel<true, false> : preprocess_backward_kernel<false, false>);
+    // antialiased: the host's belief (plan_flags); the AA instantiations follow the forward's own flag in geom_buf either way
+    auto kernel = cam_partials ? (grad_z ? preprocess_backward_kernel<true, true, false> : preprocess_backward_kernel<false, true, false>)
+                               : (grad_z ? preprocess_backward_kernel<true, false, false> : preprocess_backward_kernel<false, false, false>);
+    if (antialiased)
+        kernel = cam_partials ? (grad_z ? preprocess_backward_kernel<true, true, true> : preprocess_backward_kernel<false, true, true>)
+                              : (grad_z ? preprocess_backward_kernel<true, false, true> : preprocess_backward_kernel<false, false, true>);
     kernel<<<nblk(P, PRE_BLOCK), PRE_BLOCK, 0, st>>>(
         P, M, means3D, scales, rotations, cov3D, shs, ks, radii, gv.tiles_touched, gv.point_offsets, gv.live_bits,
         deep ? gv.has_rec : nullptr, gv.clamped, gv.rec, grad_rec, cut_key, stamp, Grid(ks.H, ks.W).tiles, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dsh, dL_dopacity,
-        dL_dscales, dL_drotations, dL_dcov3D, grad_z, cam_partials);
+        dL_dscales, dL_drotations, dL_dcov3D, grad_z, cam_partials, gv.total + 3);
 }
 
 size_t camera_partials_bytes(int64_t P) { return align_up((size_t)(P > 0 ? nblk(P, PRE_BLOCK) : 1) * CAM_ROW * sizeof(float)); }

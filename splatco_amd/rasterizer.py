@@ -14,6 +14,10 @@ shape of the tensor given and only for those that require grad.  The two matrice
 read them: a full projection built in torch from the view matrix gets the composed gradient from autograd.  Columns the
 forward never reads (viewmatrix[:, 3], projmatrix[:, 2]) get exact zeros, campos gets zeros with colors_precomp.  tanfovx /
 tanfovy stay Python floats.  Without such a tensor nothing changes: the same entry points, kernels and bits.
+With antialiased=True (upstream 3DGS `antialiasing`, gsplat rasterize_mode="antialiased") every splat's opacity is multiplied
+by h = sqrt(max(0.000025, det(Sigma2D) / det(Sigma2D + 0.3 I))), which keeps its integrated opacity independent of the
+0.3 px^2 dilation; h is differentiated with respect to the means, the covariance inputs and the view matrix.  Radii, tile
+rects and the sort do not depend on the mode; the default (False) is the same entry points, kernels and bits as before.
 PyTorch is used for device memory and streams only.
 """
 from typing import NamedTuple
@@ -104,9 +108,11 @@ SPECULATE = os.environ.get("SPLATCO_SPECULATIVE_BINNING", "1") != "0"
 _plan_guess = {}           # (device, H, W) -> (P, instances, largest tile) of the last forward at that resolution: sizes the speculative binning buffer
 
 
-def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, shs, colors_precomp, aux=False):
+def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, shs, colors_precomp, aux=False,
+                      antialiased=False):
     """plan + run through the C-ABI.  Returns (color, radii, RasterState).  aux: the blend also writes the depth and
-    opacity maps, two [H, W] tensors left in RasterState.aux for the caller to take."""
+    opacity maps, two [H, W] tensors left in RasterState.aux for the caller to take.  antialiased: the opacity compensation
+    (scr_forward_plan_run_mode with SCR_MODE_ANTIALIASED); RasterState.flags then carries PLAN_ANTIALIASED to the backward."""
     dev = means3D.device
     P = means3D.shape[0]
     M = 0 if shs is None else shs.shape[1]
@@ -122,6 +128,8 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
     maps = () if st.aux is None else (st.aux[0].data_ptr(), st.aux[1].data_ptr())
     plan_run, run = ((_C.lib.scr_forward_plan_run_aux, _C.lib.scr_forward_run_aux) if aux else
                      (_C.lib.scr_forward_plan_run, _C.lib.scr_forward_run))
+    if antialiased:      # one entry point with or without the maps (both NULL: none); the default call stays the old one
+        plan_run = lambda *a: _C.lib.scr_forward_plan_run_mode(_C.MODE_ANTIALIASED, *a[:-1], *((None, None) if not aux else ()), a[-1])
     plan = (C.c_int64 * 4)(0, 0, 0, 0)   # (tile instances, largest per-tile instance count, phase 2 already ran, plan flags)
     # The binning buffer's size is only known after the plan phase.  A guess from the previous call of this size (the
     # instance count of a training loop moves by a few per cent per step) lets both phases go out in ONE call: the GPU
@@ -168,7 +176,7 @@ def _debug_dump(path, raster_settings, **tensors):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, return_aux=False, *camera):
+                raster_settings, return_aux=False, antialiased=False, *camera):
         # camera: () or (viewmatrix, projmatrix, campos) -- the tensors of raster_settings once more, as inputs autograd sees
         ctx.camera = [(tuple(t.shape), t.dtype) for t in camera]
         cs = _CSettings(raster_settings)
@@ -194,7 +202,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             return color, radii
         try:
             color, radii, st = rasterize_forward(cs, means3D, opacities, scales, rotations, cov3Ds_precomp, sh,
-                                                 colors_precomp, **({"aux": True} if return_aux else {}))
+                                                 colors_precomp, **({"aux": True} if return_aux else {}),
+                                                 **({"antialiased": True} if antialiased else {}))
         except RuntimeError as e:
             if raster_settings.debug:
                 raise RuntimeError(str(e) + _debug_dump("snapshot_fw.dump", raster_settings, means3D=means3D, sh=sh,
@@ -215,13 +224,13 @@ class _RasterizeGaussians(torch.autograd.Function):
     def backward(ctx, grad_out_color, _grad_radii, grad_out_depth=None, grad_out_alpha=None):
         st = ctx.state
         # the camera tensors' gradients: asked of the kernel only where the tensor requires grad, None for the rest
-        want_cam = [bool(w) for w in ctx.needs_input_grad[10:]]
+        want_cam = [bool(w) for w in ctx.needs_input_grad[11:]]
         if st is None:
             zeros_cam = tuple(torch.zeros(shape, dtype=dt, device=ctx.shapes[0].device) if w else None
                               for (shape, dt), w in zip(ctx.camera, want_cam))
-            return tuple(None if t is None else torch.zeros_like(t) for t in ctx.shapes) + (None, None) + zeros_cam
+            return tuple(None if t is None else torch.zeros_like(t) for t in ctx.shapes) + (None, None, None) + zeros_cam
         if grad_out_color is None and grad_out_depth is None and grad_out_alpha is None:
-            return (None,) * (10 + len(ctx.camera))      # no output took part in the loss: every gradient is zero
+            return (None,) * (11 + len(ctx.camera))      # no output took part in the loss: every gradient is zero
         means3D, scales, rotations, cov3D, sh, colors, opacities = ctx.saved_tensors
         dev, P, cs = means3D.device, st.P, st.cs
         # with a gradient for one of the maps the blend backward carries two more channels (scr_backward_aux); without, this
@@ -281,17 +290,18 @@ class _RasterizeGaussians(torch.autograd.Function):
         g_cam = tuple(None if t is None else t.reshape(shape).to(dt) for t, (shape, dt) in zip(g_cam, ctx.camera))
         if len(g_cam) < len(ctx.camera):
             g_cam = (None,) * len(ctx.camera)
-        # order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, return_aux, camera
-        return (g_means3D, g_means2D, g_sh, g_col, g_op, g_scales, g_rot, g_cov, None, None) + g_cam
+        # order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, return_aux,
+        # antialiased, camera
+        return (g_means3D, g_means2D, g_sh, g_col, g_op, g_scales, g_rot, g_cov, None, None, None) + g_cam
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, return_aux=False):
+                        raster_settings, return_aux=False, antialiased=False):
     camera = (raster_settings.viewmatrix, raster_settings.projmatrix, raster_settings.campos)
     if not (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in camera)):
         camera = ()      # the default: the camera is a constant, nothing about the call changes
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, bool(return_aux), *camera)
+                                     cov3Ds_precomp, raster_settings, bool(return_aux), bool(antialiased), *camera)
 
 
 class GaussianRasterizer(nn.Module):
@@ -313,9 +323,11 @@ class GaussianRasterizer(nn.Module):
             return out.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, return_aux=False):
+                cov3D_precomp=None, antialiased=False, return_aux=False):
         """(image, radii); with return_aux=True (image, radii, depth, alpha): the [H, W] maps sum_i w_i z_i and sum_i w_i over
-        the image's contributors (module docstring), differentiable like the image."""
+        the image's contributors (module docstring), differentiable like the image.  antialiased=True: every opacity is
+        compensated for the 0.3 px^2 dilation of its splat (module docstring); radii are the same either way.  Pass both
+        switches by keyword."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise ValueError('GaussianRasterizer: pass either shs or colors_precomp (one of them, not both, not neither)')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -325,7 +337,7 @@ class GaussianRasterizer(nn.Module):
         return rasterize_gaussians(
             means3D, means2D, empty if shs is None else shs, empty if colors_precomp is None else colors_precomp,
             opacities, empty if scales is None else scales, empty if rotations is None else rotations,
-            empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, return_aux)
+            empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, return_aux, antialiased)
 
     def visible_filter(self, means3D, scales=None, rotations=None, cov3D_precomp=None):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \

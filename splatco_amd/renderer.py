@@ -187,12 +187,17 @@ def keep_grad(screenspace_points):
         screenspace_points.retain_grad()
 
 
-def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False, aux=False):
+def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False, aux=False,
+           antialiased=None):
     """gaussian_renderer/__init__.py:118-188.  Background tensor must be on the GPU.  aux=True: the result also holds
     "depth" and "alpha", the rasterizer's [H, W] depth and accumulated-opacity maps (GaussianRasterizer.forward).
     A camera whose world_view_transform / full_proj_transform / camera_center require grad (cameras.pose_delta_camera)
     receives the gradient of the image and the maps through the rasterizer operator: projection, covariance projection and
-    depth.  The camera's path through the MLP heads (the anchors' view direction) is not differentiated."""
+    depth.  The camera's path through the MLP heads (the anchors' view direction) is not differentiated.
+    antialiased: the rasterizer's opacity compensation (GaussianRasterizer.forward); None (the default) follows
+    pipe.antialiasing, upstream's pipeline parameter, where the pipe has one."""
+    if antialiased is None:
+        antialiased = bool(getattr(pipe, "antialiasing", False))
     is_training = pc.get_color_mlp.training
     with _C_stage("generate_neural_gaussians"):
         out = generate_neural_gaussians(viewpoint_camera, pc, visible_mask, is_training=is_training)
@@ -207,7 +212,8 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     with _C_stage("rasterize"):
         rendered_image, radii, *maps = rasterizer(means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=color,
                                                   opacities=opacity, scales=scaling, rotations=rot, cov3D_precomp=None,
-                                                  **({"return_aux": True} if aux else {}))
+                                                  **({"return_aux": True} if aux else {}),
+                                                  **({"antialiased": True} if antialiased else {}))
     res = {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
            "radii": radii}
     if aux:
