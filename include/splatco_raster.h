@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SCR_ABI_VERSION 32
+#define SCR_ABI_VERSION 33
 #define SCR_TILE 16 /* 16x16-pixel tiles: part of the result contract (tile rects, ranges, sort keys) */
 
 /* The 12 fields of GaussianRasterizationSettings, same order (gaussian_renderer/__init__.py:145-158).
@@ -568,6 +568,16 @@ typedef struct scr_adam_tensor {
     double step_size, bias_correction2_sqrt;
 } scr_adam_tensor;
 int scr_adam_step(int32_t n_tensors, const scr_adam_tensor* tensors, double beta1, double beta2, double eps, void* stream);
+/* The same step on the VISIBLE ROWS only (ABI 33): every tensor of the table is row-major [n_rows, numel / n_rows] (trailing
+ * dimensions flattened; numel a multiple of n_rows, below 2^32), row_mask[n_rows] is a device byte mask, nonzero = visible.
+ * A visible row's param / exp_avg / exp_avg_sq get exactly the bits scr_adam_step writes for the same table; every other row
+ * keeps its bit patterns and its gradient is never used (it may be NaN or Inf); a lane reads the mask before it touches a
+ * stream, so rows no view of the step sees cost no traffic beyond their mask bytes.  step_size and bias_correction2_sqrt stay
+ * the TENSOR's (the caller counts a step per call): a row that is visible again after n steps resumes from its frozen moments
+ * with the current bias corrections.  n_rows == 0 with every numel == 0 launches nothing.  No allocation, no host
+ * synchronisation; elementwise: bit-reproducible. */
+int scr_adam_step_rows(int32_t n_tensors, const scr_adam_tensor* tensors, const uint8_t* row_mask, int64_t n_rows,
+                       double beta1, double beta2, double eps, void* stream);
 
 /* ---- the tri-plane total-variation term of the training step: train.py:242-243 (`iteration % 4 == 0`, after
  * backward(), before optimizer.step()) -> scene/gaussian_model.py:217-220 (grid `level` of the active levels gets the

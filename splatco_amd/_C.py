@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("SPLATCO_RASTER_LIB", os.path.join(_HERE, "csrc", "lib
 PLAN_NONFINITE_COLOUR, PLAN_LARGE_RECTS, PLAN_ANTIALIASED = 1, 2, 4      # SCR_PLAN_*
 MODE_ANTIALIASED = 1                                # SCR_MODE_* (scr_forward_plan_mode / scr_forward_plan_run_mode)
 PROF_COUNT = 20
-ABI_VERSION = 32
+ABI_VERSION = 33
 FLIP_MAX_RADIUS = 16                                # SCR_FLIP_MAX_RADIUS
 
 (DBG_TILES_TOUCHED, DBG_POINT_OFFSETS, DBG_RANGES, DBG_POINT_LIST, DBG_N_CONTRIB, DBG_FINAL_T, DBG_SPLAT_RECORDS, DBG_QMASK,
@@ -128,6 +128,7 @@ SIGNATURES = [
     ("scr_statis_compute", i32, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp),
     ("scr_statis_apply", i32, i64, i32, *[vp] * 8),
     ("scr_adam_step", i32, i32, P(AdamTensor), f64, f64, f64, vp),
+    ("scr_adam_step_rows", i32, i32, P(AdamTensor), vp, i64, f64, f64, f64, vp),
     ("scr_tv_add_grad", i32, i32, P(TvPlane), vp),
     ("scr_knn", i32, i64, i32, P(f32), *[vp] * 5),
     ("scr_knn_curvature", i32, i64, i32, vp, vp, vp, vp),

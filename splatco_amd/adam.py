@@ -7,7 +7,11 @@ torch's default Adam), so the optimizer surgery of densification (`densify.Ancho
 work on it unchanged and checkpoints interchange with torch.optim.Adam.  What differs is the step: every group is one
 launch of `scr_adam_step` (csrc/adam.hip) over parameter, gradient and moments -- at 20 M anchors that is 40 GB of
 traffic, priced against the copy probe.  weight_decay / amsgrad / maximize are not part of the reference's optimizer and
-are refused."""
+are refused.
+
+Row-sparse step (opt-in): `step(visible=mask)` updates, in the groups that carry `"row_sparse": True` (the per-anchor
+groups), only the rows `mask` marks -- `scr_adam_step_rows` -- and leaves every other row of parameter and moments
+untouched, bit for bit; groups without the key take the dense step.  See FusedAdam.step."""
 import math
 
 import torch
@@ -34,12 +38,47 @@ class FusedAdam(torch.optim.Optimizer):
             st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
         return st
 
+    def _check_visible(self, visible):
+        """The row mask of step(visible=...) against every row-sparse group, before anything is launched."""
+        if not isinstance(visible, torch.Tensor) or visible.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"FusedAdam.step: visible must be a torch.bool or torch.uint8 tensor, got {getattr(visible, 'dtype', type(visible))}")
+        if visible.dim() != 1 or not visible.is_contiguous():
+            raise ValueError(f"FusedAdam.step: visible must be a contiguous [N] tensor, got shape {tuple(visible.shape)}")
+        if not any(group.get("row_sparse", False) for group in self.param_groups):
+            raise ValueError('FusedAdam.step: visible was given but no parameter group carries "row_sparse": True '
+                             "(the step would be a dense one)")
+        N = visible.shape[0]
+        for group in self.param_groups:
+            if not group.get("row_sparse", False):
+                continue
+            for p in group["params"]:
+                if p.dim() < 1 or p.shape[0] != N:
+                    raise ValueError(f"FusedAdam.step: a row-sparse parameter of shape {tuple(p.shape)} against a mask of {N} rows")
+                if p.device != visible.device:
+                    raise ValueError(f"FusedAdam.step: visible lives on {visible.device}, a row-sparse parameter on {p.device}")
+
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, visible=None):
+        """visible=None: the dense step of every group.
+
+        visible: a contiguous [N] torch.bool / torch.uint8 tensor on the parameters' device, nonzero = the row is stepped.
+        Groups with `"row_sparse": True` hold parameters of shape [N, ...]; of those, only the marked rows are read and
+        written (csrc/adam.hip, adam_rows_kernel), with exactly the bits the dense step gives them.  An unmarked row keeps
+        parameter, exp_avg and exp_avg_sq as they are -- no decay of its moments, no move along stale momentum -- and its
+        gradient is not looked at.  All other groups take the dense step.  ValueError if no group is row-sparse.
+
+        Semantics.  The state layout is the dense one and `step` stays the per-TENSOR counter: it advances with every
+        step, whichever rows were marked, so the bias corrections are the tensor's.  A row that becomes visible after a
+        long absence resumes from its frozen moments with the CURRENT bias corrections (close to 1 by then), as if the
+        steps in between had not happened to it.  Upstream 3DGS's sparse Adam
+        (`--optimizer_type sparse_adam`, Taming-3DGS) has no bias correction at all; here a tensor whose rows are all
+        visible in every step gets torch.optim.Adam's numbers exactly."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if visible is not None:
+            self._check_visible(visible)
         for group in self.param_groups:
             if group.get("weight_decay", 0.0) != 0.0 or group.get("amsgrad") or group.get("maximize"):
                 raise NotImplementedError("FusedAdam: a group asks for weight_decay / amsgrad / maximize")
@@ -68,7 +107,11 @@ class FusedAdam(torch.optim.Optimizer):
                 e.step_size = lr / (1.0 - b1 ** t)                     # doubles, as torch's Python forms them
                 e.bias_correction2_sqrt = math.sqrt(1.0 - b2 ** t)
             with torch.cuda.device(dev):
-                _C.check(_C.lib.scr_adam_step(len(ps), table, b1, b2, float(group["eps"]), _C.stream(dev)))
+                if visible is not None and group.get("row_sparse", False):
+                    _C.check(_C.lib.scr_adam_step_rows(len(ps), table, _C.ptr(visible), visible.shape[0], b1, b2, float(group["eps"]),
+                                                       _C.stream(dev)))
+                else:
+                    _C.check(_C.lib.scr_adam_step(len(ps), table, b1, b2, float(group["eps"]), _C.stream(dev)))
             for p in ps:                        # the update is queued for every tensor of the group: the step counts move together
                 self.state[p]["step"] += 1
         return loss

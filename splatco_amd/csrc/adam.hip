@@ -107,4 +107,121 @@ int launch_adam(int n, const scr_adam_tensor* ts, double beta1, double beta2, do
     return 0;
 }
 
+// ---- row-sparse step: the same update on the rows a byte mask marks visible, every other row left alone (bit for bit).
+// Tensors are row-major [n_rows, width]; a lane owns the same float4 as in adam_kernel, finds the rows of its four
+// elements by a 32-bit division by the tensor's width (a multiply-high and two shifts with per-tensor constants:
+// Granlund & Montgomery 1994, figure 4.1 -- exact for every 32-bit dividend), reads their mask bytes and only then touches
+// the four streams: a lane without a visible element returns before any load, so a wave of such lanes issues none.  A
+// float4 that straddles rows of different visibility is loaded whole, updated per element, and the select writes the old
+// bits back to the invisible elements (their gradient may be NaN: it reaches nothing that is stored).
+struct AdamRowsArgs {
+    AdamArgs a;
+    const uint8_t* mask;                    // [n_rows], nonzero = visible
+    uint32_t width[ADAM_MAX];               // numel / n_rows
+    uint32_t magic[ADAM_MAX];               // floor(2^32 (2^L - width) / width) + 1, L = ceil(log2 width)
+    uint8_t sh1[ADAM_MAX], sh2[ADAM_MAX];   // min(L, 1), max(L - 1, 0)
+};
+
+__device__ __forceinline__ uint32_t adam_div(uint32_t n, uint32_t magic, uint32_t sh1, uint32_t sh2) {
+    const uint32_t t = __umulhi(magic, n);
+    return (t + ((n - t) >> sh1)) >> sh2;
+}
+
+__global__ void __launch_bounds__(256) adam_rows_kernel(const AdamRowsArgs ra) {
+    const AdamArgs& a = ra.a;
+    int t = 0;
+    while (t + 1 < a.n && blockIdx.x >= a.first_block[t + 1]) ++t;      // uniform: scalar registers
+    const uint32_t n = (uint32_t)a.numel[t];                            // the launcher refuses numel >= 2^32
+    const uint64_t e64 = ((uint64_t)(blockIdx.x - a.first_block[t]) * 256 + threadIdx.x) * 4;
+    if (e64 >= n) return;
+    const uint32_t e0 = (uint32_t)e64;
+    const uint32_t w = ra.width[t], mg = ra.magic[t], s1 = ra.sh1[t], s2 = ra.sh2[t];
+    const uint8_t* __restrict__ mask = ra.mask;
+    float* __restrict__ p = a.p[t];
+    const float* __restrict__ g = a.g[t];
+    float* __restrict__ m = a.m[t];
+    float* __restrict__ v = a.v[t];
+    const float o1 = a.omb1, b2 = a.beta2, o2 = a.omb2, eps = a.eps, ss = a.step_size[t], bs = a.bias2_sqrt[t];
+    if (a.aligned[t] && n - e0 >= 4) {
+        bool vis[4];
+        const uint32_t r0 = adam_div(e0, mg, s1, s2);
+        if (w >= 4) {                       // uniform.  At most two rows under one float4: the first element's and the last's
+            const uint32_t left = w - (e0 - r0 * w);      // elements of row r0 from e0 on (>= 1)
+            const bool v0 = mask[r0] != 0, v1 = mask[r0 + (left < 4 ? 1u : 0u)] != 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) vis[j] = (uint32_t)j < left ? v0 : v1;
+        } else {
+            vis[0] = mask[r0] != 0;
+#pragma unroll
+            for (int j = 1; j < 4; ++j) vis[j] = mask[adam_div(e0 + j, mg, s1, s2)] != 0;
+        }
+        if (!(vis[0] | vis[1] | vis[2] | vis[3])) return;
+        adam_f4 P = *(const adam_f4*)(p + e0), M = *(const adam_f4*)(m + e0), V = *(const adam_f4*)(v + e0);
+        const adam_f4 G = __builtin_nontemporal_load((const adam_f4*)(g + e0));      // the gradient is dead after this pass
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float pj = P[j], mj = M[j], vj = V[j];
+            adam_one(pj, G[j], mj, vj, o1, b2, o2, eps, ss, bs);
+            P[j] = vis[j] ? pj : P[j];
+            M[j] = vis[j] ? mj : M[j];
+            V[j] = vis[j] ? vj : V[j];
+        }
+        *(adam_f4*)(p + e0) = P;
+        *(adam_f4*)(m + e0) = M;
+        *(adam_f4*)(v + e0) = V;
+    } else {
+        const uint32_t e1 = n - e0 < 4 ? n : e0 + 4;
+        for (uint32_t e = e0; e < e1; ++e) {
+            if (!mask[adam_div(e, mg, s1, s2)]) continue;
+            float P = p[e], M = m[e], V = v[e];
+            adam_one(P, g[e], M, V, o1, b2, o2, eps, ss, bs);
+            p[e] = P;
+            m[e] = M;
+            v[e] = V;
+        }
+    }
+}
+
+int launch_adam_rows(int n, const scr_adam_tensor* ts, const uint8_t* row_mask, int64_t n_rows, double beta1, double beta2,
+                     double eps, hipStream_t st) {
+    for (int t = 0; t < n; ++t)
+        if (ts[t].numel > 0xffffffffll) return 2;
+    for (int t0 = 0; t0 < n; t0 += ADAM_MAX) {
+        AdamRowsArgs ra;
+        AdamArgs& a = ra.a;
+        ra.mask = row_mask;
+        a.n = min(ADAM_MAX, n - t0);
+        a.beta1 = (float)beta1;
+        a.beta2 = (float)beta2;
+        a.omb1 = (float)(1.0 - beta1);
+        a.omb2 = (float)(1.0 - beta2);
+        a.eps = (float)eps;
+        uint64_t blocks = 0;
+        for (int t = 0; t < a.n; ++t) {
+            const scr_adam_tensor& x = ts[t0 + t];
+            a.first_block[t] = (uint32_t)blocks;
+            blocks += (uint64_t)((x.numel + 1023) / 1024);     // 256 lanes x one float4
+            if (blocks > 0x7fffffffull) return 1;
+            a.p[t] = x.param;
+            a.g[t] = x.grad;
+            a.m[t] = x.exp_avg;
+            a.v[t] = x.exp_avg_sq;
+            a.numel[t] = x.numel;
+            a.step_size[t] = (float)x.step_size;
+            a.bias2_sqrt[t] = (float)x.bias_correction2_sqrt;
+            a.aligned[t] = ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 15u) == 0);
+            const uint32_t w = x.numel > 0 ? (uint32_t)(x.numel / n_rows) : 1u;      // an empty tensor launches nothing
+            uint32_t L = 0;
+            while (L < 32 && (1ull << L) < w) ++L;
+            ra.width[t] = w;
+            ra.magic[t] = (uint32_t)((((1ull << L) - w) << 32) / w + 1);
+            ra.sh1[t] = (uint8_t)(L < 1 ? L : 1);
+            ra.sh2[t] = (uint8_t)(L > 1 ? L - 1 : 0);
+        }
+        a.first_block[a.n] = (uint32_t)blocks;
+        if (blocks) adam_rows_kernel<<<(unsigned)blocks, 256, 0, st>>>(ra);
+    }
+    return 0;
+}
+
 }  // namespace scr

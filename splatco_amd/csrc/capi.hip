@@ -1229,6 +1229,32 @@ int scr_adam_step(int32_t n_tensors, const scr_adam_tensor* tensors, double beta
     return 0;
 }
 
+int scr_adam_step_rows(int32_t n_tensors, const scr_adam_tensor* tensors, const uint8_t* row_mask, int64_t n_rows,
+                       double beta1, double beta2, double eps, void* stream) {
+    SCR_MARK_FN;
+    if (n_tensors < 0) return fail("scr_adam_step_rows: n_tensors < 0");
+    if (n_rows < 0) return fail("scr_adam_step_rows: n_rows < 0");
+    if (n_tensors > 0 && !tensors) return fail("scr_adam_step_rows: tensors is NULL");
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0)) return fail("scr_adam_step_rows: bad beta / eps");
+    if (n_rows > 0 && !row_mask) return fail("scr_adam_step_rows: row_mask is NULL");
+    int64_t total = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+        const scr_adam_tensor& x = tensors[t];
+        if (x.numel < 0 || (x.numel > 0 && (!x.param || !x.grad || !x.exp_avg || !x.exp_avg_sq))) return fail("scr_adam_step_rows: NULL tensor");
+        if (!(x.step_size >= 0.0) || !(x.step_size < 1e30) || !(x.bias_correction2_sqrt > 0.0))
+            return fail("scr_adam_step_rows: step_size must be finite and >= 0, bias_correction2_sqrt > 0 (step >= 1)");
+        if (n_rows == 0 ? x.numel != 0 : x.numel % n_rows != 0) return fail("scr_adam_step_rows: numel is not a multiple of n_rows");
+        if (x.numel > 0xffffffffll) return fail("scr_adam_step_rows: numel of 2^32 or more (32-bit element index)");
+        total += x.numel;
+    }
+    if (total == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (launch_adam_rows(n_tensors, tensors, row_mask, n_rows, beta1, beta2, eps, st))
+        return fail("scr_adam_step_rows: more than 2^31 workgroups in one launch");
+    CHECK_LAUNCH("adam_rows_kernel", 0, st);
+    return 0;
+}
+
 // ---- tri-plane total-variation term (tv.hip)
 int scr_tv_add_grad(int32_t n_planes, const scr_tv_plane* planes, void* stream) {
     SCR_MARK_FN;

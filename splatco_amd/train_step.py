@@ -55,7 +55,7 @@ def sync_densification_stats(densifier, n_views, out, vis, device):
 
 
 def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, bucket=None,
-                       consistency_weight=0.0, densifier=None, arena=None, iteration=None, tv_weight=0.0):
+                       consistency_weight=0.0, densifier=None, arena=None, iteration=None, tv_weight=0.0, sparse_adam=False):
     """views / gt_images: the identically ordered mv view list every rank holds; gt_images[i] is the
     [3,H,W] target of views[i] (host or device).  densifier: a splatco_amd.densify.AnchorDensifier; its
     accumulators receive the statistics of the LAST view of the list on every rank (sync_densification_stats).
@@ -70,7 +70,22 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
     divided by the number of ranks; needs the arena in mode "rs_ag").  With the sharded optimizer the gradients in the arena
     are complete on the owning rank only; the total-variation term is added over whole planes on every rank, which gives
     every owned slice its term exactly once.
+    sparse_adam: step only the anchors SOME view of this step sees: the union of the views' prefilter_voxel masks goes to
+    `optimizer.step(visible=union)`, which needs an adam.FusedAdam whose per-anchor groups carry "row_sparse": True (the
+    anchors no view sees have exactly zero gradient rows; the dense step would still stream them and move them along stale
+    momentum).  One rank only.
     Returns (local loss sum, last render dict, bucket or arena buffer)."""
+    from .adam import FusedAdam, ShardedFusedAdam
+    if sparse_adam:
+        if isinstance(optimizer, ShardedFusedAdam):
+            raise NotImplementedError("collaborative_step: sparse_adam with ShardedFusedAdam is not built: its flat per-rank slices "
+                                      "need a row origin to be matched against the visibility mask")
+        if not isinstance(optimizer, FusedAdam):
+            raise TypeError(f"collaborative_step: sparse_adam needs an adam.FusedAdam (step(visible=...)), got {type(optimizer).__name__}")
+        if world_info()[1] > 1:
+            raise NotImplementedError("collaborative_step: sparse_adam on more than one rank is not built: every rank must step with "
+                                      "the SAME union, all-reduced over the ranks' views, and the sharded optimizer's flat slices "
+                                      "need a row origin")
     params = arena.params if arena is not None else [p for p in pc.parameters() if p.requires_grad]
     if arena is not None:
         # the per-anchor gradients (99 % of the arena) are written in place by the gather's backward kernel; the sink is
@@ -92,7 +107,6 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
     rank, world = world_info()
     device = params[0].device
     total, out, vis, rendered = None, None, None, []
-    from .adam import ShardedFusedAdam
     sharded = isinstance(optimizer, ShardedFusedAdam)
     want_union = arena is not None and arena.sparse_rows and arena.active      # (also under the sharded optimizer: set_row_union)
     union = None
@@ -101,7 +115,7 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
         for k, (cam, gt) in enumerate(zip(shard_views(views), shard_views(gt_images))):
             with stage("prefilter_voxel"):
                 vis = prefilter_voxel(cam, pc, pipe, bg_color)
-            if want_union:
+            if want_union or sparse_adam:
                 union = vis.clone() if union is None else union.logical_or_(vis)
             with stage("render"):
                 out = render(cam, pc, pipe, bg_color, visible_mask=vis, retain_grad=True)
@@ -142,5 +156,10 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
             sync_densification_stats(densifier, len(views), out, vis, device)
     if optimizer is not None:
         with stage("optimizer_step"):
-            optimizer.step()
+            if sparse_adam:
+                if union is None:                   # no view: nothing is visible
+                    union = torch.zeros(pc.get_anchor.shape[0], dtype=torch.bool, device=device)
+                optimizer.step(visible=union)
+            else:
+                optimizer.step()
     return (total.detach() if total is not None else None), out, bucket
