@@ -164,13 +164,14 @@ l1_ssim_backward_kernel(int H, int W, const float* __restrict__ img1, const floa
 
 static SsimWindow make_window() {
     SsimWindow w;
-    double g[11], s = 0;
-    for (int i = 0; i < 11; ++i) { g[i] = exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); s += g[i]; }
-    // the reference builds the 1-D window in fp32 (torch.Tensor of python floats) and normalises in fp32
-    float gf[11], sf = 0.0f;
-    for (int i = 0; i < 11; ++i) { gf[i] = (float)g[i]; sf += gf[i]; }
+    // the reference builds the 1-D window in fp32 (torch.Tensor of python floats) and normalises in fp32.  The divisor
+    // is the correctly rounded sum of the fp32 taps (3.7592328), which equals torch's g.sum() for these taps; an ulp on
+    // it is 1.5e-7 on the 2-D window's total and, on a flat image of level 1, on s11 = E11 - mu1^2: 3.3e-4 of the gradient
+    float gf[11];
+    double s = 0;
+    for (int i = 0; i < 11; ++i) { gf[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); s += (double)gf[i]; }
+    const float sf = (float)s;
     for (int i = 0; i < 11; ++i) w.g[i] = gf[i] / sf;
-    (void)s;
     return w;
 }
 

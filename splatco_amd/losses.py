@@ -122,9 +122,15 @@ def pair_l1(gen1, gen2, real1, real2):
 
 
 def l1_ssim(image, gt_image):
-    """Fused (l1_loss, ssim) for [3,H,W] device images; falls back to the torch ops on CPU."""
+    """Fused (l1_loss, ssim) for [C,H,W] device images; falls back to the torch ops on CPU, and where gt_image wants a
+    gradient (the fused backward has none for it).  The kernel reads gt_image with image's extents: another shape or
+    device is an error here, before any launch."""
     if image.is_cuda and image.dim() == 3:
-        return _L1Ssim.apply(image, gt_image)
+        if gt_image.shape != image.shape or gt_image.device != image.device:
+            raise ValueError(f"l1_ssim: gt_image {tuple(gt_image.shape)} on {gt_image.device} does not match "
+                             f"image {tuple(image.shape)} on {image.device}")
+        if not (torch.is_grad_enabled() and gt_image.requires_grad):
+            return _L1Ssim.apply(image, gt_image)
     return l1_loss(image, gt_image), ssim(image, gt_image)
 
 

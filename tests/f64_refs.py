@@ -1,9 +1,10 @@
-"""Float64 references of the three anchor-path operators between the sampler and the rasterizer, and the inputs the
-parity tests feed them.  TEST INFRASTRUCTURE ONLY; nothing here imports the native library.
+"""Float64 references of the three anchor-path operators between the sampler and the rasterizer and of the image losses
+behind it, and the inputs the parity tests feed them.  TEST INFRASTRUCTURE ONLY; nothing here imports the native library.
 
   heads_f64       the three Linear-ReLU-Linear heads on x = cat(feat, ob_view, geo_fea)      -> checker of csrc/mlp_heads.hip
   attention_f64   TriPlaneAttention + chunk + cat(plane, attended plane)                     -> checker of csrc/attention.hip
   expand_f64      torch_restatements.expand_torch_chain on double inputs                     -> checker of csrc/expand.hip
+  ssim_f64        losses.l1_loss + losses.ssim in float64 (and the inputs of pair_l1 / scaling_reg) -> checker of csrc/ssim.hip
 
 The references are plain torch op chains, written from scene_model.py / torch_restatements.py, dtype- and device-agnostic:
 on float64 CPU tensors they are the reference, on float32 device tensors the "framework chain" whose own error against
@@ -27,15 +28,18 @@ def _f64(t):
     return t.detach().to("cpu", torch.float64)
 
 
-def err(got, ref, rows=False, keep=None):
+def err(got, ref, rows=False, keep=None, scale_floor=None, row_floor=None):
     """max|got - ref| / max|ref|.  rows: `got` / `ref` are [rows, ...]; the ratio is taken per row, the row's scale
     floored at 1e-3 of the tensor's, and the largest row is returned (>= the tensor-level ratio by construction): a
-    wrong tail row cannot hide behind 1e5 good ones.  keep: bool [rows], rows that take part."""
+    wrong tail row cannot hide behind 1e5 good ones.  keep: bool [rows], rows that take part.  scale_floor: an absolute
+    floor under the tensor's scale, row_floor: one under each row's (for a reference that may be zero throughout)."""
     got, ref = _f64(got), _f64(ref)
     assert got.shape == ref.shape, (got.shape, ref.shape)
     if got.numel() == 0:
         return 0.0
     scale = float(ref.abs().max())
+    if scale_floor is not None:
+        scale = max(scale, scale_floor)
     if not rows:
         d = float((got - ref).abs().max())
         return d / scale if scale > 0 else (0.0 if d == 0 else float("inf"))
@@ -43,6 +47,8 @@ def err(got, ref, rows=False, keep=None):
     d = (got - ref).abs().amax(dim=1)
     d = torch.where(torch.isnan(d), torch.full_like(d, float("inf")), d)
     s = ref.abs().amax(dim=1).clamp_min(1e-3 * scale)
+    if row_floor is not None:
+        s = s.clamp_min(row_floor)
     if keep is not None:
         d, s = d[keep], s[keep]
         if d.numel() == 0:
@@ -322,3 +328,255 @@ def expand_run(args, k, up, reg=0.0):
         loss.backward()
     grads = [t.grad if t.grad is not None else torch.zeros_like(t) for t in ins]
     return [o.detach() for o in outs], mask, grads
+
+
+# ---------------------------------------------------------------------------------------------------------- image losses
+# csrc/ssim.hip: l1_ssim (16 x 16 tiles, window radius 5, 256 threads, one reduce workgroup striding by 1024), pair_l1
+# (4096 elements per workgroup) and scaling_reg (2048 rows per workgroup); the last two share a finish kernel striding
+# by 1024 partials.
+SSIM_TILE, SSIM_RADIUS, SSIM_REDUCE = 16, 5, 1024
+SSIM_SHAPES = ([(3, h, w) for h, w in [(1, 1), (1, 40), (40, 1), (5, 7), (10, 10), (11, 11), (12, 12), (16, 16), (32, 48),
+                                       (15, 17), (17, 15), (33, 37), (21, 21), (22, 22)]]
+               + [(1, 17, 33), (2, 17, 33), (4, 17, 33), (3, 300, 300)])
+SSIM_CONTENT = ("noise", "identical", "ties", "flat", "flat_both", "ramp", "zeros", "anti", "range", "impulse")
+SSIM_CONTENT_SHAPE = (3, 33, 37)
+# (g_l1, g_ssim); None: the graph does not use that output (autograd hands the kernel a zero for it)
+SSIM_UPSTREAM = [(0.8, -0.2), (1.0, 0.0), (0.0, 1.0), (-3.5, 7e3), (1.0, None), (None, 1.0)]
+SSIM_NONFINITE = {"nan_x": ("x", (1, 16, 16), float("nan")), "nan_y": ("y", (1, 3, 35), float("nan")),
+                  "inf_x": ("x", (0, 0, 0), float("inf"))}
+SSIM_FAULTS = ("reach4_right", "clamp", "no_mu2_dE12", "map_index", "reduce_1024", "sign0_is_1", "tap_sum_ulp")
+
+
+def _up_name(up):
+    return "up_" + "_".join("none" if g is None else "%g" % g for g in up)
+
+
+# (name, (C, H, W), content, (g_l1, g_ssim), non-finite key or None)
+SSIM_CASES = ([("%s%dx%d" % ("" if s[0] == 3 else "c%d_" % s[0], s[1], s[2]), s, "noise", SSIM_UPSTREAM[0], None)
+               for s in SSIM_SHAPES]
+              + [(c, SSIM_CONTENT_SHAPE, c, (0.0, -0.2) if c == "impulse" else SSIM_UPSTREAM[0], None) for c in SSIM_CONTENT]
+              + [(_up_name(u), SSIM_CONTENT_SHAPE, "noise", u, None) for u in SSIM_UPSTREAM[1:]]
+              + [(k, SSIM_CONTENT_SHAPE, "noise", SSIM_UPSTREAM[0], k) for k in SSIM_NONFINITE])
+SSIM_IDS = [c[0] for c in SSIM_CASES]
+
+
+def ssim_inputs(name):
+    """fp32 CPU inputs of one l1_ssim case: dict(x, y, up, nonfinite)."""
+    _, (C, H, W), content, up, nonfinite = SSIM_CASES[SSIM_IDS.index(name)]
+    g = torch.Generator().manual_seed(1000 * C + 37 * H + W)
+    rand, randn = lambda: torch.rand(C, H, W, generator=g), lambda: torch.randn(C, H, W, generator=g)
+    x = rand()                                                         # noise: what test_fused_l1_ssim_matches_torch draws
+    y = (x + 0.15 * randn()).clamp(0, 1)
+    if content == "identical":
+        y = x.clone()
+    elif content == "ties":
+        y = torch.where(rand() < 0.5, x, y)
+    elif content == "flat":
+        x, y = 0.9 + 1e-3 * randn(), torch.full((C, H, W), 0.9)
+    elif content == "flat_both":
+        x, y = 1.0 + 1e-3 * randn(), 1.0 + 1e-3 * randn()
+    elif content == "ramp":
+        ramp = torch.linspace(0, 1, W).expand(C, H, W)
+        x, y = ramp + 1e-3 * randn(), 0.95 * ramp + 0.02
+    elif content == "zeros":
+        x, y = torch.zeros(C, H, W), torch.zeros(C, H, W)
+    elif content == "anti":
+        y = 1.0 - x
+    elif content == "range":
+        x, y = 4.0 * rand() - 1.0, 4.0 * rand() - 1.0
+    elif content == "impulse":                                         # the two pixels sit in the four tiles' common corner
+        y = x.clone()
+        x[:, 15, 15] += 0.25
+        x[:, 16, 16] -= 0.25
+    if nonfinite:
+        which, at, value = SSIM_NONFINITE[nonfinite]
+        (x if which == "x" else y)[at] = value
+    return dict(x=x.contiguous(), y=y.contiguous(), up=up, nonfinite=nonfinite)
+
+
+def ssim_window():
+    """The 11 taps as the reference project and make_window() of csrc/ssim.hip have them: built and normalised in fp32,
+    their sum the correctly rounded one (equal to torch's g.sum() for these taps, losses._window; spelled out here so
+    that the reference does not hang on a summation order).  An ulp on that sum is 1.5e-7 on the window's total and, on a flat
+    image, 3.3e-4 of the gradient: the `flat` cases see it."""
+    from math import exp
+    g = torch.tensor([exp(-(i - SSIM_RADIUS) ** 2 / float(2 * 1.5 ** 2)) for i in range(2 * SSIM_RADIUS + 1)])
+    return g / g.double().sum().float()
+
+
+def _ssim_loss(l1, s, up):
+    terms = [g * v for g, v in zip(up, (l1, s)) if g is not None]
+    return terms[0] if len(terms) == 1 else terms[0] + terms[1]
+
+
+def ssim_f64(x, y, up=None):
+    """losses.ssim and losses.l1_loss restated in float64 on the CPU (the fp32 taps cast up, the 2-D window their outer
+    product in double): (mean |x - y|, mean SSIM, d (g_l1 L1 + g_ssim SSIM) / dx by autograd, or None without `up`)."""
+    x, y = _f64(x).requires_grad_(up is not None), _f64(y)
+    C = x.shape[0]
+    g = ssim_window().double()
+    w = torch.outer(g, g).expand(C, 1, g.numel(), g.numel()).contiguous()
+    conv = lambda t: F.conv2d(t.unsqueeze(0), w, padding=SSIM_RADIUS, groups=C).squeeze(0)
+    mu1, mu2 = conv(x), conv(y)
+    mu1_sq, mu2_sq, mu1_mu2 = mu1 * mu1, mu2 * mu2, mu1 * mu2
+    s11, s22, s12 = conv(x * x) - mu1_sq, conv(y * y) - mu2_sq, conv(x * y) - mu1_mu2
+    C1, C2 = 0.01 ** 2, 0.03 ** 2
+    s = (((2 * mu1_mu2 + C1) * (2 * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s11 + s22 + C2))).mean()
+    l1 = (x - y).abs().mean()
+    dx = torch.autograd.grad(_ssim_loss(l1, s, up), x)[0] if up is not None else None
+    return l1.detach(), s.detach(), dx
+
+
+def ssim_chain(x, y, up):
+    """The fp32 framework chain (losses.l1_loss, losses.ssim) on the device of its arguments: (L1, SSIM, dx)."""
+    from splatco_amd.losses import l1_loss, ssim
+    x = x.detach().clone().requires_grad_(True)
+    l1, s = l1_loss(x, y), ssim(x, y)
+    _ssim_loss(l1, s, up).backward()
+    return l1.detach(), s.detach(), x.grad
+
+
+def ssim_restated_f32(x, y, g_l1, g_ssim, fault=None, with_maps=False):
+    """csrc/ssim.hip's arithmetic in plain fp32 torch on the CPU: zero-padded halo, separable window (horizontal pass,
+    then vertical, taps added in order), the moments, A1 A2 B1 B2, the two reciprocals and the three derivative maps in
+    the kernel's order, the same window over the maps, c0 + 2 x c1 + y c2; sums in double (with_maps: the maps
+    [3,C,H,W] as a fourth result).  (The device contracts
+    g * a + acc to one fma and adds a tile in fp32 before the double sum: neither is restated.)  -> (L1, SSIM, dx).
+    fault: one of SSIM_FAULTS, a deliberate error --
+      reach4_right   the staged tile is one column short on the right: the last tap of the horizontal pass reads 0 at
+                     the pixels of a tile's last column (forward and backward)
+      clamp          clamp-to-edge instead of zero padding (images and maps)
+      no_mu2_dE12    dmu1 without its - mu2 dE12 term
+      map_index      the backward reads map m of channel c at (c * 3 + m) where the forward wrote it at (m * C + c)
+      reduce_1024    tiles with index >= 1024 are left out of the two sums
+      sign0_is_1     sign(0) = 1 in the L1 gradient
+      tap_sum_ulp    the taps divided by their sum added one by one in fp32, an ulp below the correctly rounded one"""
+    assert fault is None or fault in SSIM_FAULTS, fault
+    x, y = x.detach().float().cpu(), y.detach().float().cpu()
+    C, H, W = x.shape
+    T, Rr, g = SSIM_TILE, SSIM_RADIUS, ssim_window()
+    if fault == "tap_sum_ulp":
+        from math import exp
+        raw = torch.tensor([exp(-(i - Rr) ** 2 / float(2 * 1.5 ** 2)) for i in range(2 * Rr + 1)])
+        total = torch.zeros(())
+        for v in raw:
+            total = total + v
+        g = raw / total
+    taps = 2 * Rr + 1
+    last_col = (torch.arange(W) % T == T - 1)
+
+    def pad(t):
+        if fault == "clamp":
+            return F.pad(t.unsqueeze(0), (Rr, Rr, Rr, Rr), mode="replicate").squeeze(0)
+        return F.pad(t, (Rr, Rr, Rr, Rr))
+
+    def window(t):                                                     # [..., H + 10, W + 10] -> [..., H, W]
+        hz = torch.zeros(*t.shape[:-1], W)
+        for k in range(taps):
+            term = g[k] * t[..., k:k + W]
+            if fault == "reach4_right" and k == taps - 1:
+                term = torch.where(last_col, torch.zeros(()), term)
+            hz = hz + term
+        out = torch.zeros(*t.shape[:-2], H, W)
+        for k in range(taps):
+            out = out + g[k] * hz[..., k:k + H, :]
+        return out
+    a, b = pad(x), pad(y)
+    mu1, mu2, e11, e22, e12 = window(torch.stack([a, b, a * a, b * b, a * b]))
+    C1, C2 = torch.tensor(0.01) * torch.tensor(0.01), torch.tensor(0.03) * torch.tensor(0.03)
+    mu1s, mu2s, mu12 = mu1 * mu1, mu2 * mu2, mu1 * mu2
+    s11, s22, s12 = e11 - mu1s, e22 - mu2s, e12 - mu12
+    A1, A2, B1, B2 = 2.0 * mu12 + C1, 2.0 * s12 + C2, mu1s + mu2s + C1, s11 + s22 + C2
+    iB1, iB2 = 1.0 / B1, 1.0 / B2
+    ss = (A1 * A2) * (iB1 * iB2)
+    l1 = (x - y).abs()
+    dE11 = -ss * iB2
+    dE12 = 2.0 * A1 * (iB1 * iB2)
+    dmu1 = 2.0 * mu2 * A2 * (iB1 * iB2) - 2.0 * mu1 * ss * iB1
+    if fault != "no_mu2_dE12":
+        dmu1 = dmu1 - mu2 * dE12
+    dmu1 = dmu1 - 2.0 * mu1 * dE11
+    n = C * H * W
+    keep = torch.ones(C, H, W, dtype=torch.bool)
+    if fault == "reduce_1024":
+        gy, gx = (H + T - 1) // T, (W + T - 1) // T
+        tile = ((torch.arange(C).view(C, 1, 1) * gy + torch.arange(H).view(1, H, 1) // T) * gx
+                + torch.arange(W).view(1, 1, W) // T)
+        keep = tile < SSIM_REDUCE
+    inv = 1.0 / float(n)
+    L1 = (l1.double()[keep].sum() * inv).float()
+    S = (ss.double()[keep].sum() * inv).float()
+    maps = torch.stack([dmu1, dE11, dE12])                             # [3, C, H, W]: (m * C + c) * plane
+    if fault == "map_index":
+        flat = maps.reshape(3 * C, H, W)
+        maps = torch.stack([torch.stack([flat[c * 3 + m] for c in range(C)]) for m in range(3)])
+    c0, c1, c2 = window(pad(maps.reshape(3 * C, H, W)).reshape(3, C, H + 2 * Rr, W + 2 * Rr))
+    d = x - y
+    one = torch.ones(())
+    sgn = torch.where(d > 0, one, torch.where(d < 0, -one, one if fault == "sign0_is_1" else torch.zeros(())))
+    inv_n = torch.tensor(inv, dtype=torch.float64).float()
+    gl = torch.tensor(0.0 if g_l1 is None else g_l1, dtype=torch.float32)
+    gs = torch.tensor(0.0 if g_ssim is None else g_ssim, dtype=torch.float32)
+    dx = (gl * inv_n) * sgn + (gs * inv_n) * (c0 + 2.0 * x * c1 + y * c2)
+    return (L1, S, dx, maps) if with_maps else (L1, S, dx)
+
+
+def ssim_dx_floor(up, n):
+    """Floor of the scale d x is measured against: (|g_l1| + |g_ssim|) / n, the size of a gradient that is not there.
+    On identical images the true gradient is 1e-16 and a ratio to it is noise over nothing."""
+    return sum(abs(g) for g in up if g is not None) / n
+
+
+# Cases whose image rows take the same floor under their own scale; every other case keeps the module's rule (a row's
+# scale floored at 1e-3 of the tensor's).  On `identical` d x = x (2 G*dE11 + G*dE12) with the two terms
+# +-2 x G*(1 / B2) = +-12 / n cancelling, so correct fp32 leaves 6e-7 of the floor in every row, which the module's
+# rule reports as 6e-4: the exact restatement 5.7e-4 against 1.5 x 3.0e-4 of the chain, a coin toss between two noises.
+# No image with y = x avoids it (the terms scale with x / B2), so the case cannot be changed to meet the rule.  A wrong
+# halo or index moves a row by 1e-3 .. 1 of the floor (test_f64_refs_host.py), fifty times the bar and more.
+SSIM_ROW_FLOOR_CASES = ("identical",)
+
+
+def ssim_row_floor(name, up, n):
+    return ssim_dx_floor(up, n) if name in SSIM_ROW_FLOOR_CASES else None
+
+
+def ssim_figures(got, ref, finite=None):
+    """{L1, SSIM, dx, dx rows: e} of (L1, SSIM, dx) triples; `ref` carries the floor of dx's scale as a fourth entry and
+    that of its rows' scale (or None) as a fifth.
+    finite: bool [C,H,W], the elements of dx that take part (the others are compared as sets by the caller)."""
+    gd, rd = _f64(got[2]), _f64(ref[2])
+    if finite is not None:
+        gd, rd = torch.where(finite, gd, torch.zeros(())), torch.where(finite, rd, torch.zeros(()))
+    W = rd.shape[-1]
+    return {"L1": err(got[0], ref[0]), "SSIM": err(got[1], ref[1]), "dx": err(gd, rd, scale_floor=ref[3]),
+            "dx rows": err(gd.reshape(-1, W), rd.reshape(-1, W), rows=True, scale_floor=ref[3], row_floor=ref[4])}
+
+
+# scaling regulariser: rows per workgroup 2048, so the last two sizes give 1024 and 1025 partials
+SREG_P = [1, 255, 256, 257, 2047, 2048, 2049, 2_097_152, 2_097_153]
+SREG_EDGE_ROWS = [(0.0, 0.7, 1.3), (0.0, 0.0, 0.4), (0.0, 0.0, 0.0), (-0.5, 0.7, 1.2), (1e-20, 1e-20, 1.0)]
+SREG_ZERO_ROWS = 3                                                    # the first three edge rows hold a zero
+
+
+def sreg_inputs(P):
+    """fp32 CPU scaling [P,3]: uniform in [0.01, 2], the first min(P, 5) rows the edge rows."""
+    g = torch.Generator().manual_seed(P)
+    s = 0.01 + 1.99 * torch.rand(P, 3, generator=g)
+    k = min(P, len(SREG_EDGE_ROWS))
+    s[:k] = torch.tensor(SREG_EDGE_ROWS[:k])
+    return s
+
+
+# pair L1: 4096 elements per workgroup, so the last two sizes give 1024 and 1025 partials
+PAIR_N = [1, 4095, 4096, 4097, 4_194_304, 4_194_305]
+PAIR_ZERO_STRIDE = 53                                                # the column 0 of the (3, 37, 53) case, flattened
+
+
+def pair_inputs(n):
+    """fp32 CPU (gen1, gen2, real1, real2) of n elements; every 53rd residual (real1 - real2) - (gen1 - gen2) is at or
+    next to zero, as column 0 of test_fused_pair_l1_matches_the_reference_ops."""
+    g = torch.Generator().manual_seed(n)
+    r1, r2, a0, b0 = (torch.rand(n, generator=g) for _ in range(4))
+    z = slice(0, None, PAIR_ZERO_STRIDE)
+    b0[z] = a0[z] - (r1[z] - r2[z])
+    return a0, b0, r1, r2

@@ -1,6 +1,9 @@
 """The float64 references of tests/f64_refs.py, checked on the CPU: they reproduce the golden fixtures captured from
 the reference's own Python, they are differentiable where the parity tests differentiate them, a tied pool maximum
-belongs to its first pixel, and the inputs of every GPU case stay inside the caps on replaced / excluded elements."""
+belongs to its first pixel, and the inputs of every GPU case stay inside the caps on replaced / excluded elements.  For the
+image losses: correct fp32 arithmetic (a restatement of csrc/ssim.hip's, and the framework chain) meets the bars of the GPU
+test on every case, and six deliberately wrong restatements each miss them on the cases chosen to see them."""
+import functools
 import os
 
 import numpy as np
@@ -195,3 +198,160 @@ def test_expansion_inputs_hold_what_the_case_is_about(name, V, k, select, edges)
             assert mask[e[q]] and float(sr[e[q], 3:].double().norm()) < 1e-12
         assert float(sr[e["quat_tiny"], 3:].abs().max()) > 0
         assert mask[e["sig_hi"]] and mask[e["sig_lo"]] and mask[e["sig_mixed"]]
+
+
+# ---------------------------------------------------------------------------------------------------------- image losses
+def test_ssim_reference_reproduces_the_golden_losses():
+    """losses.npz (captured from the reference's own loss functions in fp32): ssim_f64 / its L1 on the fixture's second
+    image pair, to the fp32 rounding of the recorded values (the bars of test_fused_l1_ssim_matches_torch)."""
+    d = _npz("losses.npz")
+    l1, s, dx = R.ssim_f64(torch.tensor(d["a1"]), torch.tensor(d["b1"]))
+    assert dx is None
+    assert abs(float(s) - float(d["ssim_1"])) <= 1e-5 * abs(float(d["ssim_1"]))
+    assert abs(float(l1) - float(d["l1_1"])) <= 1e-6
+
+
+@functools.lru_cache(maxsize=None)
+def _ssim_case(name):
+    """(inputs, float64 result + the floor of dx's scale, finite elements of the float64 dx, the chain's result, its
+    figures): computed once per case, shared by the tests below and never modified."""
+    d = R.ssim_inputs(name)
+    n = d["x"].numel()
+    ref = (*R.ssim_f64(d["x"], d["y"], d["up"]), R.ssim_dx_floor(d["up"], n), R.ssim_row_floor(name, d["up"], n))
+    finite = torch.isfinite(ref[2])
+    chain = R.ssim_chain(d["x"], d["y"], d["up"])
+    return d, ref, finite, chain, R.ssim_figures(chain, ref, finite)
+
+
+def _same_class(got, ref):
+    """A non-finite value: NaN where the reference is NaN, the same infinity where it is infinite."""
+    got, ref = float(got), float(ref)
+    return got != got if ref != ref else got == ref
+
+
+@pytest.mark.parametrize("name", R.SSIM_IDS)
+def test_correct_fp32_arithmetic_meets_the_bars_of_the_gpu_test(name):
+    """The condition under which test_gpu_f64_parity.test_l1_ssim_against_float64 may ask what it asks: on every case
+    the plain fp32 restatement of the kernel's arithmetic stays within max(2e-5, 1.5 e_chain) of float64, e_chain being
+    the fp32 framework chain's figure on the CPU (which is within its own bar by construction: what is asserted of it
+    is that it is finite where float64 is).  On the non-finite cases the three non-finite sets of dx are equal, the
+    finite rest meets the bar, and the two values are non-finite in float64's way: NaN, except L1 of `inf_x`, which is
+    +Inf in float64 itself (mean |Inf - y|).
+    Measured here: noise 3.3e-7 against 9.9e-7 (dx), flat 2.0e-4 against 4.8e-4, flat_both 8.6e-5 against 2.0e-4, ramp
+    1.8e-5 against 5.4e-5; non-finite elements 441, 168 and 121 in all three.  One thing had to give: on `identical`
+    the floor of dx's scale goes under every row's scale too (f64_refs.SSIM_ROW_FLOOR_CASES says why)."""
+    d, ref, finite, chain, f_chain = _ssim_case(name)
+    got = R.ssim_restated_f32(d["x"], d["y"], *d["up"])
+    f = R.ssim_figures(got, ref, finite)
+    values = ("L1", "SSIM")
+    for k in f:
+        if d["nonfinite"] and k in values:
+            continue
+        print(f"l1_ssim {name:16s} {k:8s} restated {f[k]:9.3e}  chain {f_chain[k]:9.3e}  bar {R.bar(f_chain[k]):9.3e}")
+    print(f"l1_ssim {name:16s} non-finite elements of dx: {int((~finite).sum())}")
+    if d["nonfinite"]:
+        assert int((~finite).sum()) == {"nan_x": 441, "nan_y": 168, "inf_x": 121}[name]   # 21 x 21, 14 x 12, 11 x 11
+        for r in (got, chain):
+            assert torch.equal(torch.isfinite(r[2]), finite)
+            assert _same_class(r[0], ref[0]) and _same_class(r[1], ref[1])
+        assert float(ref[1]) != float(ref[1]) and not torch.isfinite(ref[0])
+        assert (float(ref[0]) == float("inf")) == (name == "inf_x")
+    else:
+        assert finite.all()
+        for r in (got, chain):
+            assert all(bool(torch.isfinite(t).all()) for t in r)
+    for k in f:
+        if not (d["nonfinite"] and k in values):
+            assert f[k] <= R.bar(f_chain[k]) and f_chain[k] <= R.bar(f_chain[k]), (k, f[k], f_chain[k])
+    if name == "identical":
+        assert float(got[0]) == 0 and abs(float(got[1]) - 1) <= 2.0 ** -22
+    if name == "anti":
+        assert float(ref[1]) < 0
+
+
+_FINITE = {n for n in R.SSIM_IDS if n not in R.SSIM_NONFINITE}
+_USES_DSSIM = _FINITE - {"up_1_0", "up_1_none"}                        # the SSIM gradient reaches dx
+_W21 = {c[0] for c in R.SSIM_CASES if c[1][2] >= 21}                   # a full tile column with five pixels to its right
+SSIM_FAULT_SEEN_BY = {
+    # under any window the maps of x == y cancel (identical) or vanish (zeros); L1-only graphs never read the maps, and the
+    # value moves by the last tap (1e-3) on two columns of 37, below the floor; W < 21: the sixth pixel right of column
+    # 15 is outside the image and 0 either way
+    "reach4_right": (_USES_DSSIM & _W21) - {"identical", "zeros"},
+    # x == y at the border (impulse: the two pixels are interior): SSIM = 1 and cancelling maps under any padding
+    "clamp": _FINITE - {"identical", "zeros", "impulse"},
+    "no_mu2_dE12": _USES_DSSIM - {"zeros"},                            # mu2 = 0
+    "map_index": _USES_DSSIM - {"c1_17x33"},                           # c * 3 + m == m * C + c at C = 1
+    "reduce_1024": {"300x300"},                                        # the only case with more than 1024 tiles (1083)
+    "sign0_is_1": {"identical", "ties", "zeros"},                      # the cases with x == y where g_l1 != 0
+}
+
+
+@pytest.mark.parametrize("fault", sorted(SSIM_FAULT_SEEN_BY))
+def test_a_wrong_restatement_misses_the_bars_on_the_cases_chosen_for_it(fault):
+    """Each deliberate error of f64_refs.ssim_restated_f32 fails the bars of the GPU test on exactly the cases named in
+    SSIM_FAULT_SEEN_BY, which say why the others cannot see it: the cases see the errors they were chosen for."""
+    missed = set()
+    for name in sorted(_FINITE):
+        d, ref, finite, _, f_chain = _ssim_case(name)
+        f = R.ssim_figures(R.ssim_restated_f32(d["x"], d["y"], *d["up"], fault=fault), ref, finite)
+        bad = {k: f[k] / R.bar(f_chain[k]) for k in f if not f[k] <= R.bar(f_chain[k])}
+        if bad:
+            missed.add(name)
+            print(f"{fault:13s} {name:16s} " + "  ".join(f"{k} {v:.3g} x bar" for k, v in bad.items()))
+    assert missed and missed == SSIM_FAULT_SEEN_BY[fault], (sorted(missed - SSIM_FAULT_SEEN_BY[fault]),
+                                                            sorted(SSIM_FAULT_SEEN_BY[fault] - missed))
+
+
+def test_an_ulp_on_the_sum_of_the_taps_shows_on_flat_images():
+    """The seventh fault, tap_sum_ulp: the taps divided by their sum added one by one in fp32 (3.7592325, an ulp below the
+    correctly rounded 3.7592328).  The 2-D window then sums to 1 + 8.9e-8 where the reference's sums to 1 - 6.2e-8, and
+    s11 = E11 - mu1^2 and s22 each move by 1.5e-7 mu^2: 3e-7 on B2 = s11 + s22 + C2 = 9.0e-4, that is 3.3e-4 of the
+    maps and of dx, on `flat_both` (level 1).  The exact restatement is at 8.6e-5 there.  (The GPU test's bar on that
+    case, 1.5 x the chain's 1.8e-4 .. 2.0e-4, lies between the two.)"""
+    d, ref, finite, _, _ = _ssim_case("flat_both")
+    good = R.ssim_figures(R.ssim_restated_f32(d["x"], d["y"], *d["up"]), ref, finite)["dx"]
+    bad = R.ssim_figures(R.ssim_restated_f32(d["x"], d["y"], *d["up"], fault="tap_sum_ulp"), ref, finite)["dx"]
+    print(f"flat_both dx: exact restatement {good:.3e}, an ulp on the tap sum {bad:.3e}")
+    assert good <= 1.5e-4 and 2.5e-4 <= bad <= 4.5e-4
+    total = lambda g: float(torch.outer(g.double(), g.double()).sum()) - 1.0
+    assert abs(total(R.ssim_window()) + 6.2e-8) < 1e-8
+
+
+def test_the_reference_taps_are_the_chain_taps():
+    """f64_refs.ssim_window() fixes its own summation order; losses._window leaves it to torch's sum.  Bit for bit the
+    same taps: an ulp between them is the 3.3e-4 of the test above, and would be charged to the kernel."""
+    from splatco_amd.losses import _window
+    g = R.ssim_window()
+    assert g.dtype == torch.float32
+    assert torch.equal(_window(11, 3, torch.zeros(1)), g.unsqueeze(1).mm(g.unsqueeze(0)).expand(3, 1, 11, 11))
+
+
+def test_image_loss_inputs_hold_what_the_case_is_about():
+    T = R.SSIM_TILE
+    tiles = lambda s: s[0] * ((s[1] + T - 1) // T) * ((s[2] + T - 1) // T)
+    assert [tiles(s) > R.SSIM_REDUCE for s in R.SSIM_SHAPES] == [False] * (len(R.SSIM_SHAPES) - 1) + [True]
+    assert tiles(R.SSIM_SHAPES[-1]) == 1083
+    assert len(set(R.SSIM_IDS)) == len(R.SSIM_IDS)
+    d = R.ssim_inputs("identical")
+    assert torch.equal(d["x"], d["y"])
+    d = R.ssim_inputs("ties")
+    assert 0.4 < float((d["x"] == d["y"]).float().mean()) < 0.6
+    d = R.ssim_inputs("impulse")
+    assert (d["x"] != d["y"]).nonzero().tolist() == [[c, p, p] for c in range(3) for p in (15, 16)] and d["up"][0] == 0
+    d = R.ssim_inputs("range")
+    assert float(d["x"].min()) < -0.9 and float(d["x"].max()) > 2.9
+    for name, (which, at, value) in R.SSIM_NONFINITE.items():
+        d = R.ssim_inputs(name)
+        bad = ~torch.isfinite(d[which])
+        assert int(bad.sum()) == 1 and bool(bad[at]) and torch.isfinite(d["y" if which == "x" else "x"]).all()
+    nb = lambda n, per: (n + per - 1) // per
+    assert [nb(P, 2048) for P in R.SREG_P[-2:]] == [1024, 1025] and [nb(n, 4096) for n in R.PAIR_N[-2:]] == [1024, 1025]
+    for P in R.SREG_P:
+        s = R.sreg_inputs(P)
+        k = min(P, len(R.SREG_EDGE_ROWS))
+        assert s.shape == (P, 3) and torch.equal(s[:k], torch.tensor(R.SREG_EDGE_ROWS[:k]))
+        assert float(s[k:].min() if P > k else 1) >= 0.01 and [int((r == 0).sum()) for r in s[:3]] == [1, 2, 3][:k]
+    for n in R.PAIR_N[:4]:
+        a, b, r1, r2 = R.pair_inputs(n)
+        res = (r1 - r2) - (a - b)
+        assert float(res[::R.PAIR_ZERO_STRIDE].abs().max()) <= 2.0 ** -22 and (n < 2 or float(res.abs().max()) > 0.1)

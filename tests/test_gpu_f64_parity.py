@@ -1,4 +1,5 @@
-"""csrc/mlp_heads.hip, csrc/attention.hip and csrc/expand.hip against float64, at the edges of their launch shapes.
+"""csrc/mlp_heads.hip, csrc/attention.hip, csrc/expand.hip and csrc/ssim.hip against float64, at the edges of their launch
+shapes.
 
 Every case runs, on the same packed fp32 inputs (drawn on the CPU, tests/f64_refs.py):
   the kernel, through the product wrapper (mlp_heads.mlp_heads, plane_attention.attended_pair_planes,
@@ -9,7 +10,8 @@ For every tensor e = max|got - ref| / max|ref|; for per-anchor / per-candidate /
 row with the row's scale floored at 1e-3 of the tensor's (f64_refs.err).  The bar is max(floor, c * e_chain), e_chain
 being the same figure of the fp32 chain against the same float64 result in the same process: floor 2e-5, c = 1.5 (the
 constants of test_fused_norm_linear_matches_batchnorm_linear_chain).  Every figure is printed before anything is
-asserted (and appended to the file $SPLATCO_F64_PARITY_LOG names, if set); profiles/r08_f64_parity.txt is one such run.
+asserted (and appended to the file $SPLATCO_F64_PARITY_LOG names, if set); profiles/r08_f64_parity.txt is one such run,
+profiles/r13_loss_f64_parity.txt one of the image losses (l1_ssim, scaling_reg, pair_l1: the end of this file).
 """
 import copy
 import os
@@ -30,8 +32,8 @@ class Report:
     def __init__(self, op, case):
         self.op, self.case, self.lines, self.failed = op, case, [], []
 
-    def add(self, name, got, chain, ref, rows=False, keep=None, floor=R.FLOOR):
-        e, e_chain = R.err(got, ref, rows, keep), R.err(chain, ref, rows, keep)
+    def add(self, name, got, chain, ref, rows=False, keep=None, floor=R.FLOOR, scale_floor=None, row_floor=None):
+        e, e_chain = R.err(got, ref, rows, keep, scale_floor, row_floor), R.err(chain, ref, rows, keep, scale_floor, row_floor)
         b = R.bar(e_chain, floor)
         self.lines.append(f"{self.op:9s} {self.case:16s} {name:22s} e {e:9.3e}  e_chain {e_chain:9.3e}  bar {b:9.3e}"
                           f"{'' if e <= b else '   <-- FAIL'}")
@@ -42,6 +44,12 @@ class Report:
         self.lines.append(f"{self.op:9s} {self.case:16s} {what:22s} {'ok' if ok else 'FAIL'}")
         if not ok:
             self.failed.append((what,))
+
+    def within(self, name, d, bound):
+        """A figure with an a-priori bound (no chain to compare with)."""
+        self.lines.append(f"{self.op:9s} {self.case:16s} {name:22s} e {d:9.3e}  bound {bound:9.3e}{'' if d <= bound else '   <-- FAIL'}")
+        if not d <= bound:
+            self.failed.append((name, d, bound))
 
     def finish(self):
         text = "\n".join(self.lines)
@@ -247,4 +255,205 @@ def test_expand_compact_against_float64(name, V, k, select, edges):
         rep.require(_same_bits(k_o, k_o2) and _same_bits(k_g, k_g2) and torch.equal(k_m, k_m2) and torch.equal(k_i, k_i2),
                     "bit-reproducible" + tag)
         rep.require(all(bool(torch.isfinite(t).all()) for t in k_o + k_g), "finite" + tag)
+    rep.finish()
+
+
+# ---------------------------------------------------------------------------------------------------------- image losses
+def _l1_ssim_run(fn, x, y, up):
+    """(L1, SSIM, dx) of fn(x, y) -> (L1, SSIM) with x a fresh leaf; only the outputs `up` weights are in the graph."""
+    x = x.detach().clone().requires_grad_(True)
+    l1, s = fn(x, y)
+    R._ssim_loss(l1, s, up).backward()
+    return l1.detach(), s.detach(), x.grad
+
+
+@pytest.mark.parametrize("name", R.SSIM_IDS)
+def test_l1_ssim_against_float64(name):
+    """l1_ssim_forward / _reduce / _backward_kernel (16 x 16 tiles with a 5-pixel halo, 256 threads, the reduce workgroup
+    striding by 1024 tiles).  Shapes: images thinner or smaller than the window and the halo, around the 11 taps, exact
+    tiles and one off, a last tile that is exactly the halo and one more, C = 1, 2, 4 (the maps are indexed
+    (m * C + c) * plane) and 1083 tiles.  Content at 3 x 33 x 37: the noise of test_fused_l1_ssim_matches_torch, y == x
+    everywhere / on half the pixels (sign(0) = 0), flat and smooth images where s11 = E11 - mu1^2 cancels, zero images,
+    a negative SSIM, values outside [0, 1], and two pixels whose gradient footprint crosses four tiles.  Upstream
+    gradients of both signs and sizes, and graphs that use one output only.  A NaN or +Inf pixel: the values are
+    non-finite as in float64 (NaN; L1 of inf_x is +Inf in float64 itself), dx is non-finite on float64's set of pixels
+    and meets the bar elsewhere.  L1, SSIM, dx and dx per image row against max(2e-5, 1.5 e_chain); the scale of dx is
+    floored at (|g_l1| + |g_ssim|) / n (f64_refs.ssim_dx_floor), on `identical` that of every row too
+    (f64_refs.SSIM_ROW_FLOOR_CASES).  tests/test_f64_refs_host.py shows that correct fp32
+    arithmetic meets these bars on every case and six wrong kernels do not."""
+    from splatco_amd.losses import l1_loss, l1_ssim, ssim
+    d = R.ssim_inputs(name)
+    rep = Report("l1_ssim", name)
+    up = d["up"]
+    ref = R.ssim_f64(d["x"], d["y"], up)
+    floor = R.ssim_dx_floor(up, d["x"].numel())
+    finite = torch.isfinite(ref[2])
+    x, y = d["x"].to(DEV), d["y"].to(DEV)
+    chain = _l1_ssim_run(lambda a, b: (l1_loss(a, b), ssim(a, b)), x, y, up)
+    k1, k2 = _l1_ssim_run(l1_ssim, x, y, up), _l1_ssim_run(l1_ssim, x, y, up)
+    assert k1[2].shape == x.shape and k1[2].dtype == torch.float32 and k1[0].shape == k1[1].shape == ()
+    zero = torch.zeros(())
+    dxs = [torch.where(finite, R._f64(t[2]), zero) for t in (k1, chain, ref)]
+    if d["nonfinite"]:
+        same = lambda got, want: bool(torch.isnan(got)) if bool(torch.isnan(want)) else float(got) == float(want)
+        rep.require(same(k1[0], ref[0]) and not bool(torch.isfinite(ref[0])), "L1 non-finite as f64")
+        rep.require(bool(torch.isnan(k1[1])) and bool(torch.isnan(ref[1])), "SSIM is NaN")
+        rep.require(torch.equal(torch.isfinite(k1[2]).cpu(), finite), "non-finite set of dx")
+        rep.lines.append(f"l1_ssim   {name:16s} non-finite elements of dx  {int((~finite).sum())} of {finite.numel()}")
+    else:
+        rep.add("L1", k1[0], chain[0], ref[0])
+        rep.add("SSIM", k1[1], chain[1], ref[1])
+        rep.require(all(bool(torch.isfinite(t).all()) for t in k1) and bool(finite.all()), "finite")
+    W = x.shape[-1]
+    rep.add("dx", *dxs, scale_floor=floor)
+    rep.add("dx rows", *(t.reshape(-1, W) for t in dxs), rows=True, scale_floor=floor,
+            row_floor=R.ssim_row_floor(name, up, d["x"].numel()))
+    rep.require(all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(k1, k2)), "bit-reproducible")
+    if name == "identical":
+        rep.require(float(k1[0]) == 0.0, "L1 == 0")
+        rep.within("|SSIM - 1|", abs(float(k1[1].double()) - 1.0), 2.0 ** -22)
+    rep.finish()
+
+
+def test_l1_ssim_entry_points():
+    """The ways into the forward kernel other than a packed fp32 leaf, on 3 x 33 x 37 noise: without the derivative maps
+    (with_grad = 0: under no_grad, metrics.ssim_value, multiview.pair_similarity) the SSIM has the bits of the
+    differentiable run; a non-contiguous crop of a leaf and float64 / float16 leaves are converted inside the autograd
+    function and get the gradient of the packed fp32 run, in their own layout and dtype; a backward after a forward
+    that did not write the maps raises."""
+    from splatco_amd.losses import _L1Ssim, l1_ssim
+    from splatco_amd.metrics import ssim_value
+    from splatco_amd.multiview import pair_similarity
+    d = R.ssim_inputs("noise")
+    x, y, up = d["x"].to(DEV), d["y"].to(DEV), d["up"]
+    l1, s, dx = _l1_ssim_run(l1_ssim, x, y, up)
+    bits = lambda a, b: a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
+    with torch.no_grad():
+        l1n, sn = l1_ssim(x, y)
+    assert bits(sn, s) and bits(l1n, l1)
+    assert bits(ssim_value(x, y), s) and bits(pair_similarity(x, y), s)
+    big = torch.full((3, 40, 48), 7.0, device=DEV)
+    big[:, 3:36, 5:42] = x
+    big.requires_grad_(True)
+    crop = big[:, 3:36, 5:42]
+    assert not crop.is_contiguous() and crop.shape == x.shape
+    l1c, sc = l1_ssim(crop, y)
+    R._ssim_loss(l1c, sc, up).backward()
+    assert bits(l1c.detach(), l1) and bits(sc.detach(), s) and bits(big.grad[:, 3:36, 5:42].contiguous(), dx)
+    outside = big.grad.clone()
+    outside[:, 3:36, 5:42] = 0
+    assert float(big.grad.abs().sum()) > 0 and float(outside.abs().max()) == 0
+    for dtype in (torch.float64, torch.float16):
+        leaf = x.to(dtype).requires_grad_(True)
+        lo, so = l1_ssim(leaf, y)
+        R._ssim_loss(lo, so, up).backward()
+        l1f, sf, dxf = _l1_ssim_run(l1_ssim, leaf.detach().float(), y, up)
+        assert lo.dtype == so.dtype == torch.float32 and bits(lo.detach(), l1f) and bits(so.detach(), sf)
+        assert leaf.grad.dtype == dtype and torch.equal(leaf.grad, dxf.to(dtype))
+        if dtype == torch.float64:
+            assert bits(so.detach(), s)
+    gt = y.clone().requires_grad_(True)                              # the graph reaches the op through y only: no maps
+    l1y, _ = _L1Ssim.apply(x, gt)
+    with pytest.raises(RuntimeError, match="without the derivative maps"):
+        l1y.backward()
+
+
+def test_l1_ssim_wrapper_refuses_a_mismatched_ground_truth(monkeypatch):
+    """losses.l1_ssim hands the kernel gt_image as a bare pointer with image's extents.  A gt_image of another shape or
+    on another device is a ValueError naming both, and one that requires grad goes to the framework chain and gets its
+    gradient -- all before any launch: the forward entry is replaced by one that fails the test."""
+    from splatco_amd import _C
+    from splatco_amd.losses import l1_loss, l1_ssim, ssim
+    d = R.ssim_inputs("noise")
+    x, y = d["x"].to(DEV), d["y"].to(DEV)
+    launched = []
+    monkeypatch.setattr(_C.lib, "scr_l1_ssim_forward", lambda *a: launched.append(a) or pytest.fail("the kernel was launched"))
+    cases = {"another H": y[:, :-1], "another C": y[:2], "on the CPU": d["y"]}
+    if torch.cuda.device_count() > 1:
+        cases["on another GPU"] = d["y"].to("cuda:1")
+    for what, gt in cases.items():
+        for image in (x, x.clone().requires_grad_(True)):
+            with pytest.raises(ValueError) as e:
+                l1_ssim(image, gt)
+            msg = str(e.value)
+            assert str(tuple(x.shape)) in msg and str(tuple(gt.shape)) in msg and str(x.device) in msg and str(gt.device) in msg, (what, msg)
+    a, gt = x.clone().requires_grad_(True), y.clone().requires_grad_(True)
+    l1, s = l1_ssim(a, gt)
+    (0.8 * l1 + 0.2 * (1.0 - s)).backward()
+    a2, gt2 = x.clone().requires_grad_(True), y.clone().requires_grad_(True)
+    (0.8 * l1_loss(a2, gt2) + 0.2 * (1.0 - ssim(a2, gt2))).backward()
+    assert gt.grad is not None and float(gt.grad.abs().max()) > 0
+    assert torch.equal(gt.grad, gt2.grad) and torch.equal(a.grad, a2.grad)
+    assert not launched
+
+
+@pytest.mark.parametrize("P", R.SREG_P)
+def test_scaling_reg_against_float64(P):
+    """scaling_reg_partial / _finish / _backward_kernel (2048 rows per workgroup, 256 threads, the finish workgroup
+    striding by 1024 partials): one row, around a wave-set of 256 and a workgroup of 2048 rows, and 1024 / 1025
+    partials.  The first rows hold one, two and three zeros (where torch.prod's backward takes its own path), a
+    negative entry and (1e-20, 1e-20, 1) (a subnormal product).
+    Value: within 2^-23 of the float64 mean of the binary32 products (the order the kernel documents) + 1e-12.
+    Gradient: d s[r,0] = w (b c) with w = fl(g fl(1/P)), four roundings -- 1/P, g/P, b c, their product -- each 2^-24:
+    (1 + 2^-24)^4 - 1 < 4.5 * 2^-24 of float64 autograd of prod(dim=1).mean(), + 2^-126 where the result is subnormal;
+    the rows with a zero get exactly the product of the other two entries times w."""
+    from splatco_amd.losses import scaling_reg
+    s = R.sreg_inputs(P)
+    rep = Report("sreg", f"P={P}")
+    g = float(torch.tensor(0.37, dtype=torch.float32))               # the upstream gradient as the kernel sees it
+    exact = float(((s[:, 0] * s[:, 1]) * s[:, 2]).double().mean())
+    s64 = s.double().requires_grad_(True)
+    (g * s64.prod(dim=1).mean()).backward()
+    runs = []
+    for _ in range(2):
+        a = s.to(DEV).clone().requires_grad_(True)
+        v = scaling_reg(a)
+        (v * 0.37).backward()
+        runs.append((v.detach().cpu(), a.grad.cpu()))
+    (v, ds), (v2, ds2) = runs
+    assert v.dtype == torch.float32 and ds.dtype == torch.float32 and ds.shape == (P, 3)
+    rep.within("value", abs(float(v.double()) - exact), 2.0 ** -23 * abs(exact) + 1e-12)
+    over = ((ds.double() - s64.grad).abs() - (4.5 * 2.0 ** -24 * s64.grad.abs() + 2.0 ** -126)).max()
+    rep.within("d scaling (excess)", float(over), 0.0)
+    k = min(P, R.SREG_ZERO_ROWS)
+    w = torch.tensor(0.37, dtype=torch.float32) * torch.tensor(1.0 / P, dtype=torch.float64).float()
+    z = s[:k]
+    want = torch.stack([w * (z[:, 1] * z[:, 2]), w * (z[:, 0] * z[:, 2]), w * (z[:, 0] * z[:, 1])], dim=1)
+    rep.require(torch.equal(ds[:k], want) and int((want != 0).sum()) == 1, "zero rows exact")
+    rep.require(bool(torch.isfinite(v)) and bool(torch.isfinite(ds).all()), "finite")
+    rep.require(torch.equal(v, v2) and torch.equal(ds, ds2), "bit-reproducible")
+    rep.finish()
+
+
+@pytest.mark.parametrize("n", R.PAIR_N)
+def test_pair_l1_at_workgroup_edges(n):
+    """pair_l1_partial / _backward_kernel and the finish kernel it shares with scaling_reg: one element, around the 4096
+    elements of a workgroup, and 1024 / 1025 partials.  The assertions of test_fused_pair_l1_matches_the_reference_ops:
+    the value within 2^-23 of the double mean of the binary32 residuals and no further from it than the framework's,
+    the gradients with the framework's signs (sign(0) = 0; every 53rd residual is at or next to zero) and within 2^-22."""
+    from splatco_amd.losses import l1_loss, pair_l1
+    a0, b0, r1, r2 = R.pair_inputs(n)
+    rep = Report("pair_l1", f"n={n}")
+    exact = float(((r1 - r2) - (a0 - b0)).abs().double().mean())
+    a0, b0, r1, r2 = (t.to(DEV) for t in (a0, b0, r1, r2))
+    for need in ((True, True), (True, False), (False, True)):
+        tag = " d" + "".join(str(i + 1) for i in range(2) if need[i])
+        outs = []
+        for fused in (True, True, False):
+            a, b = a0.clone().requires_grad_(need[0]), b0.clone().requires_grad_(need[1])
+            loss = pair_l1(a, b, r1, r2) if fused else l1_loss(r1 - r2, a - b)
+            (loss * 0.37).backward()
+            outs.append((loss.detach(), a.grad, b.grad))
+        (lf, af, bf), (lf2, af2, bf2), (lt, at, bt) = outs
+        e, e_t = abs(float(lf.double()) - exact), abs(float(lt.double()) - exact)
+        rep.within("value" + tag, e, 2.0 ** -23 * exact + 1e-12)
+        rep.within("value vs torch's" + tag, e, e_t + 2.0 ** -24 * exact + 1e-12)
+        ok = lf.dtype == torch.float32 and torch.equal(lf, lf2)
+        for got, got2, want, needed in ((af, af2, at, need[0]), (bf, bf2, bt, need[1])):
+            ok = ok and (got is None) == (not needed) and (want is None) == (not needed)
+            if needed:
+                ok = ok and torch.equal(got, got2)
+                rep.require(torch.equal(got.sign(), want.sign()) and torch.allclose(got, want, rtol=2.0 ** -22, atol=0),
+                            "gradient" + tag + (" (gen1)" if got is af else " (gen2)"))
+        rep.require(bool(ok), "bit-reproducible" + tag)
     rep.finish()
