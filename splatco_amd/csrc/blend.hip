@@ -182,12 +182,48 @@ __device__ __forceinline__ int blend_tile(int slot, int tiles, const uint32_t* _
 }
 
 // ------------------------------------------------------------------ forward
+// The forward's per-pixel update of one splat, run under a lane mask: C += colour * w, (AUX: D += z * w,) T = Tn, last = j in
+// the lanes of `live`, nothing in the others -- what a select per value did (common.h sel(): 4.3 cycles each against 2.3 for
+// a plain op) costs two SALU writes of EXEC, which go to the scalar port.  A lane that is masked never reads the colour, so
+// a colour that is not finite (SAFE) cannot reach a pixel its splat does not contribute to: one block for both instantiations.
+// EXEC IS RESTORED TO ALL ONES, not to a saved value: right only because the forward kernel is a one-wave workgroup whose
+// control flow around the call is wave-uniform (lanes outside the image stay active and sit in `done`), so EXEC is full
+// there.  Nothing but the masked VALU ops may stand between the two EXEC writes: one asm statement, no DPP / v_readlane
+// near it (they read EXEC-dependent lanes and have wait states after an EXEC write).
+template <bool AUX>
+__device__ __forceinline__ void masked_blend(unsigned long long live, float w, float cr, float cg, float cb, float z, float Tn,
+                                             uint32_t j, float& C0, float& C1, float& C2, float& D, float& T, uint32_t& last) {
+    if constexpr (AUX)
+        asm volatile("s_mov_b64 exec, %6\n\t"
+                     "v_fmac_f32_e32 %0, %7, %11\n\t"
+                     "v_fmac_f32_e32 %1, %8, %11\n\t"
+                     "v_fmac_f32_e32 %2, %9, %11\n\t"
+                     "v_fmac_f32_e32 %3, %10, %11\n\t"
+                     "v_mov_b32_e32 %4, %12\n\t"
+                     "v_mov_b32_e32 %5, %13\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(C0), "+v"(C1), "+v"(C2), "+v"(D), "+v"(T), "+v"(last)
+                     : "s"(live), "v"(cr), "v"(cg), "v"(cb), "v"(z), "v"(w), "v"(Tn), "v"(j));
+    else
+        asm volatile("s_mov_b64 exec, %5\n\t"
+                     "v_fmac_f32_e32 %0, %6, %9\n\t"
+                     "v_fmac_f32_e32 %1, %7, %9\n\t"
+                     "v_fmac_f32_e32 %2, %8, %9\n\t"
+                     "v_mov_b32_e32 %3, %10\n\t"
+                     "v_mov_b32_e32 %4, %11\n\t"
+                     "s_mov_b64 exec, -1"
+                     : "+v"(C0), "+v"(C1), "+v"(C2), "+v"(T), "+v"(last)
+                     : "s"(live), "v"(cr), "v"(cg), "v"(cb), "v"(w), "v"(Tn), "v"(j));
+}
+
 constexpr int FCHUNK = 64;  // list entries examined per round (one per lane)
 
 // SAFE: some visible Gaussian of this call carries a colour that is not finite (NaN / Inf input; preprocess_kernel raised
 // SCR_PLAN_NONFINITE_COLOUR and the host picked this instantiation).  Such a colour must reach only the pixels its splat
 // contributes to, as it does where non-contributing splats are SKIPPED; blended with alpha 0 it would turn 0 * colour into
-// NaN for every pixel of every quadrant that stages the record.  The SAFE instantiation selects the colour sums instead.
+// NaN for every pixel of every quadrant that stages the record.  The forward's update is masked per lane (masked_blend): a
+// lane the splat does not contribute to never reads the colour, so its two instantiations are the same code; the
+// backward's SAFE instantiation selects (splat_pixel_grad).
 // AUX: the depth map sum_i w_i z_i (w_i = alpha_i T_i over the contributors of the colour image, z_i = the view-space depth
 // of the splat record) and the accumulated opacity sum_i w_i = 1 - final T leave in the same pass: a sixth staged field
 // group carries z, one more accumulator per pixel, two more stores.  The background adds nothing to either map, and
@@ -243,7 +279,7 @@ blend_forward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict
             if (AUX) r2y = rec[3 * (size_t)id + 2].y;      // the view-space depth
         }
     };
-    // slots past a chunk's count are blended with alpha 0: they must hold finite numbers
+    // slots past a chunk's count are evaluated with the rest of their group and masked: they must hold finite numbers
     for (int i = lane; i < NF * (FCHUNK / 2); i += WAVE) (&sp[0][0])[i] = make_float4(0, 0, 0, 0);
     uint32_t m0, id0;
     load_mask_id(0, m0, id0);
@@ -293,12 +329,14 @@ blend_forward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict
                 power[h] = __builtin_elementwise_fma(dx, __builtin_elementwise_fma(A, dx, B * dy), (Cq * dy) * dy);
                 al[h] = o * v2f{fast_exp(power[h].x), fast_exp(power[h].y)};
             }
-            float alpha[NS], pw[NS];
+            float alpha[NS], pw[NS], om[NS];
 #pragma unroll
             for (int h = 0; h < NP; ++h) {
                 alpha[2 * h] = vmin(c099, al[h].x); alpha[2 * h + 1] = vmin(c099, al[h].y);
                 pw[2 * h] = power[h].x; pw[2 * h + 1] = power[h].y;
             }
+#pragma unroll
+            for (int u = 0; u < NS; ++u) om[u] = 1.0f - alpha[u];     // off the T chain: ready before the sequential updates
             // lane masks (SGPR pairs): which pixels does splat u touch
             unsigned long long hit[NS], anyh = 0ull;
 #pragma unroll
@@ -321,31 +359,20 @@ blend_forward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restrict
                 const float cr = (u & 1) ? p3[h].y : p3[h].x, cg = (u & 1) ? p3[h].w : p3[h].z;
                 const float cb = (u & 1) ? p4[h].y : p4[h].x, cj = (u & 1) ? p4[h].w : p4[h].z;
                 // A pixel the splat does not touch, a finished pixel, and the pixel this very splat would finish (the
-                // reference tests T (1 - alpha) < 1e-4 BEFORE blending and drops the splat) all blend it with alpha 0,
-                // which leaves T and C bit-for-bit unchanged (T * (1 - 0), fma(c, 0 * T, C)): ONE select on alpha does
-                // the work of three (alpha, the weight, the new T) -- selects issue at half the rate of plain fp32.
-                // The stop test runs on the unselected alpha and is masked afterwards; T never drops below 1e-4 (the
-                // update that would do so is the stop).
+                // reference tests T (1 - alpha) < 1e-4 BEFORE blending and drops the splat) keep T, C and last as they are:
+                // the update runs under the lane mask `live` (masked_blend), so those lanes are simply not written.  The
+                // product T (1 - alpha) is formed once: it is the stop test's operand AND the new T of the live lanes;
+                // T never drops below 1e-4 (the update that would do so is the stop).
                 const unsigned long long hm = hit[u] & ~done;
-                const unsigned long long stop = lanes(T * (1.0f - alpha[u]) < 0.0001f) & hm;
+                const float Tn = T * om[u];
+                const unsigned long long stop = lanes(Tn < 0.0001f) & hm;
                 done |= stop;
                 const unsigned long long live = hm & ~stop;
                 SCR_COUNT(1, __builtin_popcountll(live));
                 SCR_COUNT_SUB(live);
-                const float a = sel(live, alpha[u], 0.0f);
-                const float w = a * T;
-                if (SAFE) {     // 0 * colour is not 0 for a colour that is not finite
-                    C0 = sel(live, __builtin_fmaf(cr, w, C0), C0);
-                    C1 = sel(live, __builtin_fmaf(cg, w, C1), C1);
-                    C2 = sel(live, __builtin_fmaf(cb, w, C2), C2);
-                } else {
-                    C0 = __builtin_fmaf(cr, w, C0);
-                    C1 = __builtin_fmaf(cg, w, C1);
-                    C2 = __builtin_fmaf(cb, w, C2);
-                }
-                if (AUX) D = __builtin_fmaf((u & 1) ? p5[h].y : p5[h].x, w, D);     // w = 0 where the splat takes no part; z is finite
-                T = T * (1.0f - a);
-                last = sel(live, __float_as_uint(cj), last);
+                const float w = alpha[u] * T;
+                masked_blend<AUX>(live, w, cr, cg, cb, AUX ? ((u & 1) ? p5[h].y : p5[h].x) : 0.0f, Tn, __float_as_uint(cj),
+                                  C0, C1, C2, D, T, last);
             }
         };
         int k = 0;
