@@ -36,6 +36,8 @@ typedef float v2f __attribute__((ext_vector_type(2)));  // two fp32 lanes of a p
 //   backward: [8] staged pairs  [9] lanes that contribute (alpha >= 1/255, power <= 0, not behind the pixel's last contributor)
 //             [10] lanes behind their pixel's last contributor  [11] lanes inside the alpha >= 1/255 ellipse, whatever the order
 //             [12] pairs in groups whose reduction was skipped (no lane hit)  [13] empty slots of partial groups
+//             [16] (wave, round) pairs with staged entries  [17] those in which no pixel's last contributor falls into the
+//             round (the cut-off j < last is the same mask for every entry)  [18] staged pairs of ALL rounds of that kind
 //   4x4-pixel sub-blocks (what a finer mask could pack, four sub-blocks per wave, each walking its own list):
 //             [4] / [14] (pair, sub-block) combinations with a lane at work, forward / backward;
 //             [5] / [15] sum over waves of the LONGEST of the wave's four sub-block lists (the rounds such a wave would take
@@ -66,12 +68,13 @@ __device__ __forceinline__ void count_sub_blocks(unsigned long long m, unsigned 
     } while (0)
 #endif
 #ifdef SCR_BLEND_COUNT
-__device__ unsigned long long g_blend_counters[16];
+constexpr int SCR_NCOUNT = 20;
+__device__ unsigned long long g_blend_counters[SCR_NCOUNT];
 #define SCR_COUNT(i, v) (cnt_[(i)] += (unsigned long long)(v))
-#define SCR_COUNT_DECL unsigned long long cnt_[16] = {}, sub_[4] = {}, subc_[4] = {}
+#define SCR_COUNT_DECL unsigned long long cnt_[SCR_NCOUNT] = {}, sub_[4] = {}, subc_[4] = {}
 #define SCR_COUNT_FLUSH(lane)                                                        \
     if ((lane) == 0)                                                                 \
-        for (int q_ = 0; q_ < 16; ++q_)                                              \
+        for (int q_ = 0; q_ < SCR_NCOUNT; ++q_)                                              \
             if (cnt_[q_]) atomicAdd(&g_blend_counters[q_], cnt_[q_])
 #else
 #define SCR_COUNT(i, v) ((void)0)
@@ -439,8 +442,29 @@ __device__ __forceinline__ void column_fold(float& s0, float& s1, float& s2, flo
                  : "+v"(s0), "+v"(s1), "+v"(s2)
                  : "v"(t0), "v"(t1), "v"(t2));
 }
-constexpr int TCS = WAVE + 4;   // words per column of a wave's transposition block (the four extra words keep the two
-                                // columns of a 16-lane row on different banks in the ds_read_b128 above)
+// SCR_BWD_ITEMS (developer A/B only: tools/build_variant.sh NAME blend.hip -DSCR_BWD_ITEMS=<bits>; the product builds with all
+// of them): the per-lane / per-round facts of the backward kernel that profiles/r15_blend_backward.txt measures one by one.
+//   2 = the list position read per reducing lane    4 = the cross-wave combine in one batch
+//   8 = the transposition block laid out for the ds_read_b128 lane groups
+// None of them changes a value.  (Bit 1 was the contributor cut-off decided once per round: measured and dropped, same file.)
+#ifndef SCR_BWD_ITEMS
+#define SCR_BWD_ITEMS 14
+#endif
+constexpr bool BWD_LANE_POS = (SCR_BWD_ITEMS & 2) != 0, BWD_BATCH_COMBINE = (SCR_BWD_ITEMS & 4) != 0,
+               BWD_TR_SPLIT = (SCR_BWD_ITEMS & 8) != 0;
+
+// A wave's transposition block: eight columns of 64 words.  gfx950 serves a ds_read_b128 in four groups of 16 lanes that are
+// NOT contiguous -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same two sets + 32 -- one LDS cycle each when the 16
+// lanes' 16-byte slots cover the 64 banks.  Lane (column c, pixel column x) reads words base(c) + 8 x .. + 7 in two reads:
+// a group holds x = 0..3 of one even and one odd column and x = 4..7 of the other even and the other odd one, so the even
+// columns may share their slots (bases = 0 mod 64 words) and the odd ones must sit one slot off (bases = 4 mod 64).  The even
+// columns lie back to back, the odd ones behind them, four words on: 516 words, 4 LDS cycles per read.  (A uniform stride of
+// 68 words -- what contiguous 16-lane groups would want -- puts columns 0 and 2, and 1 and 3, two slots apart: both reads
+// two-way, 8 cycles.)  The stores (ds_write_b32, 32-lane halves, 32 banks) write 64 consecutive words per column: conflict-free
+// in either layout.
+constexpr int TCS = WAVE + 4;       // the uniform column stride (SCR_BWD_ITEMS without 8)
+constexpr int TR_WORDS = BWD_TR_SPLIT ? 8 * WAVE + 4 : 8 * TCS;
+__device__ __forceinline__ constexpr int tr_col(int c) { return BWD_TR_SPLIT ? WAVE * (c >> 1) + (c & 1) * (4 * WAVE + 4) : c * TCS; }
 
 // Per-pixel gradient terms of one splat (back-to-front recurrences).  Not decision bearing, so the
 // compiler may contract mul+add pairs here (fewer VALU issues); the tolerance is the gradient bar of
@@ -514,13 +538,64 @@ __device__ __forceinline__ void store16_dword_aligned(void* p, float4 v) {
     asm volatile("global_store_dwordx4 %0, %1, off" : : "v"(p), "v"(q) : "memory");
 }
 
+// The cross-wave combine's four adds r += x_w, each in the lanes of its mask c_w only, in the order w = 0, 1, 2, 3: the parts
+// of all four waves are loaded in one batch (one wait), and a part that its wave did not write this round holds stale bits
+// -- loaded, but never an operand in a lane whose condition is false (masked_blend's pattern: SALU writes of EXEC around
+// plain adds instead of a branch, or a select, per wave).  The masks come from ballots taken inside the caller's divergent
+// branch, so they lie within EXEC as it stands there; EXEC IS RESTORED TO THAT VALUE, not to all ones.  Only VALU adds stand
+// between the EXEC writes.
+__device__ __forceinline__ void masked_add4(float4& r, const float4 (&x)[4], const unsigned long long (&c)[4]) {
+    unsigned long long keep;
+    asm volatile("s_mov_b64 %4, exec\n\t"
+                 "s_mov_b64 exec, %5\n\t"
+                 "v_add_f32_e32 %0, %0, %9\n\t"
+                 "v_add_f32_e32 %1, %1, %10\n\t"
+                 "v_add_f32_e32 %2, %2, %11\n\t"
+                 "v_add_f32_e32 %3, %3, %12\n\t"
+                 "s_mov_b64 exec, %6\n\t"
+                 "v_add_f32_e32 %0, %0, %13\n\t"
+                 "v_add_f32_e32 %1, %1, %14\n\t"
+                 "v_add_f32_e32 %2, %2, %15\n\t"
+                 "v_add_f32_e32 %3, %3, %16\n\t"
+                 "s_mov_b64 exec, %7\n\t"
+                 "v_add_f32_e32 %0, %0, %17\n\t"
+                 "v_add_f32_e32 %1, %1, %18\n\t"
+                 "v_add_f32_e32 %2, %2, %19\n\t"
+                 "v_add_f32_e32 %3, %3, %20\n\t"
+                 "s_mov_b64 exec, %8\n\t"
+                 "v_add_f32_e32 %0, %0, %21\n\t"
+                 "v_add_f32_e32 %1, %1, %22\n\t"
+                 "v_add_f32_e32 %2, %2, %23\n\t"
+                 "v_add_f32_e32 %3, %3, %24\n\t"
+                 "s_mov_b64 exec, %4"
+                 : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w), "=&s"(keep)
+                 : "s"(c[0]), "s"(c[1]), "s"(c[2]), "s"(c[3]),
+                   "v"(x[0].x), "v"(x[0].y), "v"(x[0].z), "v"(x[0].w), "v"(x[1].x), "v"(x[1].y), "v"(x[1].z), "v"(x[1].w),
+                   "v"(x[2].x), "v"(x[2].y), "v"(x[2].z), "v"(x[2].w), "v"(x[3].x), "v"(x[3].y), "v"(x[3].z), "v"(x[3].w));
+}
+__device__ __forceinline__ void masked_add4(float& r, const float (&x)[4], const unsigned long long (&c)[4]) {
+    unsigned long long keep;
+    asm volatile("s_mov_b64 %1, exec\n\t"
+                 "s_mov_b64 exec, %2\n\t"
+                 "v_add_f32_e32 %0, %0, %6\n\t"
+                 "s_mov_b64 exec, %3\n\t"
+                 "v_add_f32_e32 %0, %0, %7\n\t"
+                 "s_mov_b64 exec, %4\n\t"
+                 "v_add_f32_e32 %0, %0, %8\n\t"
+                 "s_mov_b64 exec, %5\n\t"
+                 "v_add_f32_e32 %0, %0, %9\n\t"
+                 "s_mov_b64 exec, %1"
+                 : "+v"(r), "=&s"(keep)
+                 : "s"(c[0]), "s"(c[1]), "s"(c[2]), "s"(c[3]), "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]));
+}
+
 // ------------------------------------------------------------------ backward
 // what a lane keeps of the third part of a gathered splat record: blue, and with AUX the depth.  (A member that exists only
 // with AUX: a plain variable that the colour-only instantiation never reads still reorders its register moves.)
 template <bool AUX> struct RecTail { float x; };
 template <> struct RecTail<true> { float x, z; };
 constexpr int BCH = 64;  // list entries per round: one per lane of each wave
-constexpr int BWD_MIN_WAVES = 4;   // 128 VGPRs, 39.3 KB of LDS: four workgroups per CU; no spills
+constexpr int BWD_MIN_WAVES = 4;   // 127 VGPRs, 38.8 KB of LDS: four workgroups per CU; no spills
 constexpr int ACC_BUFS = 2;        // per-round sums double-buffered by round parity (one barrier per round)
 
 // AUX (gradients of the depth and opacity maps, see splat_pixel_grad): the per-splat sum  sum_pixels (alpha T) dL/ddepth  is
@@ -528,7 +603,7 @@ constexpr int ACC_BUFS = 2;        // per-round sums double-buffered by round pa
 // otherwise, through the same column_fold (it comes out in the odd banks of the colour columns), takes one more LDS slot
 // per (wave, position), is added over the waves in the same fixed order by wave 3 -- idle in the colour-only combine -- and
 // goes to a float stream of its own at the record's Gaussian-major index (grad_z).  The opacity map's "colour" is the
-// constant 1: no sum of its own.  2 KB more LDS (41.3 KB) leave three workgroups per CU; the instantiation is compiled
+// constant 1: no sum of its own.  2 KB more LDS (40.8 KB) leave three workgroups per CU; the instantiation is compiled
 // for that occupancy.
 constexpr int BWD_MIN_WAVES_AUX = 3;
 template <bool SAFE, bool AUX>       // see blend_forward_kernel / splat_pixel_grad
@@ -553,7 +628,7 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
     __shared__ float4 accA[ACC_BUFS][4][BCH], accB[ACC_BUFS][4][BCH];
     __shared__ float accC[ACC_BUFS][4][BCH];
     __shared__ float accD[ACC_BUFS][4][BCH];     // AUX: sum (alpha T) dL/ddepth per position (unused, so not allocated, without)
-    __shared__ __attribute__((aligned(16))) float tr[4][8 * TCS];    // the waves' transposition blocks (column_fold)
+    __shared__ __attribute__((aligned(16))) float tr[4][TR_WORDS];   // the waves' transposition blocks (tr_col, column_fold)
     __shared__ uint32_t wave_max[4];
     const int t = blend_tile((int)blockIdx.x, tiles, order, total);
     if (t < 0) return;
@@ -604,7 +679,7 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
     }
     const float xw = rcol < 4 ? (float)rx : 0.0f;
     float* const trw = &tr[wave][0];
-    const float* const trr = trw + rcol * TCS + 8 * rx;
+    const float* const trr = trw + tr_col(rcol) + 8 * rx;
     // where the lane's three sums go (lanes 0 and 4 of every column store): per sum the address of entry 0 in parity 0 and
     // the entry stride, in bytes -- (M0, My, Myy) from a Y column's even bank, (Mx, Mxx, Mxy) from its odd one, (c0, c1, c2)
     // from a colour column's even bank
@@ -612,9 +687,11 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
     const bool rstore = (lane & 3) == 0 && (rcol < 4 || ((lane >> 2) & 1) == 0);
     const bool rstore_z = AUX && (lane & 3) == 0 && rcol >= 4 && ((lane >> 2) & 1) == 1;     // a colour column's odd bank
     const int rcu = rcol & 3;                                    // the column's splat of the group
-    // (lane masks in SGPR pairs: the list position of the column's splat is selected from the four the group's record reads
-    // broadcast anyway -- an LDS read of its own would be a second exposed round trip per group)
-    const unsigned long long rcu1 = lanes(rcu == 1), rcu2 = lanes(rcu == 2), rcu3 = lanes(rcu == 3);
+    // The list position of the column's splat sits in the staging block, in the slot the group's record reads broadcast:
+    // the lane reads its own (one ds_read_b32 with a per-lane address, issued in the batch of the record reads, so it adds
+    // no round trip; three selects per group on lane masks of rcu otherwise)
+    const float4* const rpos = &st[wave][2][3 - rcu];           // + k: slot k + 3 - rcu
+    const unsigned long long rcu1 = lanes(rcu == 1), rcu2 = lanes(rcu == 2), rcu3 = lanes(rcu == 3);      // (!BWD_LANE_POS)
     char* const accA0 = (char*)&accA[0][wave][0];
     char* const accB0 = (char*)&accB[0][wave][0];
     char* const rdst0 = rkind == 0 ? accA0 : rkind == 1 ? accA0 + 4 : accB0 + 8;
@@ -749,6 +826,8 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
                 rc[u] = *(const float2*)&st[wave][2][k + 3 - u];
                 if (AUX) rz[u] = st[wave][2][k + 3 - u].z;
             }
+            uint32_t jpos = 0u;     // list position of the splat of this lane's column (a zero pad slot when TAIL cuts it)
+            if (BWD_LANE_POS) jpos = __float_as_uint(rpos[k].y);
             float Gs[4], al[4], om[4], Tu[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -799,8 +878,8 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
                 asm volatile("" ::: "memory");
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    trw[u * TCS + lane] = Y[u];
-                    trw[(4 + u) * TCS + lane] = Wt[u];
+                    trw[tr_col(u) + lane] = Y[u];
+                    trw[tr_col(4 + u) + lane] = Wt[u];
                 }
                 asm volatile("" ::: "memory");
                 const float4 va = *(const float4*)trr, vb = *(const float4*)(trr + 4);
@@ -836,19 +915,27 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
             }
             // column rcol & 3 is splat u of the group, entry k - u of the wave's list; every listed position is written
             if (rstore && (!TAIL || k - rcu >= 0)) {
-                const uint32_t jw = sel(rcu3, jj[3], sel(rcu2, jj[2], sel(rcu1, jj[1], jj[0])));
+                const uint32_t jw = BWD_LANE_POS ? jpos : sel(rcu3, jj[3], sel(rcu2, jj[2], sel(rcu1, jj[1], jj[0])));
                 *(float*)(rdst0 + par * PAR_A + jw * 16u) = s0;
                 *(float*)(rdst1 + par * PAR_A + jw * 16u) = s1;
                 *(float*)(rdst2 + par * rpar2 + jw * rstride2) = s2;
             }
             if (AUX && rstore_z && (!TAIL || k - rcu >= 0)) {
-                const uint32_t jw = sel(rcu3, jj[3], sel(rcu2, jj[2], sel(rcu1, jj[1], jj[0])));
+                const uint32_t jw = BWD_LANE_POS ? jpos : sel(rcu3, jj[3], sel(rcu2, jj[2], sel(rcu1, jj[1], jj[0])));
                 accD[par][wave][jw] = s0;
             }
         };
         int k = cnt - 1;
         for (; k >= 3; k -= 4) group(k, std::false_type{});
         if (k >= 0) group(k, std::true_type{});
+#ifdef SCR_BLEND_COUNT
+        {   // a round in which no pixel's last contributor falls: every lane takes all of its entries or none
+            const bool no_edge = ~(lanes(last_rel >= BCH) | lanes(last_rel <= 0)) == 0ull;
+            SCR_COUNT(16, cnt != 0);
+            SCR_COUNT(17, cnt != 0 && no_edge);
+            SCR_COUNT(18, no_edge ? cnt : 0);
+        }
+#endif
         SCR_COUNT_CHUNK_END(7);
         // ---- the wave's entries: moments about the quadrant's origin -> about the splat's centre, in the record layout
         // the combine below and preprocess_backward_kernel read: (sum Y dx, sum Y dy, sum Y dx^2, sum Y dx dy |
@@ -878,10 +965,24 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
                 return wave == 0 ? accA[par][w][lane] : wave == 1 ? accB[par][w][lane]
                                                                   : make_float4(accC[par][w][lane], 0.0f, 0.0f, 0.0f);
             };
+            if constexpr (BWD_BATCH_COMBINE) {
+                // which waves took part, as lane masks (ballots of the lanes inside this branch)
+                const unsigned long long took[4] = {lanes(((m_this >> 0) & 1u) && i < wmax0), lanes(((m_this >> 1) & 1u) && i < wmax1),
+                                                    lanes(((m_this >> 2) & 1u) && i < wmax2), lanes(((m_this >> 3) & 1u) && i < wmax3)};
+                if (wave == 2) {
+                    const float x[4] = {accC[par][0][lane], accC[par][1][lane], accC[par][2][lane], accC[par][3][lane]};
+                    masked_add4(r.x, x, took);
+                } else {
+                    const float4* const p = wave == 0 ? &accA[par][0][lane] : &accB[par][0][lane];
+                    const float4 x[4] = {p[0], p[BCH], p[2 * BCH], p[3 * BCH]};
+                    masked_add4(r, x, took);
+                }
+            } else {
             if (((m_this >> 0) & 1u) && i < wmax0) { const float4 x = part(0); r.x += x.x; r.y += x.y; r.z += x.z; r.w += x.w; }
             if (((m_this >> 1) & 1u) && i < wmax1) { const float4 x = part(1); r.x += x.x; r.y += x.y; r.z += x.z; r.w += x.w; }
             if (((m_this >> 2) & 1u) && i < wmax2) { const float4 x = part(2); r.x += x.x; r.y += x.y; r.z += x.z; r.w += x.w; }
             if (((m_this >> 3) & 1u) && i < wmax3) { const float4 x = part(3); r.x += x.x; r.y += x.y; r.z += x.z; r.w += x.w; }
+            }
             GradRec& gr = grad_rec[slot_this];
             if (wave == 0) store16_dword_aligned(&gr.a, r);
             else if (wave == 1) store16_dword_aligned(&gr.b, r);
@@ -893,10 +994,17 @@ blend_backward_kernel(int W, int H, int gx, int tiles, const uint32_t* __restric
         if (AUX && wave == 3 && base + lane < n && m_this != 0) {     // the depth sum of the same entries, same order
             const uint32_t i = base + lane;
             float r = 0.0f;
+            if constexpr (BWD_BATCH_COMBINE) {
+                const unsigned long long took[4] = {lanes(((m_this >> 0) & 1u) && i < wmax0), lanes(((m_this >> 1) & 1u) && i < wmax1),
+                                                    lanes(((m_this >> 2) & 1u) && i < wmax2), lanes(((m_this >> 3) & 1u) && i < wmax3)};
+                const float x[4] = {accD[par][0][lane], accD[par][1][lane], accD[par][2][lane], accD[par][3][lane]};
+                masked_add4(r, x, took);
+            } else {
             if (((m_this >> 0) & 1u) && i < wmax0) r += accD[par][0][lane];
             if (((m_this >> 1) & 1u) && i < wmax1) r += accD[par][1][lane];
             if (((m_this >> 2) & 1u) && i < wmax2) r += accD[par][2][lane];
             if (((m_this >> 3) & 1u) && i < wmax3) r += accD[par][3][lane];
+            }
             grad_z[slot_this] = r;
         }
     }
@@ -949,11 +1057,11 @@ void launch_blend_backward(const KSettings& ks, const GeomView& gv, const BinVie
 }  // namespace scr
 
 #ifdef SCR_BLEND_COUNT
-extern "C" int scr_tool_blend_counters(unsigned long long* out16, int reset) {
-    if (out16 && hipMemcpyFromSymbol(out16, HIP_SYMBOL(scr::g_blend_counters), 16 * 8) != hipSuccess) return 1;
+extern "C" int scr_tool_blend_counters(unsigned long long* out20, int reset) {
+    if (out20 && hipMemcpyFromSymbol(out20, HIP_SYMBOL(scr::g_blend_counters), scr::SCR_NCOUNT * 8) != hipSuccess) return 1;
     if (reset) {
-        unsigned long long z[16] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(scr::g_blend_counters), z, 16 * 8) != hipSuccess) return 1;
+        unsigned long long z[scr::SCR_NCOUNT] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(scr::g_blend_counters), z, scr::SCR_NCOUNT * 8) != hipSuccess) return 1;
     }
     return 0;
 }

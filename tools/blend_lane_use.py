@@ -17,9 +17,9 @@ from splatco_amd.rasterizer import GaussianRasterizationSettings, GaussianRaster
 from splatco_amd.synthetic import synthetic_camera, synthetic_gaussians
 
 
-def run(sigma_scale, P=1_000_000, W=1920, H=1080):
+def run(sigma_scale, P=1_000_000, W=1920, H=1080, seed=0):
     dev = torch.device("cuda:0")
-    cam, g = synthetic_camera(W, H), synthetic_gaussians(P, W, H, seed=0, sigma_scale=sigma_scale)
+    cam, g = synthetic_camera(W, H), synthetic_gaussians(P, W, H, seed=seed, sigma_scale=sigma_scale)
     tx, ty = math.tan(cam.FoVx * 0.5), math.tan(cam.FoVy * 0.5)
     rs = GaussianRasterizationSettings(H, W, tx, ty, torch.tensor(g["bg"], device=dev), 1.0, cam.world_view_transform.to(dev),
                                        cam.full_proj_transform.to(dev), 1, cam.camera_center.to(dev), False, False)
@@ -28,7 +28,7 @@ def run(sigma_scale, P=1_000_000, W=1920, H=1080):
     m2d = torch.zeros(P, 3, device=dev, requires_grad=True)
     fn = _C.lib.scr_tool_blend_counters
     fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_int], ctypes.c_int
-    buf = (ctypes.c_ulonglong * 16)()
+    buf = (ctypes.c_ulonglong * 20)()      # SCR_NCOUNT of blend.hip
     torch.cuda.synchronize()
     assert fn(buf, 1) == 0
     img, radii = GaussianRasterizer(rs)(means3D=m, means2D=m2d, opacities=o, colors_precomp=c, scales=s, rotations=r)
@@ -42,6 +42,7 @@ def run(sigma_scale, P=1_000_000, W=1920, H=1080):
     b_pairs, b_hit, b_past, b_geo, b_skip, b_tail = k[8], k[9], k[10], k[11], k[12], k[13]
     f_sub, f_submax, b_sub, b_submax = k[4], k[5], k[14], k[15]
     f_chunkmax, b_chunkmax = k[6], k[7]
+    b_rounds, b_rounds_uni, b_pairs_uni = k[16], k[17], k[18]
     lines = [f"scene: P = {P}, {W}x{H}, sigma_scale = {sigma_scale}: {I} (Gaussian, tile) instances, {int((radii > 0).sum())} visible",
              "forward  (blend_forward_kernel, one wave per 8x8 quadrant, 64 lanes per staged splat):",
              f"  staged (wave, splat) pairs            {f_pairs:>14,d}   = {f_pairs / max(I, 1):.2f} per instance (of 4 quadrants)",
@@ -64,6 +65,9 @@ def run(sigma_scale, P=1_000_000, W=1920, H=1080):
               f"  backward: (pair, sub-block) combinations at work {b_sub:>14,d} = {b_sub / max(4 * b_pairs, 1):.1%} of 4 per pair; "
               f"lanes at work inside them {b_hit / max(16 * b_sub, 1):.1%}; rounds if every wave walked its longest sub-block list: "
               f"{b_submax:,d} = {b_submax / max(b_pairs, 1):.2f} of today's; in step round by round (64 list entries): {b_chunkmax:,d} = {b_chunkmax / max(b_pairs, 1):.2f}"]
+    lines += ["backward rounds in which no pixel's last contributor falls (the cut-off is one lane mask for the whole round):",
+              f"  (wave, round) pairs with staged entries {b_rounds:>14,d}; of that kind {b_rounds_uni:>14,d} = {b_rounds_uni / max(b_rounds, 1):.1%}",
+              f"  staged (wave, splat) pairs inside them  {b_pairs_uni:>14,d} = {b_pairs_uni / max(b_pairs, 1):.1%} of the staged pairs"]
     return "\n".join(lines)
 
 
