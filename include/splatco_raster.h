@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SCR_ABI_VERSION 33
+#define SCR_ABI_VERSION 34
 #define SCR_TILE 16 /* 16x16-pixel tiles: part of the result contract (tile rects, ranges, sort keys) */
 
 /* The 12 fields of GaussianRasterizationSettings, same order (gaussian_renderer/__init__.py:145-158).
@@ -65,9 +65,10 @@ const char* scr_last_error(void);
 size_t scr_geom_bytes(int64_t P, int32_t image_height, int32_t image_width); /* per-Gaussian state + per-tile counters */
 size_t scr_binning_bytes(int64_t num_rendered, int64_t max_tile_instances);  /* per tile-instance lists */
 size_t scr_image_bytes(int32_t image_height, int32_t image_width);           /* final_T + n_contrib */
-size_t scr_backward_scratch_bytes(int64_t num_rendered);                     /* per-instance gradient records */
-size_t scr_backward_scratch_bytes_aux(int64_t num_rendered);                 /* the same + the per-instance depth sums of scr_backward_aux */
-size_t scr_backward_scratch_bytes_camera(int64_t num_rendered, int64_t P);   /* the same + one 128-byte row per 256 Gaussians (scr_backward_camera) */
+/* scr_backward's scratch: the per-instance gradient records; maps != 0 (a map gradient is given): + one float per instance
+ * (the depth sums); camera != 0 (a camera output is given): the records, those floats whatever `maps` says, and one
+ * 128-byte row per 256 Gaussians. */
+size_t scr_backward_scratch_bytes(int64_t num_rendered, int64_t P, int32_t maps, int32_t camera);
 
 /* ---- visible_filter: radii_out[P] int32 (> 0 <=> visible).  Either (scales, rotations) or cov3D_precomp. */
 int scr_visible_filter(int64_t P, const float* means3D, const float* scales, const float* rotations,
@@ -89,23 +90,8 @@ int scr_mark_visible(int64_t P, const float* means3D, const float* viewmatrix, u
  * SCR_PLAN_NONFINITE_COLOUR: a visible Gaussian carries a colour that is NaN or +-Inf.  The reference
  * SKIPS a splat at every pixel it does not contribute to, so such a colour reaches only the pixels the splat does
  * contribute to; the fast blend kernels carry non-contributing splats with alpha 0 (0 * NaN would spread), so calls
- * with this bit run the kernels' select-based instantiations and give the reference's result, NaN for NaN. */
-enum { SCR_PLAN_NONFINITE_COLOUR = 1,
-       SCR_PLAN_ANTIALIASED = 4,    /* the forward ran in the antialiased mode (scr_forward_plan_mode): the splat records carry
-                                     * opacity * h.  The backward's kernels take THIS bit from geom_buf too (see below). */
-       SCR_PLAN_LARGE_RECTS = 2 };  /* some Gaussian's tile rect has more than 32 tiles: scr_backward clears the gradient
-                                     * records of its further tiles before the blend backward fills in the ones it writes.
-                                     * The backward takes THIS bit from geom_buf (where the forward left it), not from its
-                                     * plan_flags argument: a stale argument cannot leave uninitialised records in the sums.
-                                     * SCR_PLAN_NONFINITE_COLOUR selects a kernel instantiation on the host and is taken
-                                     * from the argument (a wrong value there only changes how NaN colours spread); with
-                                     * settings->debug the argument is compared with geom_buf's word and a mismatch fails. */
-int scr_forward_plan(int64_t P, int32_t M, const float* means3D, const float* scales,
-                     const float* rotations, const float* cov3D_precomp, const float* opacities,
-                     const float* shs, const float* colors_precomp, const scr_settings* settings,
-                     void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream);
-
-/* ---- forward with a mode word (ABI 32).  mode = 0 IS scr_forward_plan; an unknown bit fails before anything is launched.
+ * with this bit run the kernels' select-based instantiations and give the reference's result, NaN for NaN.
+ * mode: 0 is the default; an unknown bit fails before anything is launched.
  * SCR_MODE_ANTIALIASED: the opacity compensation of Mip-Splatting (upstream 3DGS `antialiasing`, gsplat
  * rasterize_mode="antialiased").  The operator adds 0.3 px^2 to the diagonal of every projected covariance; in this mode a
  * splat's opacity is scaled so that its integrated opacity stays what it was before that dilation:
@@ -114,97 +100,76 @@ int scr_forward_plan(int64_t P, int32_t M, const float* means3D, const float* sc
  * in binary32, in this order, without contraction.  A negative or NaN ratio (rank-deficient covariance) falls on the floor,
  * h = 0.005.  Nothing else changes: radii, tile rects, tiles_touched, the culls, the sort and every other record field are
  * bit-identical to mode 0, and every later kernel reads the opacity from the record.  The call raises SCR_PLAN_ANTIALIASED
- * in the plan flags (plan_host[3] and geom_buf); scr_forward_run[_aux] take such a state as any other. */
+ * in the plan flags (plan_host[3] and geom_buf); scr_forward_run takes such a state as any other. */
 enum { SCR_MODE_ANTIALIASED = 1 };
-int scr_forward_plan_mode(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales,
-                          const float* rotations, const float* cov3D_precomp, const float* opacities,
-                          const float* shs, const float* colors_precomp, const scr_settings* settings,
-                          void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream);
+enum { SCR_PLAN_NONFINITE_COLOUR = 1,
+       SCR_PLAN_ANTIALIASED = 4,    /* the forward ran with SCR_MODE_ANTIALIASED: the splat records carry opacity * h.
+                                     * The backward's kernels take THIS bit from geom_buf too (see scr_backward). */
+       SCR_PLAN_LARGE_RECTS = 2 };  /* some Gaussian's tile rect has more than 32 tiles: scr_backward clears the gradient
+                                     * records of its further tiles before the blend backward fills in the ones it writes.
+                                     * The backward takes THIS bit from geom_buf (where the forward left it), not from its
+                                     * plan_flags argument: a stale argument cannot leave uninitialised records in the sums.
+                                     * SCR_PLAN_NONFINITE_COLOUR selects a kernel instantiation on the host and is taken
+                                     * from the argument (a wrong value there only changes how NaN colours spread); with
+                                     * settings->debug the argument is compared with geom_buf's word and a mismatch fails. */
+int scr_forward_plan(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales,
+                     const float* rotations, const float* cov3D_precomp, const float* opacities,
+                     const float* shs, const float* colors_precomp, const scr_settings* settings,
+                     void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream);
 
 /* ---- forward, phase 2: per-tile bucketing, depth sort, front-to-back blend.
  * out_color is [3, H, W] fp32.  geom_buf / binning_buf / image_buf must be kept for scr_backward.
  * Follows the mode of the plan phase that filled geom_buf (the records carry the compensated opacity); the
- * SCR_PLAN_ANTIALIASED bit of plan_flags is accepted and changes nothing here. */
-int scr_forward_run(int64_t P, int64_t num_rendered, int64_t max_tile_instances, int64_t plan_flags,
-                    const scr_settings* settings, void* geom_buf, void* binning_buf, void* image_buf, float* out_color,
-                    void* stream);
-
-/* ---- forward, phase 2, with the depth and opacity maps from the same pass (ABI 30).  out_depth / out_alpha are [H, W] fp32:
+ * SCR_PLAN_ANTIALIASED bit of plan_flags is accepted and changes nothing here.
+ * The depth and opacity maps come from the same pass.  Here and in scr_forward_plan_run, out_depth and out_alpha are both
+ * NULL (no maps) or both given; one alone fails before anything is launched.  They are [H, W] fp32:
  *   out_alpha = sum_i w_i,   out_depth = sum_i w_i z_i,   w_i = alpha_i T_i
  * over exactly the contributors of out_color (same hit test, same T (1 - alpha) < 1e-4 stop, same n_contrib); z_i is the
  * Gaussian's view-space depth ([x,y,z,1] * viewmatrix, third component -- the value of SCR_DBG_SPLAT_RECORDS[.][9]).  The
  * background adds nothing to either map and the depth is NOT normalised: the expected depth of a pixel is
  * out_depth / out_alpha where out_alpha > 0.  A colour that is not finite reaches neither map.  out_color, radii and the
- * saved buffers are bit-identical to scr_forward_run's. */
-int scr_forward_run_aux(int64_t P, int64_t num_rendered, int64_t max_tile_instances, int64_t plan_flags,
-                        const scr_settings* settings, void* geom_buf, void* binning_buf, void* image_buf, float* out_color,
-                        float* out_depth, float* out_alpha, void* stream);
+ * saved buffers are bit-identical with and without the maps. */
+int scr_forward_run(int64_t P, int64_t num_rendered, int64_t max_tile_instances, int64_t plan_flags,
+                    const scr_settings* settings, void* geom_buf, void* binning_buf, void* image_buf, float* out_color,
+                    float* out_depth, float* out_alpha, void* stream);
 
 /* ---- forward, both phases in one call when the caller's guess of the binning size was good enough.
  * Same as scr_forward_plan; then, if binning_buf is not NULL and binning_capacity_bytes >= scr_binning_bytes(I, max tile),
  * scr_forward_run on it without returning to the caller in between (the GPU otherwise idles for the caller's allocation and
  * second call: 20 us of a 1 ms step).  plan_host[4]: instances, largest tile, 1 if phase 2 ran (0: allocate and call
- * scr_forward_run), plan flags.  A training loop's instance count moves by a few per cent per step: last step's count plus slack. */
-int scr_forward_plan_run(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
+ * scr_forward_run), plan flags.  A training loop's instance count moves by a few per cent per step: last step's count plus slack.
+ * mode as in scr_forward_plan, the maps as in scr_forward_run. */
+int scr_forward_plan_run(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
                          const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
                          const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
-                         void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color, void* stream);
-/* the same with the depth and opacity maps (see scr_forward_run_aux) */
-int scr_forward_plan_run_aux(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
-                             const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
-                             const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
-                             void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
-                             float* out_depth, float* out_alpha, void* stream);
-/* the same with a mode word (ABI 32; see scr_forward_plan_mode).  out_depth and out_alpha both NULL: no maps
- * (scr_forward_plan_run); both given: scr_forward_plan_run_aux; one of them alone fails.  mode = 0 IS those two. */
-int scr_forward_plan_run_mode(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
-                              const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
-                              const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
-                              void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
-                              float* out_depth, float* out_alpha, void* stream);
+                         void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
+                         float* out_depth, float* out_alpha, void* stream);
 
-/* ---- backward.  dL_dcolor is [3,H,W].  Outputs (each may be NULL when its input was NULL):
+/* ---- backward of a loss on the colour image and the maps of scr_forward_run: every output is the gradient of the whole
+ * loss.  dL_dcolor is [3,H,W], always given (zeros when the image took no part).  dL_ddepth / dL_dalpha are [H, W]; either
+ * may be NULL (that map took no part in the loss), and both NULL selects the colour-only kernels, whether the forward wrote
+ * the maps or not.  The depth gradient reaches dL_dmeans3D through the view matrix, as the forward formed z.
+ * Outputs (each may be NULL when its input was NULL):
  * dL_dmeans3D[P,3], dL_dmeans2D[P,3] (d/d NDC position, z = 0: the gradient SplatCo reads back
  * at scene/gaussian_model.py:779), dL_dcolors[P,3], dL_dsh[P,M,3], dL_dopacity[P], dL_dscales[P,3],
  * dL_drotations[P,4], dL_dcov3D[P,6].  Every output element is written (zeros for culled Gaussians).
- * Deterministic: bit-identical results run to run (no floating-point atomics).  scratch: scr_backward_scratch_bytes
- * (one 36-byte gradient record per (Gaussian, tile) instance; the entries of a tile's list behind every pixel's last
- * contributor get none -- the tile's cut key in the image buffer, written by the backward, tells which).
+ * Deterministic: bit-identical results run to run (no floating-point atomics).
+ * scratch: scr_backward_scratch_bytes(num_rendered, P, a map gradient is given, a camera output is given): one 36-byte
+ * gradient record per (Gaussian, tile) instance (the entries of a tile's list behind every pixel's last contributor get
+ * none -- the tile's cut key in the image buffer, written by the backward, tells which); behind the records one float per
+ * instance for the maps, and behind those the camera sums' rows.
  * geom_buf and image_buf are WRITTEN (per-Gaussian record flags, per-tile cut keys): one backward at a time per forward
  * state; the forward's results in them are left intact, so the backward can be repeated.  plan_flags: plan_host[3].
- * Antialiased mode (ABI 32): the backward follows the SCR_PLAN_ANTIALIASED flag the forward left in geom_buf.  Then
+ * Antialiased mode: the backward follows the SCR_PLAN_ANTIALIASED flag the forward left in geom_buf.  Then
  * g = dL/d(opacity h) comes from the blend, dL_dopacity = g h, and where the clamp of h passed (det0 / det > 0.000025)
  * dL/dr = g o / (2 h) enters dL/da, dL/db, dL/dc of the 2-D covariance in front of the chain -- so it reaches dL_dmeans3D,
- * dL_dscales, dL_drotations, dL_dcov3D (and scr_backward_camera's sums) like every other term; on the floor nothing is added.
+ * dL_dscales, dL_drotations, dL_dcov3D (and the camera sums) like every other term; on the floor nothing is added.
  * The input opacity is not an argument of the backward: o is formed as the record's opacity divided by h, h recomputed from
  * the inputs as the forward did.  The bit of the plan_flags ARGUMENT only picks the kernel instantiation that can do this; it
  * then looks at geom_buf's flag itself.  A stale argument cannot give plausible wrong numbers: with the bit wrongly set the
  * results are the right ones; with the bit wrongly clear every gradient the kernel writes is NaN.  With settings->debug
- * the argument is compared with geom_buf's word and a mismatch fails. */
-int scr_backward(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_flags, const float* means3D, const float* scales,
-                 const float* rotations, const float* cov3D_precomp, const float* shs,
-                 const scr_settings* settings, const int32_t* radii, void* geom_buf,
-                 const void* binning_buf, void* image_buf, const float* dL_dcolor, void* scratch,
-                 float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
-                 float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                 void* stream);
-
-/* ---- backward of a loss on the colour image AND the maps of scr_forward_run_aux (ABI 30): every output is the gradient of
- * the whole loss.  dL_ddepth / dL_dalpha are [H, W]; either may be NULL (that map took no part in the loss), with both NULL
- * the call IS scr_backward.  dL_dcolor is always given (zeros when the image took no part).  The depth gradient reaches
- * dL_dmeans3D through the view matrix, as the forward formed z.  scratch: scr_backward_scratch_bytes_aux (the records and,
- * behind them, one float per instance).  Works on the saved buffers of either forward entry point; deterministic as
- * scr_backward is, and follows the antialiased flag in geom_buf as scr_backward does. */
-int scr_backward_aux(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_flags, const float* means3D, const float* scales,
-                     const float* rotations, const float* cov3D_precomp, const float* shs,
-                     const scr_settings* settings, const int32_t* radii, void* geom_buf,
-                     const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
-                     const float* dL_dalpha, void* scratch,
-                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
-                     float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                     void* stream);
-
-/* ---- backward with the camera's gradients (ABI 31).  scr_backward_aux plus three outputs in front of `stream`:
+ * the argument is compared with geom_buf's word and a mismatch fails.
+ * The camera's gradients, three outputs in front of `stream`:
  *   dL_dviewmatrix[16], dL_dprojmatrix[16]  in the layout of scr_settings' matrices (row-vector convention, X[4 c + j]),
  *   dL_dcampos[3]                           through the SH view direction; zeros with colors_precomp (shs NULL).
  * The two matrices are independent inputs, as the forward reads them: viewmatrix through the view-space mean (columns 0..2:
@@ -212,19 +177,18 @@ int scr_backward_aux(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_fl
  * mean (columns 0, 1, 3).  Columns the forward never reads get exact zeros.  Culled Gaussians add nothing; the sort, the
  * culls, the tile rects and the blend's thresholds are constants, and a clamped Jacobian (t.x / t.z or t.y / t.z outside
  * 1.3 tan fov) passes nothing to that component of the view-space mean, as in dL_dmeans3D.  Each of the three may be NULL
- * (not wanted); with all three NULL the call IS scr_backward_aux.  Every given output is written, with zeros when P == 0 or
- * num_rendered == 0.  The per-Gaussian outputs are bit-identical to scr_backward_aux's.  Deterministic: the sums over the
- * Gaussians are formed in a fixed order (per 256-Gaussian workgroup, then over the workgroups' rows by one more kernel),
- * without floating-point atomics.  scratch: scr_backward_scratch_bytes_camera(num_rendered, P).
- * Follows the antialiased flag in geom_buf as scr_backward does: the camera sums include the compensation's share. */
-int scr_backward_camera(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_flags, const float* means3D, const float* scales,
-                        const float* rotations, const float* cov3D_precomp, const float* shs,
-                        const scr_settings* settings, const int32_t* radii, void* geom_buf,
-                        const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
-                        const float* dL_dalpha, void* scratch,
-                        float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
-                        float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                        float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream);
+ * (not wanted); with all three NULL the kernels without the camera sums run.  Every given output is written, with zeros when
+ * P == 0 or num_rendered == 0.  The per-Gaussian outputs are bit-identical with and without the camera outputs.
+ * Deterministic: the sums over the Gaussians are formed in a fixed order (per 256-Gaussian workgroup, then over the
+ * workgroups' rows by one more kernel), without floating-point atomics; they include the compensation's share. */
+int scr_backward(int64_t P, int32_t M, int64_t num_rendered, int64_t plan_flags, const float* means3D, const float* scales,
+                 const float* rotations, const float* cov3D_precomp, const float* shs,
+                 const scr_settings* settings, const int32_t* radii, void* geom_buf,
+                 const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
+                 const float* dL_dalpha, void* scratch,
+                 float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
+                 float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                 float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream);
 
 /* ---- debug getters: copy the integer / float intermediates out of the opaque buffers (parity tests).
  * which: see SCR_DBG_*.  `out` is a device buffer of the stated element count. */

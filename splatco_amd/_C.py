@@ -17,9 +17,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPLATCO_RASTER_LIB", os.path.join(_HERE, "csrc", "libsplatco_raster.so"))
 
 PLAN_NONFINITE_COLOUR, PLAN_LARGE_RECTS, PLAN_ANTIALIASED = 1, 2, 4      # SCR_PLAN_*
-MODE_ANTIALIASED = 1                                # SCR_MODE_* (scr_forward_plan_mode / scr_forward_plan_run_mode)
+MODE_ANTIALIASED = 1                                # SCR_MODE_* (scr_forward_plan / scr_forward_plan_run)
 PROF_COUNT = 20
-ABI_VERSION = 33
+ABI_VERSION = 34
 FLIP_MAX_RADIUS = 16                                # SCR_FLIP_MAX_RADIUS
 
 (DBG_TILES_TOUCHED, DBG_POINT_OFFSETS, DBG_RANGES, DBG_POINT_LIST, DBG_N_CONTRIB, DBG_FINAL_T, DBG_SPLAT_RECORDS, DBG_QMASK,
@@ -61,21 +61,13 @@ SIGNATURES = [
     ("scr_geom_bytes", sz, i64, i32, i32),
     ("scr_binning_bytes", sz, i64, i64),
     ("scr_image_bytes", sz, i32, i32),
-    ("scr_backward_scratch_bytes", sz, i64),
-    ("scr_backward_scratch_bytes_aux", sz, i64),
-    ("scr_backward_scratch_bytes_camera", sz, i64, i64),
+    ("scr_backward_scratch_bytes", sz, i64, i64, i32, i32),
     ("scr_visible_filter", i32, i64, vp, vp, vp, vp, P(Settings), vp, vp),
     ("scr_mark_visible", i32, i64, vp, vp, vp, vp),
-    ("scr_forward_plan", i32, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp),
-    ("scr_forward_plan_mode", i32, i64, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp),
-    ("scr_forward_run", i32, i64, i64, i64, i64, P(Settings), *[vp] * 5),
-    ("scr_forward_run_aux", i32, i64, i64, i64, i64, P(Settings), *[vp] * 7),
-    ("scr_forward_plan_run", i32, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp, sz, vp, vp, vp),
-    ("scr_forward_plan_run_aux", i32, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp, sz, *[vp] * 5),
-    ("scr_forward_plan_run_mode", i32, i64, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp, sz, *[vp] * 5),
-    ("scr_backward", i32, i64, i32, i64, i64, *[vp] * 5, P(Settings), *[vp] * 15),
-    ("scr_backward_aux", i32, i64, i32, i64, i64, *[vp] * 5, P(Settings), *[vp] * 17),
-    ("scr_backward_camera", i32, i64, i32, i64, i64, *[vp] * 5, P(Settings), *[vp] * 20),
+    ("scr_forward_plan", i32, i64, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp),
+    ("scr_forward_run", i32, i64, i64, i64, i64, P(Settings), *[vp] * 7),
+    ("scr_forward_plan_run", i32, i64, i64, i32, *[vp] * 7, P(Settings), vp, vp, P(i64), vp, sz, *[vp] * 5),
+    ("scr_backward", i32, i64, i32, i64, i64, *[vp] * 5, P(Settings), *[vp] * 20),
     ("scr_debug_force_deep_lists", i32, i32),
     ("scr_debug_get", i32, i32, i64, i64, i32, i32, *[vp] * 5),
     ("scr_tpa_scratch_bytes", sz, i32, i32, i32),

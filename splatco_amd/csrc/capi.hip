@@ -175,6 +175,17 @@ static int check_settings(const scr_settings* s) {
     return 0;
 }
 
+static int check_plan_flags(int64_t plan_flags) {
+    if (plan_flags & ~(int64_t)(SCR_PLAN_NONFINITE_COLOUR | SCR_PLAN_LARGE_RECTS | SCR_PLAN_ANTIALIASED)) return fail("plan_flags %lld: not a value scr_forward_plan returned", (long long)plan_flags);
+    return 0;
+}
+
+// out_depth / out_alpha of the forward: both NULL (no maps) or both given
+static int check_maps(const float* out_depth, const float* out_alpha) {
+    if ((out_depth != nullptr) != (out_alpha != nullptr)) return fail("out_depth / out_alpha: give both maps or neither");
+    return 0;
+}
+
 extern "C" {
 
 int scr_abi_version(void) { return SCR_ABI_VERSION; }
@@ -183,9 +194,9 @@ const char* scr_last_error(void) { return g_err; }
 size_t scr_geom_bytes(int64_t P, int32_t H, int32_t W) { return geom_view(nullptr, P, H, W).bytes; }
 size_t scr_binning_bytes(int64_t I, int64_t max_tile) { return bin_view(nullptr, I, max_tile).bytes; }
 size_t scr_image_bytes(int32_t H, int32_t W) { return img_view(nullptr, H, W).bytes; }
-size_t scr_backward_scratch_bytes(int64_t I) { return grad_rec_bytes(I); }
-size_t scr_backward_scratch_bytes_aux(int64_t I) { return grad_rec_bytes(I) + grad_z_bytes(I); }
-size_t scr_backward_scratch_bytes_camera(int64_t I, int64_t P) { return grad_rec_bytes(I) + grad_z_bytes(I) + camera_partials_bytes(P); }
+size_t scr_backward_scratch_bytes(int64_t I, int64_t P, int32_t maps, int32_t camera) {
+    return grad_rec_bytes(I) + (maps || camera ? grad_z_bytes(I) : 0) + (camera ? camera_partials_bytes(P) : 0);
+}
 
 int scr_visible_filter(int64_t P, const float* means3D, const float* scales, const float* rotations,
                        const float* cov3D_precomp, const scr_settings* settings, int32_t* radii_out,
@@ -282,59 +293,23 @@ static int plan_wait(const scr_settings* settings, void* geom_buf, int64_t P, un
     return 0;
 }
 
-static int forward_plan_impl(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales,
-                             const float* rotations, const float* cov3D_precomp, const float* opacities,
-                             const float* shs, const float* colors_precomp, const scr_settings* settings,
-                             void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream) {
+int scr_forward_plan(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales,
+                     const float* rotations, const float* cov3D_precomp, const float* opacities,
+                     const float* shs, const float* colors_precomp, const scr_settings* settings,
+                     void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream) {
+    SCR_MARK_FN;
     unsigned long long seq = 0;
     const int rc = plan_enqueue(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
                                 radii_out, plan_host, (hipStream_t)stream, seq, mode);
     return rc ? rc : plan_wait(settings, geom_buf, P, seq, plan_host, (hipStream_t)stream);
 }
 
-int scr_forward_plan(int64_t P, int32_t M, const float* means3D, const float* scales,
-                     const float* rotations, const float* cov3D_precomp, const float* opacities,
-                     const float* shs, const float* colors_precomp, const scr_settings* settings,
-                     void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream) {
-    SCR_MARK_FN;
-    return forward_plan_impl(0, P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
-                             radii_out, plan_host, stream);
-}
-
-int scr_forward_plan_mode(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales,
-                          const float* rotations, const float* cov3D_precomp, const float* opacities,
-                          const float* shs, const float* colors_precomp, const scr_settings* settings,
-                          void* geom_buf, int32_t* radii_out, int64_t* plan_host, void* stream) {
-    SCR_MARK_FN;
-    return forward_plan_impl(mode, P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
-                             radii_out, plan_host, stream);
-}
-
-// out_depth / out_alpha: both NULL (the colour-only entry points) or both given (the *_aux ones)
-static int forward_run_impl(int64_t P, int64_t I, int64_t max_tile, int64_t plan_flags, const scr_settings* settings, void* geom_buf,
-                            void* binning_buf, void* image_buf, float* out_color, float* out_depth, float* out_alpha,
-                            void* stream, bool scatter_done);
-
-int scr_forward_run(int64_t P, int64_t I, int64_t max_tile, int64_t plan_flags, const scr_settings* settings, void* geom_buf,
-                    void* binning_buf, void* image_buf, float* out_color, void* stream) {
-    SCR_MARK_FN;
-    return forward_run_impl(P, I, max_tile, plan_flags, settings, geom_buf, binning_buf, image_buf, out_color, nullptr, nullptr,
-                            stream, false);
-}
-
-int scr_forward_run_aux(int64_t P, int64_t I, int64_t max_tile, int64_t plan_flags, const scr_settings* settings, void* geom_buf,
-                        void* binning_buf, void* image_buf, float* out_color, float* out_depth, float* out_alpha, void* stream) {
-    SCR_MARK_FN;
-    if (!out_depth || !out_alpha) return fail("out_depth / out_alpha is NULL");
-    return forward_run_impl(P, I, max_tile, plan_flags, settings, geom_buf, binning_buf, image_buf, out_color, out_depth, out_alpha,
-                            stream, false);
-}
-
-static int forward_run_impl(int64_t P, int64_t I, int64_t max_tile, int64_t plan_flags, const scr_settings* settings, void* geom_buf,
-                            void* binning_buf, void* image_buf, float* out_color, float* out_depth, float* out_alpha,
-                            void* stream, bool scatter_done) {
+// phase 2 behind scr_forward_run and scr_forward_plan_run (scatter_done: the latter's early scatter filled the keys)
+static int forward_run(int64_t P, int64_t I, int64_t max_tile, int64_t plan_flags, const scr_settings* settings, void* geom_buf,
+                       void* binning_buf, void* image_buf, float* out_color, float* out_depth, float* out_alpha,
+                       void* stream, bool scatter_done) {
     if (check_settings(settings)) return 1;
-    if (plan_flags & ~(int64_t)(SCR_PLAN_NONFINITE_COLOUR | SCR_PLAN_LARGE_RECTS | SCR_PLAN_ANTIALIASED)) return fail("plan_flags %lld: not a value scr_forward_plan returned", (long long)plan_flags);
+    if (check_plan_flags(plan_flags)) return 1;
     if (!geom_buf || !binning_buf || !image_buf || !out_color) return fail("NULL buffer");
     hipStream_t st = (hipStream_t)stream;
     KSettings ks = ksettings(settings);
@@ -355,51 +330,21 @@ static int forward_run_impl(int64_t P, int64_t I, int64_t max_tile, int64_t plan
     return 0;
 }
 
-static int forward_plan_run_impl(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
-                                 const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
-                                 const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
-                                 void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
-                                 float* out_depth, float* out_alpha, void* stream, int64_t mode);
+int scr_forward_run(int64_t P, int64_t I, int64_t max_tile, int64_t plan_flags, const scr_settings* settings, void* geom_buf,
+                    void* binning_buf, void* image_buf, float* out_color, float* out_depth, float* out_alpha, void* stream) {
+    SCR_MARK_FN;
+    if (check_maps(out_depth, out_alpha)) return 1;
+    return forward_run(P, I, max_tile, plan_flags, settings, geom_buf, binning_buf, image_buf, out_color, out_depth, out_alpha,
+                       stream, false);
+}
 
-int scr_forward_plan_run(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
+int scr_forward_plan_run(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
                          const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
                          const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
-                         void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color, void* stream) {
+                         void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
+                         float* out_depth, float* out_alpha, void* stream) {
     SCR_MARK_FN;
-    return forward_plan_run_impl(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
-                                 radii_out, plan_host, binning_buf, binning_capacity_bytes, image_buf, out_color, nullptr, nullptr,
-                                 stream, 0);
-}
-
-int scr_forward_plan_run_aux(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
-                             const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
-                             const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
-                             void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
-                             float* out_depth, float* out_alpha, void* stream) {
-    SCR_MARK_FN;
-    if (binning_buf && image_buf && out_color && (!out_depth || !out_alpha)) return fail("out_depth / out_alpha is NULL");
-    return forward_plan_run_impl(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
-                                 radii_out, plan_host, binning_buf, binning_capacity_bytes, image_buf, out_color, out_depth, out_alpha,
-                                 stream, 0);
-}
-
-int scr_forward_plan_run_mode(int64_t mode, int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
-                              const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
-                              const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
-                              void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
-                              float* out_depth, float* out_alpha, void* stream) {
-    SCR_MARK_FN;
-    if ((out_depth != nullptr) != (out_alpha != nullptr)) return fail("out_depth / out_alpha: give both maps or neither");
-    return forward_plan_run_impl(P, M, means3D, scales, rotations, cov3D_precomp, opacities, shs, colors_precomp, settings, geom_buf,
-                                 radii_out, plan_host, binning_buf, binning_capacity_bytes, image_buf, out_color, out_depth, out_alpha,
-                                 stream, mode);
-}
-
-static int forward_plan_run_impl(int64_t P, int32_t M, const float* means3D, const float* scales, const float* rotations,
-                                 const float* cov3D_precomp, const float* opacities, const float* shs, const float* colors_precomp,
-                                 const scr_settings* settings, void* geom_buf, int32_t* radii_out, int64_t* plan_host,
-                                 void* binning_buf, size_t binning_capacity_bytes, void* image_buf, float* out_color,
-                                 float* out_depth, float* out_alpha, void* stream, int64_t mode) {
+    if (check_maps(out_depth, out_alpha)) return 1;
     if (!plan_host) return fail("plan_host is NULL");
     plan_host[2] = 0;
     hipStream_t st = (hipStream_t)stream;
@@ -435,73 +380,24 @@ static int forward_plan_run_impl(int64_t P, int32_t M, const float* means3D, con
         }
         return 0;                                  // caller allocates, then scr_forward_run
     }
-    rc = forward_run_impl(P, plan_host[0], plan_host[1], plan_host[3], settings, geom_buf, binning_buf, image_buf, out_color, out_depth,
-                          out_alpha, stream, scattered);
+    rc = forward_run(P, plan_host[0], plan_host[1], plan_host[3], settings, geom_buf, binning_buf, image_buf, out_color, out_depth,
+                     out_alpha, stream, scattered);
     if (rc) return rc;
     plan_host[2] = 1;
     return 0;
 }
 
-static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
-                         const float* rotations, const float* cov3D_precomp, const float* shs,
-                         const scr_settings* settings, const int32_t* radii, void* geom_buf,
-                         const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
-                         const float* dL_dalpha, void* scratch,
-                         float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
-                         float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                         float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream);
-
+// dL_ddepth / dL_dalpha both NULL: the colour-only kernels; the three camera outputs all NULL: the kernels without the
+// camera sums
 int scr_backward(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
                  const float* rotations, const float* cov3D_precomp, const float* shs,
                  const scr_settings* settings, const int32_t* radii, void* geom_buf,
-                 const void* binning_buf, void* image_buf, const float* dL_dcolor, void* scratch,
+                 const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
+                 const float* dL_dalpha, void* scratch,
                  float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
                  float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                 void* stream) {
+                 float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream) {
     SCR_MARK_FN;
-    return backward_impl(P, M, I, plan_flags, means3D, scales, rotations, cov3D_precomp, shs, settings, radii, geom_buf, binning_buf,
-                         image_buf, dL_dcolor, nullptr, nullptr, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dsh, dL_dopacity,
-                         dL_dscales, dL_drotations, dL_dcov3D, nullptr, nullptr, nullptr, stream);
-}
-
-int scr_backward_aux(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
-                     const float* rotations, const float* cov3D_precomp, const float* shs,
-                     const scr_settings* settings, const int32_t* radii, void* geom_buf,
-                     const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
-                     const float* dL_dalpha, void* scratch,
-                     float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
-                     float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                     void* stream) {
-    SCR_MARK_FN;
-    return backward_impl(P, M, I, plan_flags, means3D, scales, rotations, cov3D_precomp, shs, settings, radii, geom_buf, binning_buf,
-                         image_buf, dL_dcolor, dL_ddepth, dL_dalpha, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dsh, dL_dopacity,
-                         dL_dscales, dL_drotations, dL_dcov3D, nullptr, nullptr, nullptr, stream);
-}
-
-int scr_backward_camera(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
-                        const float* rotations, const float* cov3D_precomp, const float* shs,
-                        const scr_settings* settings, const int32_t* radii, void* geom_buf,
-                        const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
-                        const float* dL_dalpha, void* scratch,
-                        float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
-                        float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                        float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream) {
-    SCR_MARK_FN;
-    return backward_impl(P, M, I, plan_flags, means3D, scales, rotations, cov3D_precomp, shs, settings, radii, geom_buf, binning_buf,
-                         image_buf, dL_dcolor, dL_ddepth, dL_dalpha, scratch, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dsh, dL_dopacity,
-                         dL_dscales, dL_drotations, dL_dcov3D, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, stream);
-}
-
-// dL_ddepth / dL_dalpha both NULL: the colour-only kernels, whichever entry point was called; the three camera outputs all
-// NULL: the kernels without the camera sums
-static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, const float* means3D, const float* scales,
-                         const float* rotations, const float* cov3D_precomp, const float* shs,
-                         const scr_settings* settings, const int32_t* radii, void* geom_buf,
-                         const void* binning_buf, void* image_buf, const float* dL_dcolor, const float* dL_ddepth,
-                         const float* dL_dalpha, void* scratch,
-                         float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsh,
-                         float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                         float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream) {
     if (check_settings(settings)) return 1;
     if (P < 0) return fail("P < 0");
     const bool camera = dL_dviewmatrix || dL_dprojmatrix || dL_dcampos;
@@ -511,7 +407,7 @@ static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, co
         if (dL_dcampos) HIP_TRY(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float), (hipStream_t)stream));
         return 0;
     }
-    if (plan_flags & ~(int64_t)(SCR_PLAN_NONFINITE_COLOUR | SCR_PLAN_LARGE_RECTS | SCR_PLAN_ANTIALIASED)) return fail("plan_flags %lld: not a value scr_forward_plan returned", (long long)plan_flags);
+    if (check_plan_flags(plan_flags)) return 1;
     if (!geom_buf || !binning_buf || !image_buf || !dL_dcolor || !scratch) return fail("NULL buffer");
     if (!means3D || !radii || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity) return fail("NULL argument");
     if (shs ? !dL_dsh : !dL_dcolors) return fail("colour gradient output missing");
@@ -525,9 +421,9 @@ static int backward_impl(int64_t P, int32_t M, int64_t I, int64_t plan_flags, co
     // a value no earlier call of this process used (and that uninitialised memory is unlikely to hold): see blend.hip
     static std::atomic<unsigned long long> stamp_counter{0x5ca1ab1e00000000ull};
     const unsigned long long stamp = ++stamp_counter;
-    // the depth sums lie behind the records (scr_backward_scratch_bytes_aux)
+    // the depth sums lie behind the records (scr_backward_scratch_bytes with maps)
     float* const grad_z = (I > 0 && (dL_ddepth || dL_dalpha)) ? (float*)((char*)scratch + grad_rec_bytes(I)) : nullptr;
-    // the camera sums' rows lie behind both (scr_backward_scratch_bytes_camera reserves the depth sums whether used or not)
+    // the camera sums' rows lie behind both (scr_backward_scratch_bytes with camera reserves the depth sums whether used or not)
     float* const cam_partials = camera ? (float*)((char*)scratch + grad_rec_bytes(I) + grad_z_bytes(I)) : nullptr;
     if (settings->debug) {      // the flags the caller carried from scr_forward_plan against the ones the forward left in geom_buf
         unsigned long long dev_flags = 0;

@@ -9,15 +9,15 @@ non-differentiable.  Saved state is per call, so the mv live graphs of train.py:
 With return_aux=True the same pass also returns the depth map sum_i w_i z_i and the accumulated opacity sum_i w_i
 (w_i = alpha_i T_i, z_i the view-space depth; background excluded, depth not normalised), both differentiable.
 The camera is differentiable too: when raster_settings.viewmatrix, .projmatrix or .campos requires grad (and gradient mode is
-on) the backward also returns dL/dviewmatrix, dL/dprojmatrix [4, 4] and dL/dcampos [3] (scr_backward_camera), each in the
+on) the backward also returns dL/dviewmatrix, dL/dprojmatrix [4, 4] and dL/dcampos [3] (scr_backward's camera outputs), each in the
 shape of the tensor given and only for those that require grad.  The two matrices are independent inputs, as the kernels
 read them: a full projection built in torch from the view matrix gets the composed gradient from autograd.  Columns the
 forward never reads (viewmatrix[:, 3], projmatrix[:, 2]) get exact zeros, campos gets zeros with colors_precomp.  tanfovx /
-tanfovy stay Python floats.  Without such a tensor nothing changes: the same entry points, kernels and bits.
+tanfovy stay Python floats.  Without such a tensor nothing changes: the same kernels and bits.
 With antialiased=True (upstream 3DGS `antialiasing`, gsplat rasterize_mode="antialiased") every splat's opacity is multiplied
 by h = sqrt(max(0.000025, det(Sigma2D) / det(Sigma2D + 0.3 I))), which keeps its integrated opacity independent of the
 0.3 px^2 dilation; h is differentiated with respect to the means, the covariance inputs and the view matrix.  Radii, tile
-rects and the sort do not depend on the mode; the default (False) is the same entry points, kernels and bits as before.
+rects and the sort do not depend on the mode; the default (False) is the same kernels and bits as before.
 PyTorch is used for device memory and streams only.
 """
 from typing import NamedTuple
@@ -112,7 +112,7 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
                       antialiased=False):
     """plan + run through the C-ABI.  Returns (color, radii, RasterState).  aux: the blend also writes the depth and
     opacity maps, two [H, W] tensors left in RasterState.aux for the caller to take.  antialiased: the opacity compensation
-    (scr_forward_plan_run_mode with SCR_MODE_ANTIALIASED); RasterState.flags then carries PLAN_ANTIALIASED to the backward."""
+    (SCR_MODE_ANTIALIASED); RasterState.flags then carries PLAN_ANTIALIASED to the backward."""
     dev = means3D.device
     P = means3D.shape[0]
     M = 0 if shs is None else shs.shape[1]
@@ -125,11 +125,8 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
     st.aux = None
     if aux:
         st.aux = (torch.empty(cs.H, cs.W, dtype=torch.float32, device=dev), torch.empty(cs.H, cs.W, dtype=torch.float32, device=dev))
-    maps = () if st.aux is None else (st.aux[0].data_ptr(), st.aux[1].data_ptr())
-    plan_run, run = ((_C.lib.scr_forward_plan_run_aux, _C.lib.scr_forward_run_aux) if aux else
-                     (_C.lib.scr_forward_plan_run, _C.lib.scr_forward_run))
-    if antialiased:      # one entry point with or without the maps (both NULL: none); the default call stays the old one
-        plan_run = lambda *a: _C.lib.scr_forward_plan_run_mode(_C.MODE_ANTIALIASED, *a[:-1], *((None, None) if not aux else ()), a[-1])
+    maps = (None, None) if st.aux is None else (st.aux[0].data_ptr(), st.aux[1].data_ptr())
+    mode = _C.MODE_ANTIALIASED if antialiased else 0
     plan = (C.c_int64 * 4)(0, 0, 0, 0)   # (tile instances, largest per-tile instance count, phase 2 already ran, plan flags)
     # The binning buffer's size is only known after the plan phase.  A guess from the previous call of this size (the
     # instance count of a training loop moves by a few per cent per step) lets both phases go out in ONE call: the GPU
@@ -142,10 +139,11 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
             scale = 1.06 * P / guess[0]
             cap = _C.lib.scr_binning_bytes(min(int(guess[1] * scale) + 4096, (1 << 32) - 2), max(int(guess[2] * 1.25), guess[2] + 64))
             spec = _C.scratch(cap, dev)
-        _C.check(plan_run(P, M, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D_precomp),
-                          _C.ptr(opacities), _C.ptr(shs), _C.ptr(colors_precomp), cs.ref(),
-                          st.geom.data_ptr(), _C.ptr(radii), plan, None if spec is None else spec.data_ptr(),
-                          0 if spec is None else spec.numel(), st.image.data_ptr(), color.data_ptr(), *maps, _C.stream()))
+        _C.check(_C.lib.scr_forward_plan_run(
+            mode, P, M, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D_precomp),
+            _C.ptr(opacities), _C.ptr(shs), _C.ptr(colors_precomp), cs.ref(),
+            st.geom.data_ptr(), _C.ptr(radii), plan, None if spec is None else spec.data_ptr(),
+            0 if spec is None else spec.numel(), st.image.data_ptr(), color.data_ptr(), *maps, _C.stream()))
         st.I, st.max_tile, st.flags = int(plan[0]), int(plan[1]), int(plan[3])
         _plan_guess[key] = (P, st.I, st.max_tile)
         if plan[2]:
@@ -153,8 +151,8 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
         else:
             del spec
             st.binning = _C.scratch(_C.lib.scr_binning_bytes(st.I, st.max_tile), dev)
-            _C.check(run(P, st.I, st.max_tile, st.flags, cs.ref(), st.geom.data_ptr(), st.binning.data_ptr(),
-                         st.image.data_ptr(), color.data_ptr(), *maps, _C.stream()))
+            _C.check(_C.lib.scr_forward_run(P, st.I, st.max_tile, st.flags, cs.ref(), st.geom.data_ptr(), st.binning.data_ptr(),
+                                            st.image.data_ptr(), color.data_ptr(), *maps, _C.stream()))
     st.radii = radii
     return color, radii, st
 
@@ -233,8 +231,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             return (None,) * (11 + len(ctx.camera))      # no output took part in the loss: every gradient is zero
         means3D, scales, rotations, cov3D, sh, colors, opacities = ctx.saved_tensors
         dev, P, cs = means3D.device, st.P, st.cs
-        # with a gradient for one of the maps the blend backward carries two more channels (scr_backward_aux); without, this
-        # is the colour-only backward whichever forward ran.  A missing dL/dcolor is zeros then: the kernels always read it
+        # with a gradient for one of the maps the blend backward carries two more channels; without, this is the
+        # colour-only backward whichever forward ran.  A missing dL/dcolor is zeros then: the kernels always read it
         aux = grad_out_depth is not None or grad_out_alpha is not None
         g = (_dev_f32(grad_out_color, "grad_out_color") if grad_out_color is not None
              else torch.zeros(3, cs.H, cs.W, dtype=torch.float32, device=dev))
@@ -259,22 +257,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         if any(want_cam):      # [16 | 16 | 3]: dL/dviewmatrix, dL/dprojmatrix, dL/dcampos, row-major like the settings' tensors
             cam_buf = torch.empty(35, dtype=torch.float32, device=dev)
             g_cam = tuple(cam_buf[lo:hi] if w else None for (lo, hi), w in zip(((0, 16), (16, 32), (32, 35)), want_cam))
-            scratch = _C.scratch(_C.lib.scr_backward_scratch_bytes_camera(st.I, P), dev)
-        else:
-            scratch = _C.scratch((_C.lib.scr_backward_scratch_bytes_aux if aux else _C.lib.scr_backward_scratch_bytes)(st.I), dev)
-        head = (P, st.M, st.I, st.flags, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D),
-                _C.ptr(sh), cs.ref(), st.radii.data_ptr(), st.geom.data_ptr(), st.binning.data_ptr(), st.image.data_ptr(),
-                g.data_ptr())
-        outs = (scratch.data_ptr(), g_means3D.data_ptr(), g_means2D.data_ptr(), _C.ptr(g_col), _C.ptr(g_sh),
-                g_op.data_ptr(), _C.ptr(g_scales), _C.ptr(g_rot), _C.ptr(g_cov), *(_C.ptr(t) for t in g_cam), _C.stream())
+        scratch = _C.scratch(_C.lib.scr_backward_scratch_bytes(st.I, P, int(aux), int(bool(g_cam))), dev)
         try:
           with torch.cuda.device(dev):
-            if g_cam:
-                _C.check(_C.lib.scr_backward_camera(*head, _C.ptr(g_depth), _C.ptr(g_alpha), *outs))
-            elif aux:
-                _C.check(_C.lib.scr_backward_aux(*head, _C.ptr(g_depth), _C.ptr(g_alpha), *outs))
-            else:
-                _C.check(_C.lib.scr_backward(*head, *outs))
+            _C.check(_C.lib.scr_backward(
+                P, st.M, st.I, st.flags, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D),
+                _C.ptr(sh), cs.ref(), st.radii.data_ptr(), st.geom.data_ptr(), st.binning.data_ptr(), st.image.data_ptr(),
+                g.data_ptr(), _C.ptr(g_depth), _C.ptr(g_alpha), scratch.data_ptr(), g_means3D.data_ptr(),
+                g_means2D.data_ptr(), _C.ptr(g_col), _C.ptr(g_sh), g_op.data_ptr(), _C.ptr(g_scales), _C.ptr(g_rot),
+                _C.ptr(g_cov), *(_C.ptr(t) for t in g_cam or (None,) * 3), _C.stream()))
         except RuntimeError as e:
             if ctx.raster_settings.debug:
                 raise RuntimeError(str(e) + _debug_dump("snapshot_bw.dump", ctx.raster_settings, means3D=means3D, sh=sh,

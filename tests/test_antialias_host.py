@@ -136,10 +136,15 @@ def test_unknown_mode_bit_is_refused():
     from splatco_amd import _C
     plan = (ctypes.c_int64 * 4)(7, 7, 7, 7)
     for mode in (2, 3, 1 << 40, -1):
-        rc = _C.lib.scr_forward_plan_mode(mode, 0, 0, *[None] * 7, None, None, None, plan, None)
+        rc = _C.lib.scr_forward_plan(mode, 0, 0, *[None] * 7, None, None, None, plan, None)
         assert rc != 0 and "mode" in _C.lib.scr_last_error().decode()
-        rc = _C.lib.scr_forward_plan_run_mode(mode, 0, 0, *[None] * 7, None, None, None, plan, None, 0, *[None] * 5)
+        rc = _C.lib.scr_forward_plan_run(mode, 0, 0, *[None] * 7, None, None, None, plan, None, 0, *[None] * 5)
         assert rc != 0 and "mode" in _C.lib.scr_last_error().decode()
     # a known mode gets as far as the argument checks
-    assert _C.lib.scr_forward_plan_mode(_C.MODE_ANTIALIASED, 0, 0, *[None] * 7, None, None, None, plan, None) != 0
+    assert _C.lib.scr_forward_plan(_C.MODE_ANTIALIASED, 0, 0, *[None] * 7, None, None, None, plan, None) != 0
     assert "settings" in _C.lib.scr_last_error().decode()
+    # one map without the other is refused before anything is launched, whichever of the two is given
+    one = ctypes.c_void_p(256)      # never dereferenced: the call fails on the pair
+    for maps in ((one, None), (None, one)):
+        assert _C.lib.scr_forward_run(0, 0, 0, 0, None, None, None, None, None, *maps, None) != 0
+        assert "out_depth / out_alpha" in _C.lib.scr_last_error().decode()

@@ -11,14 +11,15 @@ from util import rel_l2, small_scene
 
 def test_abi_has_the_camera_entry_points():
     from splatco_amd import _C
-    assert _C.ABI_VERSION >= 31 and _C.lib.scr_abi_version() == _C.ABI_VERSION
-    for name in ("scr_backward_camera", "scr_backward_scratch_bytes_camera"):
+    assert _C.ABI_VERSION >= 34 and _C.lib.scr_abi_version() == _C.ABI_VERSION
+    for name in ("scr_backward", "scr_backward_scratch_bytes"):      # the camera outputs and the `camera` flag are theirs
         assert name in _C.SYMBOLS and hasattr(_C.lib, name), name
+    size = _C.lib.scr_backward_scratch_bytes
     # the records, the depth sums and one 128-byte row per 256 Gaussians, each part 256-byte aligned
-    base = _C.lib.scr_backward_scratch_bytes_aux(1000)
-    assert _C.lib.scr_backward_scratch_bytes_camera(1000, 1) == base + 256
-    assert _C.lib.scr_backward_scratch_bytes_camera(1000, 70000) == base + 274 * 128
-    assert _C.lib.scr_backward_scratch_bytes_camera(0, 0) >= _C.lib.scr_backward_scratch_bytes_aux(0) + 128
+    base = size(1000, 0, 1, 0)
+    assert size(1000, 1, 0, 1) == size(1000, 1, 1, 1) == base + 256      # the depth sums are reserved whatever `maps` says
+    assert size(1000, 70000, 0, 1) == size(1000, 70000, 1, 1) == base + 274 * 128
+    assert size(0, 0, 0, 1) >= size(0, 0, 1, 0) + 128
 
 
 def test_pose_delta_camera_at_zero_is_the_camera():

@@ -164,7 +164,7 @@ def test_off_is_the_old_call():
         outs.append((img.detach(), radii, {k: v.grad for k, v in kw.items()}))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     assert all(_same_bits(outs[0][2][k], outs[1][2][k]) for k in outs[0][2])
-    # the records of scr_forward_plan_run_mode(0, ...) against those of scr_forward_plan_run
+    # the records of a direct plan-only scr_forward_plan_run(0, ...) against those of the operator's default forward
     st, radii = _state(cam, g)
     assert st.flags & _C.PLAN_ANTIALIASED == 0
     vis = radii > 0
@@ -175,9 +175,9 @@ def test_off_is_the_old_call():
     plan = (C.c_int64 * 4)(0, 0, 0, 0)
     ins = [_t(g[k]) for k in ("means3D", "scales", "rotations", "opacities", "colors")]
     with torch.cuda.device(_dev()):
-        _C.check(_C.lib.scr_forward_plan_run_mode(0, P, 0, ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), None,
-                                                   ins[3].data_ptr(), None, ins[4].data_ptr(), st.cs.ref(), geom.data_ptr(),
-                                                   radii0.data_ptr(), plan, None, 0, None, None, None, None, _C.stream()))
+        _C.check(_C.lib.scr_forward_plan_run(0, P, 0, ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), None,
+                                              ins[3].data_ptr(), None, ins[4].data_ptr(), st.cs.ref(), geom.data_ptr(),
+                                              radii0.data_ptr(), plan, None, 0, None, None, None, None, _C.stream()))
         rec0 = torch.empty(P, 12, dtype=torch.float32, device=_dev())
         _C.check(_C.lib.scr_debug_get(_C.DBG_SPLAT_RECORDS, P, 0, st.cs.H, st.cs.W, geom.data_ptr(), None, None,
                                       rec0.data_ptr(), _C.stream()))

@@ -31,12 +31,12 @@ bad |= nc != f["n_contrib"]
 dL[:, bad] = 0
 print("excused pixels", bad.sum())
 P, I = stt.P, stt.I
-scratch = torch.zeros(_C.lib.scr_backward_scratch_bytes(I), dtype=torch.uint8, device=dev)
+scratch = torch.zeros(_C.lib.scr_backward_scratch_bytes(I, P, 0, 0), dtype=torch.uint8, device=dev)
 outs = [torch.empty(P, w, device=dev) for w in (3, 3, 3, 1, 3, 4)]
 _C.check(_C.lib.scr_backward(P, 0, I, stt.flags, m.data_ptr(), s.data_ptr(), r.data_ptr(), None, None, cs.ref(), stt.radii.data_ptr(),
-                             stt.geom.data_ptr(), stt.binning.data_ptr(), stt.image.data_ptr(), t(dL).data_ptr(), scratch.data_ptr(),
+                             stt.geom.data_ptr(), stt.binning.data_ptr(), stt.image.data_ptr(), t(dL).data_ptr(), None, None, scratch.data_ptr(),
                              outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), None, outs[3].data_ptr(), outs[4].data_ptr(),
-                             outs[5].data_ptr(), None, R._stream()))
+                             outs[5].data_ptr(), None, None, None, None, R._stream()))
 torch.cuda.synchronize()
 rec = scratch.cpu().numpy().view(np.float32)[:I * 9].reshape(I, 9).astype(np.float64)
 tt = f["tiles_touched"].astype(np.int64)
