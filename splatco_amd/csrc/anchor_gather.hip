@@ -307,7 +307,7 @@ anchor_gather_backward_kernel(int64_t N, int64_t V, const int64_t* __restrict__ 
     if (threadIdx.x < AG_ROWS && (int)threadIdx.x < rows) myv = inv[n0 + threadIdx.x];
     if (threadIdx.x < 64) {
         const unsigned long long bal = __builtin_amdgcn_ballot_w64(myv >= 0);
-        const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        const int below = (int)lanes_below(bal);
         rowv[threadIdx.x] = myv >= 0 ? below : -1;
         if (myv >= 0 && below == 0) first_v = myv;
         if (threadIdx.x == 0) nvis = __builtin_popcountll(bal);

@@ -13,34 +13,9 @@
 //               each instance's Gaussian-major index (where the backward pass puts its gradient
 //               record) from the Gaussian's tile rect, so no payload travels through the sort.
 // Both passes move 8-12 B per instance once instead of 6+ radix passes over 12 B.
-#include "common.h"
+#include "compact.h"     // block_exclusive_scan
 
 namespace scr {
-
-// ------------------------------------------------------------------ block-wide exclusive scan
-template <int THREADS>
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds_waves /*[THREADS/64+1]*/,
-                                                         uint32_t& block_total) {
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        uint32_t n = __shfl_up(inc, d, WAVE);
-        if (lane >= d) inc += n;
-    }
-    if (lane == WAVE - 1) lds_waves[w] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < THREADS / WAVE; ++k) {
-        uint32_t s = lds_waves[k];
-        if (k < w) base += s;
-        tot += s;
-    }
-    block_total = tot;
-    __syncthreads();
-    return base + inc - v;
-}
 
 // ------------------------------------------------------------------ plan scans (2 workgroups)
 // block 0: block_sums[nblk] -> exclusive prefix in place, total -> *total

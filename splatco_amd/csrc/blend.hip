@@ -99,10 +99,6 @@ __device__ __forceinline__ float fast_exp(float x) {
     return __builtin_fmaf(g, r, g);
 }
 
-__device__ __forceinline__ uint32_t lanes_below(unsigned long long ballot) {  // popcount of lower lanes
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
-
 // ------------------------------------------------------------------ longest tiles first, XCDs balanced
 // A blend launch is a few rounds of tiles over the chip's workgroup slots; blocks are handed out in order, round-robin
 // over the 8 XCDs.  Two things go wrong on a scene that is not uniform: the last, partial round lasts as long as the

@@ -7,7 +7,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "common.h"
+#include "compact.h"
 #include "adam.h"
 #include "tv.h"
 #include <chrono>
@@ -164,6 +164,27 @@ static bool mailbox_wait(Mailbox& mb, unsigned long long seq, bool two, hipStrea
             if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) return false;
         }
     }
+}
+
+// the plan half of a compaction (compact.h) of n items: `launch(scratch view, mailbox, stamp)` enqueues the count pass of
+// kernel `name`, and the number of kept items comes back to *count_host
+template <class Launch>
+static int compact_plan(const char* name, int64_t n, void* scratch, int64_t* count_host, hipStream_t st, Launch launch) {
+    if (!count_host || !scratch || n <= 0 || n >= (1ll << 31)) return fail("%s: bad plan arguments", name);
+    const CompactScratch s = compact_scratch(scratch, n);
+    Mailbox& mb = mailbox();
+    const unsigned long long seq = ++mb.seq;
+    launch(s, mb.dev, seq);
+    CHECK_LAUNCH(name, 0, st);
+    unsigned long long t = 0;
+    if (mailbox_wait(mb, seq, false, st)) {
+        t = mb.host[0];
+    } else {
+        HIP_TRY(hipMemcpyAsync(&t, s.total, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    *count_host = (int64_t)t;
+    return 0;
 }
 
 static int check_settings(const scr_settings* s) {
@@ -501,9 +522,7 @@ int scr_debug_get(int which, int64_t P, int64_t I, int32_t H, int32_t W, const v
 }
 
 // ---- fused expansion + compaction (expand.hip)
-static inline size_t expand_nwg(int64_t n) { return (size_t)((n + 1023) / 1024); }
-
-size_t scr_expand_scratch_bytes(int64_t n) { return align_up((expand_nwg(n) + 1) * 4) + 256; }
+size_t scr_expand_scratch_bytes(int64_t n) { return compact_scratch_bytes(n); }
 
 int scr_expand_plan(int64_t n, const float* neural_opacity, void* scratch, int64_t* num_selected_host,
                     void* stream) {
@@ -515,21 +534,11 @@ int scr_expand_plan(int64_t n, const float* neural_opacity, void* scratch, int64
     if (!neural_opacity || !scratch) return fail("NULL argument");
     if (n >= (1ll << 31)) return fail("more than 2^31 candidates");
     hipStream_t st = (hipStream_t)stream;
-    uint32_t* wg = (uint32_t*)scratch;
-    unsigned long long* total = (unsigned long long*)((char*)scratch + align_up((expand_nwg(n) + 1) * 4));
-    Mailbox& mb = mailbox();
-    const unsigned long long seq = ++mb.seq;
-    { ProfScope ps_(SCR_PROF_EXPAND, st); launch_expand_count(n, neural_opacity, wg, total, mb.dev, seq, st); }
-    CHECK_LAUNCH("expand_count_kernel", 0, st);
-    unsigned long long t = 0;
-    if (mailbox_wait(mb, seq, false, st)) {
-        t = mb.host[0];
-    } else {
-        HIP_TRY(hipMemcpyAsync(&t, total, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    *num_selected_host = (int64_t)t;
-    return 0;
+    return compact_plan("compact_count_kernel<KeepOpacity>", n, scratch, num_selected_host, st,
+                        [&](const CompactScratch& s, unsigned long long* mb, unsigned long long seq) {
+                            ProfScope ps_(SCR_PROF_EXPAND, st);
+                            launch_expand_count(n, neural_opacity, s, mb, seq, st);
+                        });
 }
 
 // mask -> index list with the expansion's count / scan / write scheme (scratch: scr_expand_scratch_bytes(n))
@@ -542,21 +551,11 @@ int scr_mask_index_plan(int64_t n, const uint8_t* mask, void* scratch, int64_t* 
     if (!mask || !scratch) return fail("NULL argument");
     if (n >= (1ll << 31)) return fail("more than 2^31 mask entries");
     hipStream_t st = (hipStream_t)stream;
-    uint32_t* wg = (uint32_t*)scratch;
-    unsigned long long* total = (unsigned long long*)((char*)scratch + align_up((expand_nwg(n) + 1) * 4));
-    Mailbox& mb = mailbox();
-    const unsigned long long seq = ++mb.seq;
-    { ProfScope ps_(SCR_PROF_EXPAND, st); launch_mask_count(n, mask, wg, total, mb.dev, seq, st); }
-    CHECK_LAUNCH("mask_count_kernel", 0, st);
-    unsigned long long t = 0;
-    if (mailbox_wait(mb, seq, false, st)) {
-        t = mb.host[0];
-    } else {
-        HIP_TRY(hipMemcpyAsync(&t, total, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    *num_set_host = (int64_t)t;
-    return 0;
+    return compact_plan("compact_count_kernel<KeepMask>", n, scratch, num_set_host, st,
+                        [&](const CompactScratch& s, unsigned long long* mb, unsigned long long seq) {
+                            ProfScope ps_(SCR_PROF_EXPAND, st);
+                            launch_mask_count(n, mask, s, mb, seq, st);
+                        });
 }
 
 int scr_mask_index_run(int64_t n, const uint8_t* mask, const void* scratch, int64_t* index, int64_t* inverse, void* stream) {
@@ -1191,7 +1190,7 @@ int scr_knn_curvature(int64_t N, int32_t k, const float* points, const int64_t* 
 }
 
 // ---- a scene from a point cloud (scene_init.hip)
-size_t scr_voxel_unique_scratch_bytes(int64_t N) { return align_up((voxel_unique_nwg(N > 0 ? N : 1) + 1) * 4) + 256; }
+size_t scr_voxel_unique_scratch_bytes(int64_t N) { return compact_scratch_bytes(N > 0 ? N : 1); }
 
 size_t scr_points_bounds_scratch_bytes(int64_t N) { return align_up(points_bounds_nwg(N > 0 ? N : 1) * 8 * sizeof(float)); }
 
@@ -1228,21 +1227,10 @@ int scr_voxel_unique_plan(int64_t N, const int64_t* sorted_keys, void* scratch, 
     if (N <= 0 || N >= (1ll << 31)) return fail("scr_voxel_unique_plan: need 0 < N < 2^31");
     if (!sorted_keys || !scratch) return fail("scr_voxel_unique_plan: NULL argument");
     hipStream_t st = (hipStream_t)stream;
-    uint32_t* wg = (uint32_t*)scratch;
-    unsigned long long* total = (unsigned long long*)((char*)scratch + align_up((voxel_unique_nwg(N) + 1) * 4));
-    Mailbox& mb = mailbox();
-    const unsigned long long seq = ++mb.seq;
-    launch_voxel_unique_count(N, sorted_keys, wg, total, mb.dev, seq, st);
-    CHECK_LAUNCH("voxel_unique_count_kernel", 0, st);
-    unsigned long long t = 0;
-    if (mailbox_wait(mb, seq, false, st)) {
-        t = mb.host[0];
-    } else {
-        HIP_TRY(hipMemcpyAsync(&t, total, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    *num_unique_host = (int64_t)t;
-    return 0;
+    return compact_plan("compact_count_kernel<KeepHead>", N, scratch, num_unique_host, st,
+                        [&](const CompactScratch& s, unsigned long long* mb, unsigned long long seq) {
+                            launch_voxel_unique_count(N, sorted_keys, s, mb, seq, st);
+                        });
 }
 
 int scr_voxel_unique_run(int64_t N, const int64_t* sorted_keys, const void* scratch, float voxel_size,

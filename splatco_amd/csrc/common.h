@@ -217,6 +217,9 @@ __device__ __forceinline__ float vmin(float a, float b) {
     return r;
 }
 __device__ __forceinline__ unsigned long long lanes(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ uint32_t lanes_below(unsigned long long ballot) {  // popcount of lower lanes
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+}
 // any of three values NaN or +-Inf (v_cmp_class_f32: signalling NaN, quiet NaN, -Inf, +Inf)
 __device__ __forceinline__ bool nonfinite3(float a, float b, float c) {
     constexpr int NAN_OR_INF = 0x1 | 0x2 | 0x4 | 0x200;
@@ -248,9 +251,6 @@ __host__ __device__ inline int xcd_of_tile(int t, int gx) {
 // difference between this bound and the per-pixel evaluation.  Dropping such a splat cannot
 // change any result (it would be skipped by every pixel anyway), so lists, n_contrib and images
 // stay bit-identical to the un-culled semantics.  NaNs compare false -> kept.
-// Conservative sub-tile culling.  A splat contributes to a pixel only where its quadratic form
-// q(d) = a dx^2 + b dx dy + c dy^2 stays below thr = ln(255 * opacity) (alpha >= 1/255); a pixel box can be
-// skipped when the exact minimum of q over the box exceeds thr by more than the rounding of the terms.
 struct SplatForm {
     float mx, my, a, b, c, thr;
     float vy, vx;  // minimiser slopes along an edge: dy* = vy * dx on a vertical edge, dx* = vx * dy on a horizontal one
@@ -270,7 +270,7 @@ __device__ inline SplatForm splat_form(float4 r0, float4 r1) {
     f.vx = -f.b / (2.0f * f.a);
     return f;
 }
-// The four quadrants of a tile at once.  Same minimum as box_reachable, found with two edge minima per quadrant
+// The four quadrants of a tile at once.  The exact minimum of q over each box, found with two edge minima per quadrant
 // instead of four: q is convex with its minimiser at d = 0, so over a box that does not contain 0 the minimum lies on a
 // face that is VISIBLE from 0 (from a point of any other face a step towards 0 stays inside the box and lowers q) --
 // at most the vertical edge dx = cx and the horizontal edge dy = cy, where (cx, cy) = 0 clamped into the box
@@ -389,10 +389,14 @@ size_t camera_partials_bytes(int64_t P);
 void launch_camera_grad_finish(int64_t P, const float* cam_partials, float* dL_dview, float* dL_dproj, float* dL_dcampos,
                                hipStream_t st);
 
-void launch_expand_count(int64_t n, const float* neural_opacity, uint32_t* wg_count, unsigned long long* total,
-                         unsigned long long* mailbox, unsigned long long seq, hipStream_t st);
-void launch_mask_count(int64_t n, const uint8_t* mask, uint32_t* wg_count, unsigned long long* total,
-                       unsigned long long* mailbox, unsigned long long seq, hipStream_t st);
+// the count passes of the three compactions (compact.h; the scratch view is compact_scratch()'s)
+struct CompactScratch;
+void launch_expand_count(int64_t n, const float* neural_opacity, const CompactScratch& s, unsigned long long* mailbox,
+                         unsigned long long seq, hipStream_t st);
+void launch_mask_count(int64_t n, const uint8_t* mask, const CompactScratch& s, unsigned long long* mailbox,
+                       unsigned long long seq, hipStream_t st);
+void launch_voxel_unique_count(int64_t n, const int64_t* keys, const CompactScratch& s, unsigned long long* mailbox,
+                               unsigned long long seq, hipStream_t st);
 void launch_mask_index(int64_t n, const uint8_t* mask, const uint32_t* wg_offset, int64_t* index, int64_t* inverse,
                        hipStream_t st);
 void launch_expand_run(int64_t n, int k, const float* neural_opacity, const float* color, const float* scale_rot,
@@ -428,14 +432,9 @@ void launch_knn(int64_t N, int k, const float* grid9, const float* sorted_pts, c
                 const int32_t* cell_start, int64_t* out_idx, hipStream_t st);
 void launch_knn_curvature(int64_t N, int k, const float* pts, const int64_t* idx, float* curvature, hipStream_t st);
 // scene_init.hip: voxelisation and the fused 3-NN mean squared distance
-void launch_wg_scan(uint32_t nwg, uint32_t* wg_count, unsigned long long* total, unsigned long long* mailbox,
-                    unsigned long long seq, hipStream_t st);
 size_t points_bounds_nwg(int64_t N);
 void launch_points_bounds(int64_t N, const float* pts, float* partial, float* out, hipStream_t st);
-size_t voxel_unique_nwg(int64_t n);
 void launch_voxel_keys(int64_t N, const float* pts, float v, const int32_t* lo, int packed, int64_t* out, hipStream_t st);
-void launch_voxel_unique_count(int64_t n, const int64_t* keys, uint32_t* wg_count, unsigned long long* total,
-                               unsigned long long* mailbox, unsigned long long seq, hipStream_t st);
 void launch_voxel_unique_write(int64_t n, const int64_t* keys, const uint32_t* wg_offset, float v, const int32_t* lo,
                                float* out, hipStream_t st);
 void launch_knn3_cell_keys(int64_t N, const float* grid8, const float* pts, int64_t* keys, hipStream_t st);

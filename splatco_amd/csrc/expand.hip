@@ -11,71 +11,26 @@
 //   xyz     = anchor[v] + offsets[c] * grid_scaling[v,0:3]
 //
 // HBM-bound: 56 B read per candidate (+36 B per anchor), 56 B written per kept Gaussian.
-// Compaction = wave ballot + mbcnt prefix inside a workgroup, workgroup offsets from a scan of
-// per-workgroup counts (count pass reads 4 B per candidate).  Backward is one thread per candidate;
+// Compaction = the count / scan / write scheme of compact.h (count pass reads 4 B per candidate); this file
+// supplies the predicates, the write kernels and the scheme's one scan kernel.  Backward is one thread per candidate;
 // the per-anchor sums over its k candidates go through LDS in slot order -> no atomics, deterministic.
-#include "common.h"
+#include "compact.h"
 
 namespace scr {
 
-constexpr int EXP_THREADS = 256;
-constexpr int EXP_ITEMS = 4;                      // candidates per thread
-constexpr int EXP_PER_WG = EXP_THREADS * EXP_ITEMS;  // candidates per workgroup
-
-__device__ __forceinline__ uint32_t lanes_below64(unsigned long long ballot) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
-
-// pass 1: kept candidates per workgroup
-__global__ void __launch_bounds__(EXP_THREADS)
-expand_count_kernel(int64_t n, const float* __restrict__ neural_opacity, uint32_t* __restrict__ wg_count) {
-    __shared__ uint32_t wsum[EXP_THREADS / WAVE];
-    uint32_t c = 0;
-    float no[EXP_ITEMS];      // all loads first, from clamped indices: `i < n && load` put a branch around every load and
-#pragma unroll                // the ballot behind it -- four memory round trips one after the other per workgroup
-    for (int r = 0; r < EXP_ITEMS; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * EXP_PER_WG + r * EXP_THREADS + threadIdx.x;
-        no[r] = neural_opacity[min(i, n - 1)];
-    }
-#pragma unroll
-    for (int r = 0; r < EXP_ITEMS; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * EXP_PER_WG + r * EXP_THREADS + threadIdx.x;
-        const bool keep = i < n && no[r] > 0.0f;
-        c += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(keep));
-    }
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;  // every lane of a wave holds the wave's count
-    __syncthreads();
-    if (threadIdx.x == 0) wg_count[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// pass 2 (one workgroup): exclusive scan of the workgroup counts, total to *total
-__global__ void __launch_bounds__(1024) expand_scan_kernel(uint32_t nwg, uint32_t* __restrict__ wg_count,
-                                                           unsigned long long* __restrict__ total,
-                                                           volatile unsigned long long* mailbox, unsigned long long seq) {
-    __shared__ uint32_t lds[1024 / WAVE];
+// pass 2 of every compaction (one workgroup; declared in compact.h): exclusive scan of the workgroup counts, total to *total
+__global__ void __launch_bounds__(1024) compact_scan_kernel(uint32_t nwg, uint32_t* __restrict__ wg_count,
+                                                            unsigned long long* __restrict__ total,
+                                                            volatile unsigned long long* mailbox, unsigned long long seq) {
+    __shared__ uint32_t lds[1024 / WAVE + 1];
     unsigned long long carry = 0;
     for (uint32_t base = 0; base < nwg; base += 1024) {
         const uint32_t i = base + threadIdx.x;
         const uint32_t v = i < nwg ? wg_count[i] : 0u;
-        uint32_t inc = v;
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            uint32_t o = __shfl_up(inc, d, WAVE);
-            if (lane >= d) inc += o;
-        }
-        if (lane == 63) lds[w] = inc;
-        __syncthreads();
-        uint32_t wbase = 0, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 1024 / WAVE; ++q) {
-            const uint32_t s = lds[q];
-            if (q < w) wbase += s;
-            tot += s;
-        }
-        if (i < nwg) wg_count[i] = (uint32_t)carry + wbase + inc - v;
+        uint32_t tot;
+        const uint32_t ex = block_exclusive_scan<1024>(v, lds, tot);
+        if (i < nwg) wg_count[i] = (uint32_t)carry + ex;
         carry += tot;
-        __syncthreads();
     }
     if (threadIdx.x == 0) {
         *total = carry;
@@ -87,102 +42,59 @@ __global__ void __launch_bounds__(1024) expand_scan_kernel(uint32_t nwg, uint32_
     }
 }
 
+// the expansion keeps a candidate whose opacity is positive
+struct KeepOpacity {
+    using Operand = float;
+    const float* __restrict__ neural_opacity;
+    __device__ float load(int64_t c) const { return neural_opacity[c]; }
+    __device__ bool keep(float no, int64_t) const { return no > 0.0f; }
+};
+
 // ---- mask -> index list (the visible-anchor index of gaussian_renderer/__init__.py:23-29, `t[visible_mask]`): the same
 // count / scan / write scheme on a byte mask; replaces torch.nonzero (a 60 GB/s int64 reduction + a select)
-__global__ void __launch_bounds__(EXP_THREADS)
-mask_count_kernel(int64_t n, const uint8_t* __restrict__ mask, uint32_t* __restrict__ wg_count) {
-    __shared__ uint32_t wsum[EXP_THREADS / WAVE];
-    uint32_t c = 0;
+struct KeepMask {
+    using Operand = uint8_t;
+    const uint8_t* __restrict__ mask;
+    __device__ uint8_t load(int64_t c) const { return mask[c]; }
+    __device__ bool keep(uint8_t m, int64_t) const { return m != 0; }
+};
+
+__global__ void __launch_bounds__(COMPACT_THREADS)
+mask_index_kernel(int64_t n, KeepMask mask, const uint32_t* __restrict__ wg_offset, int64_t* __restrict__ index,
+                  int64_t* __restrict__ inverse) {
+    const CompactRank<KeepMask> c = compact_rank(n, mask, wg_offset);
 #pragma unroll
-    for (int r = 0; r < EXP_ITEMS; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * EXP_PER_WG + r * EXP_THREADS + threadIdx.x;
-        const bool keep = i < n && mask[i] != 0;
-        c += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(keep));
-    }
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) wg_count[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-__global__ void __launch_bounds__(EXP_THREADS)
-mask_index_kernel(int64_t n, const uint8_t* __restrict__ mask, const uint32_t* __restrict__ wg_offset,
-                  int64_t* __restrict__ index, int64_t* __restrict__ inverse) {
-    __shared__ uint32_t wcnt[EXP_ITEMS][EXP_THREADS / WAVE];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    bool keep[EXP_ITEMS];
-    uint32_t below[EXP_ITEMS];
-#pragma unroll
-    for (int r = 0; r < EXP_ITEMS; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * EXP_PER_WG + r * EXP_THREADS + threadIdx.x;
-        keep[r] = i < n && mask[i] != 0;
-        const unsigned long long b = __builtin_amdgcn_ballot_w64(keep[r]);
-        below[r] = lanes_below64(b);
-        if (lane == 0) wcnt[r][w] = (uint32_t)__builtin_popcountll(b);
-    }
-    __syncthreads();
-    uint32_t base = wg_offset[blockIdx.x];
-#pragma unroll
-    for (int r = 0; r < EXP_ITEMS; ++r) {
-        uint32_t before = 0;
-#pragma unroll
-        for (int q = 0; q < EXP_THREADS / WAVE; ++q) before += q < w ? wcnt[r][q] : 0u;
-        const int64_t i = (int64_t)blockIdx.x * EXP_PER_WG + r * EXP_THREADS + threadIdx.x;
-        if (keep[r]) index[base + before + below[r]] = i;
-        if (inverse && i < n) inverse[i] = keep[r] ? (int64_t)(base + before + below[r]) : -1ll;
-#pragma unroll
-        for (int q = 0; q < EXP_THREADS / WAVE; ++q) base += wcnt[r][q];
+    for (int r = 0; r < COMPACT_ITEMS; ++r) {
+        const int64_t i = compact_item(r);
+        if (c.keep[r]) index[c.pos[r]] = i;
+        if (inverse && i < n) inverse[i] = c.keep[r] ? (int64_t)c.pos[r] : -1ll;
     }
 }
 
 // pass 3: expand + compact
-__global__ void __launch_bounds__(EXP_THREADS)
+__global__ void __launch_bounds__(COMPACT_THREADS)
 expand_run_kernel(int64_t n, int k, const float* __restrict__ neural_opacity, const float* __restrict__ color,
                   const float* __restrict__ scale_rot, const float* __restrict__ offsets, int ldo,
                   const float* __restrict__ grid_scaling, const float* __restrict__ anchor,
                   const uint32_t* __restrict__ wg_offset, int32_t* __restrict__ out_index,
                   uint8_t* __restrict__ mask_out, float* __restrict__ xyz, float* __restrict__ color_out,
                   float* __restrict__ opacity, float* __restrict__ scaling, float* __restrict__ rot) {
-    __shared__ uint32_t wcnt[EXP_ITEMS][EXP_THREADS / WAVE];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    bool keep[EXP_ITEMS];
-    uint32_t below[EXP_ITEMS];
-    float no[EXP_ITEMS];      // (all loads first, as in the count kernel)
+    const CompactRank<KeepOpacity> cr = compact_rank(n, KeepOpacity{neural_opacity}, wg_offset);
 #pragma unroll
-    for (int r = 0; r < EXP_ITEMS; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * EXP_PER_WG + r * EXP_THREADS + threadIdx.x;
-        no[r] = neural_opacity[min(i, n - 1)];
-    }
-#pragma unroll
-    for (int r = 0; r < EXP_ITEMS; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * EXP_PER_WG + r * EXP_THREADS + threadIdx.x;
-        keep[r] = i < n && no[r] > 0.0f;
-        const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep[r]);
-        below[r] = lanes_below64(bal);
-        if (lane == 0) wcnt[r][w] = (uint32_t)__builtin_popcountll(bal);
-    }
-    __syncthreads();
-    uint32_t run = wg_offset[blockIdx.x];
-#pragma unroll
-    for (int r = 0; r < EXP_ITEMS; ++r) {
-        uint32_t base = run;
-#pragma unroll
-        for (int q = 0; q < EXP_THREADS / WAVE; ++q) {
-            const uint32_t c = wcnt[r][q];
-            if (q < w) base += c;
-            run += c;
-        }
-        const int64_t i = (int64_t)blockIdx.x * EXP_PER_WG + r * EXP_THREADS + threadIdx.x;
+    for (int r = 0; r < COMPACT_ITEMS; ++r) {
+        const int64_t i = compact_item(r);
         if (i >= n) continue;
-        if (mask_out) mask_out[i] = keep[r];
-        if (!keep[r]) {
+        if (mask_out) mask_out[i] = cr.keep[r];
+        if (!cr.keep[r]) {
             out_index[i] = -1;
             continue;
         }
-        const size_t p = (size_t)base + below[r];
+        const size_t p = cr.pos[r];
         out_index[i] = (int32_t)p;
         const int64_t v = i / k;
         const float* sr = scale_rot + 7 * i;
         const float* gs = grid_scaling + 6 * v;
-        opacity[p] = no[r];
+        opacity[p] = cr.v[r];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             color_out[3 * p + c] = color[3 * i + c];
@@ -287,38 +199,27 @@ expand_backward_kernel(int64_t V, int k, int apw, const float* __restrict__ scal
     }
 }
 
-void launch_expand_count(int64_t n, const float* neural_opacity, uint32_t* wg_count, unsigned long long* total,
-                         unsigned long long* mailbox, unsigned long long seq, hipStream_t st) {
-    const uint32_t nwg = (uint32_t)((n + EXP_PER_WG - 1) / EXP_PER_WG);
-    expand_count_kernel<<<nwg, EXP_THREADS, 0, st>>>(n, neural_opacity, wg_count);
-    expand_scan_kernel<<<1, 1024, 0, st>>>(nwg, wg_count, total, mailbox, seq);
+void launch_expand_count(int64_t n, const float* neural_opacity, const CompactScratch& s, unsigned long long* mailbox,
+                         unsigned long long seq, hipStream_t st) {
+    launch_compact_count(n, KeepOpacity{neural_opacity}, s, mailbox, seq, st);
 }
 
-void launch_mask_count(int64_t n, const uint8_t* mask, uint32_t* wg_count, unsigned long long* total,
-                       unsigned long long* mailbox, unsigned long long seq, hipStream_t st) {
-    const uint32_t nwg = (uint32_t)((n + EXP_PER_WG - 1) / EXP_PER_WG);
-    mask_count_kernel<<<nwg, EXP_THREADS, 0, st>>>(n, mask, wg_count);
-    expand_scan_kernel<<<1, 1024, 0, st>>>(nwg, wg_count, total, mailbox, seq);
-}
-// the scan pass alone, for compactions whose count kernel lives in another file (scene_init.hip)
-void launch_wg_scan(uint32_t nwg, uint32_t* wg_count, unsigned long long* total, unsigned long long* mailbox,
-                    unsigned long long seq, hipStream_t st) {
-    expand_scan_kernel<<<1, 1024, 0, st>>>(nwg, wg_count, total, mailbox, seq);
+void launch_mask_count(int64_t n, const uint8_t* mask, const CompactScratch& s, unsigned long long* mailbox,
+                       unsigned long long seq, hipStream_t st) {
+    launch_compact_count(n, KeepMask{mask}, s, mailbox, seq, st);
 }
 void launch_mask_index(int64_t n, const uint8_t* mask, const uint32_t* wg_offset, int64_t* index, int64_t* inverse,
                        hipStream_t st) {
-    const uint32_t nwg = (uint32_t)((n + EXP_PER_WG - 1) / EXP_PER_WG);
-    mask_index_kernel<<<nwg, EXP_THREADS, 0, st>>>(n, mask, wg_offset, index, inverse);
+    mask_index_kernel<<<(uint32_t)compact_nwg(n), COMPACT_THREADS, 0, st>>>(n, KeepMask{mask}, wg_offset, index, inverse);
 }
 
 void launch_expand_run(int64_t n, int k, const float* neural_opacity, const float* color, const float* scale_rot,
                        const float* offsets, int ldo, const float* grid_scaling, const float* anchor,
                        const uint32_t* wg_offset, int32_t* out_index, uint8_t* mask_out, float* xyz,
                        float* color_out, float* opacity, float* scaling, float* rot, hipStream_t st) {
-    const uint32_t nwg = (uint32_t)((n + EXP_PER_WG - 1) / EXP_PER_WG);
-    expand_run_kernel<<<nwg, EXP_THREADS, 0, st>>>(n, k, neural_opacity, color, scale_rot, offsets, ldo, grid_scaling,
-                                                   anchor, wg_offset, out_index, mask_out, xyz, color_out, opacity,
-                                                   scaling, rot);
+    expand_run_kernel<<<(uint32_t)compact_nwg(n), COMPACT_THREADS, 0, st>>>(n, k, neural_opacity, color, scale_rot, offsets, ldo,
+                                                                            grid_scaling, anchor, wg_offset, out_index, mask_out,
+                                                                            xyz, color_out, opacity, scaling, rot);
 }
 
 void launch_expand_backward(int64_t V, int k, const float* scale_rot, const float* offsets, int ldo,

@@ -8,9 +8,8 @@
 //                   (qx - lo_x) << 42 | (qy - lo_y) << 21 | (qz - lo_z), whose integer order is the lexicographic order
 //                   of (qx, qy, qz) -- what np.unique(axis=0) returns; unpacked (an axis needs more than 21 bits): the
 //                   three integers, for the caller's lexicographic row sort.  12 B read, 8 B written per point.
-//   voxel_unique    on the SORTED keys: head flags (key[i] != key[i-1]), wave ballot + mbcnt compaction with the
-//                   expansion's count / scan / write scheme (expand.hip), decode to float32(q) * v.  8 B read per key in
-//                   each pass, 12 B written per survivor.
+//   voxel_unique    on the SORTED keys: head flags (key[i] != key[i-1]) compacted with the count / scan / write scheme
+//                   of compact.h, decode to float32(q) * v.  8 B read per key in each pass, 12 B written per survivor.
 //   knn3_dist2      mean of the squared distances to the 3 nearest OTHER points, fused: the points come bucketed in a
 //                   uniform grid (knn3_cell_keys, sorted by the caller), one thread per query in cell order walks the
 //                   cube of cells around its own -- each x-run of cells is ONE contiguous range of the sorted points --
@@ -20,19 +19,13 @@
 // Arithmetic order is normative (-ffp-contract=off): e = p_j - p_i, d = (ex*ex + ey*ey) + ez*ez, ((b0 + b1) + b2) / 3.
 // The three smallest VALUES are unique whatever the tie-breaking, so the result is independent of the search order and
 // bit-identical to a brute force.  No atomics.
-#include "common.h"
+#include "compact.h"
 
 #include <math.h>
 
 namespace scr {
 
-constexpr int SI_THREADS = 256;
-constexpr int SI_ITEMS = 4;
-constexpr int SI_PER_WG = SI_THREADS * SI_ITEMS;      // keys per workgroup of the unique passes
-
-__device__ __forceinline__ uint32_t si_lanes_below64(unsigned long long ballot) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
+constexpr int SI_THREADS = 256;                       // block size of the bounds, keys and kNN kernels
 
 // ------------------------------------------------------------------ bounding box
 // min / max of every axis and a non-finite flag, in two passes of plain reductions (no atomics): torch.aminmax(dim=0) of a
@@ -144,58 +137,27 @@ voxel_keys_kernel(int64_t N, const float* __restrict__ pts, float v, int lox, in
     }
 }
 
-__device__ __forceinline__ bool si_head(const int64_t* __restrict__ keys, int64_t i, int64_t n) {
-    // key[i - 1] from a clamped index, so that the load does not sit behind the branch
-    const int64_t k = keys[min(i, n - 1)], kp = keys[min(max(i - 1, (int64_t)0), n - 1)];
-    return i < n && (i == 0 || k != kp);
-}
+// a sorted key is kept where a run of equal keys begins
+struct KeepHead {
+    struct Operand { int64_t k, prev; };
+    const int64_t* __restrict__ keys;
+    __device__ Operand load(int64_t c) const { return {keys[c], keys[max(c - 1, (int64_t)0)]}; }
+    __device__ bool keep(const Operand& o, int64_t i) const { return i == 0 || o.k != o.prev; }
+};
 
-__global__ void __launch_bounds__(SI_THREADS)
-voxel_unique_count_kernel(int64_t n, const int64_t* __restrict__ keys, uint32_t* __restrict__ wg_count) {
-    __shared__ uint32_t wsum[SI_THREADS / WAVE];
-    uint32_t c = 0;
+__global__ void __launch_bounds__(COMPACT_THREADS)
+voxel_unique_write_kernel(int64_t n, KeepHead head, const uint32_t* __restrict__ wg_offset, float v, int lox, int loy, int loz,
+                          float* __restrict__ out) {
+    const CompactRank<KeepHead> c = compact_rank(n, head, wg_offset);
 #pragma unroll
-    for (int r = 0; r < SI_ITEMS; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * SI_PER_WG + r * SI_THREADS + threadIdx.x;
-        c += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(si_head(keys, i, n)));
-    }
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;      // every lane of a wave holds the wave's count
-    __syncthreads();
-    if (threadIdx.x == 0) wg_count[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-__global__ void __launch_bounds__(SI_THREADS)
-voxel_unique_write_kernel(int64_t n, const int64_t* __restrict__ keys, const uint32_t* __restrict__ wg_offset, float v,
-                          int lox, int loy, int loz, float* __restrict__ out) {
-    __shared__ uint32_t wcnt[SI_ITEMS][SI_THREADS / WAVE];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    bool keep[SI_ITEMS];
-    uint32_t below[SI_ITEMS];
-#pragma unroll
-    for (int r = 0; r < SI_ITEMS; ++r) {
-        const int64_t i = (int64_t)blockIdx.x * SI_PER_WG + r * SI_THREADS + threadIdx.x;
-        keep[r] = si_head(keys, i, n);
-        const unsigned long long b = __builtin_amdgcn_ballot_w64(keep[r]);
-        below[r] = si_lanes_below64(b);
-        if (lane == 0) wcnt[r][w] = (uint32_t)__builtin_popcountll(b);
-    }
-    __syncthreads();
-    uint32_t base = wg_offset[blockIdx.x];
-#pragma unroll
-    for (int r = 0; r < SI_ITEMS; ++r) {
-        uint32_t before = 0;
-#pragma unroll
-        for (int q = 0; q < SI_THREADS / WAVE; ++q) before += q < w ? wcnt[r][q] : 0u;
-        const int64_t i = (int64_t)blockIdx.x * SI_PER_WG + r * SI_THREADS + threadIdx.x;
-        if (keep[r]) {
-            const int64_t k = keys[i];
-            const size_t o = 3 * (size_t)(base + before + below[r]);
+    for (int r = 0; r < COMPACT_ITEMS; ++r) {
+        if (c.keep[r]) {
+            const int64_t k = c.v[r].k;
+            const size_t o = 3 * (size_t)c.pos[r];
             out[o] = (float)((int)(k >> 42) + lox) * v;
             out[o + 1] = (float)((int)((k >> 21) & 0x1fffff) + loy) * v;
             out[o + 2] = (float)((int)(k & 0x1fffff) + loz) * v;
         }
-#pragma unroll
-        for (int q = 0; q < SI_THREADS / WAVE; ++q) base += wcnt[r][q];
     }
 }
 
@@ -204,19 +166,15 @@ void launch_voxel_keys(int64_t N, const float* pts, float v, const int32_t* lo, 
                                                                                           packed, out);
 }
 
-size_t voxel_unique_nwg(int64_t n) { return (size_t)((n + SI_PER_WG - 1) / SI_PER_WG); }
-
-void launch_voxel_unique_count(int64_t n, const int64_t* keys, uint32_t* wg_count, unsigned long long* total,
-                               unsigned long long* mailbox, unsigned long long seq, hipStream_t st) {
-    const uint32_t nwg = (uint32_t)voxel_unique_nwg(n);
-    voxel_unique_count_kernel<<<nwg, SI_THREADS, 0, st>>>(n, keys, wg_count);
-    launch_wg_scan(nwg, wg_count, total, mailbox, seq, st);
+void launch_voxel_unique_count(int64_t n, const int64_t* keys, const CompactScratch& s, unsigned long long* mailbox,
+                               unsigned long long seq, hipStream_t st) {
+    launch_compact_count(n, KeepHead{keys}, s, mailbox, seq, st);
 }
 
 void launch_voxel_unique_write(int64_t n, const int64_t* keys, const uint32_t* wg_offset, float v, const int32_t* lo,
                                float* out, hipStream_t st) {
-    voxel_unique_write_kernel<<<(uint32_t)voxel_unique_nwg(n), SI_THREADS, 0, st>>>(n, keys, wg_offset, v, lo[0], lo[1],
-                                                                                   lo[2], out);
+    voxel_unique_write_kernel<<<(uint32_t)compact_nwg(n), COMPACT_THREADS, 0, st>>>(n, KeepHead{keys}, wg_offset, v, lo[0],
+                                                                                    lo[1], lo[2], out);
 }
 
 // ------------------------------------------------------------------ fused 3-NN mean squared distance

@@ -207,7 +207,7 @@ EXPAND_OUTS = ("xyz", "color", "opacity", "scaling", "rot")
 @pytest.mark.parametrize("name,V,k,select,edges", R.EXPAND_CASES, ids=[c[0] for c in R.EXPAND_CASES])
 def test_expand_compact_against_float64(name, V, k, select, edges):
     """k = 1, 5, 10, 33 offsets per anchor; n = V k candidates on both sides of the first workgroup (1024) and of the
-    1024 and 2048 workgroups after which expand_scan_kernel carries its running total into the next chunk; everything
+    1024 and 2048 workgroups after which compact_scan_kernel carries its running total into the next chunk; everything
     kept, nothing kept, every other candidate kept.  The k cases carry the edge rows of f64_refs.expand_inputs: zero
     and 1e-20 quaternions (the clamped branch of the normalisation, forward and backward), scale_rot[:, :3] = +-90
     (saturated sigmoid), neural_opacity +0.0, -0.0 and the smallest subnormal (the mask is `> 0`).  The mask is exact

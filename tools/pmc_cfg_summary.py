@@ -21,7 +21,7 @@ CLASSES = (  # kernel-name prefix -> bench.py kernel class (capi.hip kProfNames)
     ("preprocess_kernel", "preprocess_kernel"), ("plan_scan", "plan_scan_kernel"), ("scatter_kernel", "scatter_kernel"),
     ("tile_sort", "tile_sort_kernel"), ("tile_merge", "tile_sort_kernel"), ("tile_order", "blend_forward_kernel"),
     ("blend_forward", "blend_forward_kernel"), ("blend_backward", "blend_backward_kernel"),
-    ("expand_backward", "expand_backward_kernel"), ("expand_", "expand_kernel"),
+    ("expand_backward", "expand_backward_kernel"), ("expand_", "expand_kernel"), ("compact_", "expand_kernel"),
     ("triplane_forward", "triplane_forward_kernel"), ("plane_row_pairs", "triplane_forward_kernel"),
     ("tp_", "plane_sample_backward_kernels"), ("mlp_heads_forward", "mlp_heads_kernel"),
     ("mlp_heads_", "mlp_heads_backward_kernel"), ("nl_bwd", "norm_linear_backward_kernels"), ("nl_", "norm_linear_kernels"),
