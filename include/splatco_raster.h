@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SCR_ABI_VERSION 34
+#define SCR_ABI_VERSION 35
 #define SCR_TILE 16 /* 16x16-pixel tiles: part of the result contract (tile rects, ranges, sort keys) */
 
 /* The 12 fields of GaussianRasterizationSettings, same order (gaussian_renderer/__init__.py:145-158).
@@ -382,6 +382,34 @@ int scr_pair_l1_forward(int64_t n, const float* gen1, const float* gen2, const f
                         float* out, void* stream);
 int scr_pair_l1_backward(int64_t n, const float* gen1, const float* gen2, const float* real1, const float* real2, const float* g,
                          float* d_gen1, float* d_gen2, void* stream);
+
+/* ---- depth supervision (ABI 35): the aligned inverse-depth L1 of upstream 3DGS (depth_l1_weight, invdepthmap, depth_mask) on
+ * the maps of scr_forward_run.  depth D, alpha A, target g: float32 [H,W]; mask m: absent (mask_kind 0, all ones), float32
+ * weights >= 0 (1) or uint8 / bool with nonzero = 1 (2), read as it is.  H W <= 2^31 - 1.
+ *   valid pixel  m > 0, g, D and A finite, A >= min_alpha and D > 0.  Everything else is a hole: it adds to no sum and gets
+ *                exactly zero gradient, whatever it holds (NaN, Inf): no product with a hole's values is formed.
+ *   prediction   p = A / D (mode 0, "inverse": monocular / inverse-depth priors) or D / A (mode 1, "expected": metric depth), one
+ *                binary32 division.  (With min_alpha = 0 in mode 1 a pixel with A = 0 is valid and divides by zero.)
+ *   alignment    align != 0: (s, t) minimise sum_valid m (s p + t - g)^2: the moments S0 = sum m, Sp = sum m p, Spp = sum m p^2,
+ *                Sg = sum m g, Spg = sum m p g in binary64, s = (S0 Spg - Sp Sg) / (S0 Spp - Sp^2), t = (Sg - s Sp) / S0, solved
+ *                on the device.  Fewer than two valid pixels, or S0 Spp - Sp^2 <= 1e-12 S0 Spp: s = 1, t = 0.  align == 0: s = 1,
+ *                t = 0 and the moment pass is not launched.  (s, t) are constants of the backward pass.
+ *   loss         L = (1 / (H W)) sum_valid m |s p + t - g|: residual and sum in binary64, rounded once.  The divisor counts
+ *                every pixel (upstream's .mean() over the masked map), so a hole never raises another pixel's weight.
+ *   gradient     q = g[0] m s sign(s p + t - g) / (H W) at valid pixels, sign(0) = 0;  mode 0: d_alpha = q / D, d_depth = -q A / D^2;
+ *                mode 1: d_depth = q / A, d_alpha = -q D / A^2.  Every pixel of d_depth / d_alpha is written (0 at holes; either
+ *                may be NULL).  g is read from device memory.
+ * out4 = (L, s, t, n_valid) in DEVICE memory (n_valid as a float: exact below 2^24 valid pixels).  The forward leaves (s, t)
+ * in `scratch`, which the backward reads.  Each workgroup sums a fixed contiguous pixel range and writes one record; one
+ * workgroup folds the records in a fixed order: no atomics, no memset, the same bits run after run whatever the scratch held
+ * before; no host read. */
+size_t scr_depth_loss_scratch_bytes(int32_t H, int32_t W);
+int scr_depth_loss_forward(int32_t H, int32_t W, const float* depth, const float* alpha, const float* target, const void* mask,
+                           int32_t mask_kind /*0 none, 1 f32, 2 u8*/, int32_t mode, int32_t align, float min_alpha, void* scratch,
+                           float* out4, void* stream);
+int scr_depth_loss_backward(int32_t H, int32_t W, const float* depth, const float* alpha, const float* target, const void* mask,
+                            int32_t mask_kind, int32_t mode, float min_alpha, const void* scratch, const float* g, float* d_depth,
+                            float* d_alpha, void* stream);
 
 /* ---- the head of generate_neural_gaussians (gaussian_renderer/__init__.py:23-31) for the reference's sizes (feat 32, 10 offsets):
  * the four visible-anchor gathers, exp(_scaling) and the [V,71] concatenation in one pass.  visible_index[V] int64 = the

@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("SPLATCO_RASTER_LIB", os.path.join(_HERE, "csrc", "lib
 PLAN_NONFINITE_COLOUR, PLAN_LARGE_RECTS, PLAN_ANTIALIASED = 1, 2, 4      # SCR_PLAN_*
 MODE_ANTIALIASED = 1                                # SCR_MODE_* (scr_forward_plan / scr_forward_plan_run)
 PROF_COUNT = 20
-ABI_VERSION = 34
+ABI_VERSION = 35
 FLIP_MAX_RADIUS = 16                                # SCR_FLIP_MAX_RADIUS
 
 (DBG_TILES_TOUCHED, DBG_POINT_OFFSETS, DBG_RANGES, DBG_POINT_LIST, DBG_N_CONTRIB, DBG_FINAL_T, DBG_SPLAT_RECORDS, DBG_QMASK,
@@ -101,6 +101,9 @@ SIGNATURES = [
     ("scr_pair_l1_scratch_bytes", sz, i64),
     ("scr_pair_l1_forward", i32, i64, *[vp] * 7),
     ("scr_pair_l1_backward", i32, i64, *[vp] * 8),
+    ("scr_depth_loss_scratch_bytes", sz, i32, i32),
+    ("scr_depth_loss_forward", i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp),
+    ("scr_depth_loss_backward", i32, i32, i32, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp),
     ("scr_anchor_gather_stat_rows", i32, i64),
     ("scr_anchor_gather_stat_buffer_rows", i64, i64),
     ("scr_anchor_gather", i32, i64, *[vp] * 10, i32, vp, vp),

@@ -876,6 +876,46 @@ int scr_pair_l1_backward(int64_t n, const float* gen1, const float* gen2, const 
     return 0;
 }
 
+// ---- depth supervision on the rasterizer's maps (depth_loss.hip)
+static int depth_loss_args(int32_t H, int32_t W, const void* mask, int32_t mask_kind, int32_t mode, float min_alpha) {
+    if (H < 1 || W < 1) return fail("depth_loss: bad image size H = %d, W = %d", H, W);
+    if ((int64_t)H * W > 2147483647LL) return fail("depth_loss: H W = %lld exceeds 2^31 - 1", (long long)H * W);
+    if (mask_kind < 0 || mask_kind > 2) return fail("depth_loss: mask_kind %d (0 none, 1 float32, 2 uint8)", mask_kind);
+    if (mask_kind != 0 && !mask) return fail("depth_loss: mask is NULL with mask_kind %d", mask_kind);
+    if (mode != 0 && mode != 1) return fail("depth_loss: mode %d (0 inverse, 1 expected)", mode);
+    if (!(min_alpha >= 0.0f) || !(min_alpha <= 3.402823466e38f)) return fail("depth_loss: min_alpha %g must be finite and >= 0", (double)min_alpha);
+    return 0;
+}
+
+size_t scr_depth_loss_scratch_bytes(int32_t H, int32_t W) { return depth_loss_scratch_bytes(H > 0 ? H : 1, W > 0 ? W : 1); }
+
+int scr_depth_loss_forward(int32_t H, int32_t W, const float* depth, const float* alpha, const float* target, const void* mask,
+                           int32_t mask_kind, int32_t mode, int32_t align, float min_alpha, void* scratch, float* out4,
+                           void* stream) {
+    SCR_MARK_FN;
+    if (depth_loss_args(H, W, mask, mask_kind, mode, min_alpha)) return 1;
+    if (!depth || !alpha || !target || !scratch || !out4) return fail("depth_loss: NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    { ProfScope ps_(SCR_PROF_L1_SSIM, st);
+      launch_depth_loss_forward(H, W, depth, alpha, target, mask, mask_kind, mode, align != 0, min_alpha, scratch, out4, st); }
+    CHECK_LAUNCH("depth_loss_residual_kernel", 0, st);
+    return 0;
+}
+
+int scr_depth_loss_backward(int32_t H, int32_t W, const float* depth, const float* alpha, const float* target, const void* mask,
+                            int32_t mask_kind, int32_t mode, float min_alpha, const void* scratch, const float* g, float* d_depth,
+                            float* d_alpha, void* stream) {
+    SCR_MARK_FN;
+    if (depth_loss_args(H, W, mask, mask_kind, mode, min_alpha)) return 1;
+    if (!depth || !alpha || !target || !scratch || !g) return fail("depth_loss: NULL argument");
+    if (!d_depth && !d_alpha) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    { ProfScope ps_(SCR_PROF_L1_SSIM_BACKWARD, st);
+      launch_depth_loss_backward(H, W, depth, alpha, target, mask, mask_kind, mode, min_alpha, scratch, g, d_depth, d_alpha, st); }
+    CHECK_LAUNCH("depth_loss_backward_kernel", 0, st);
+    return 0;
+}
+
 // ---- visible-anchor gather (anchor_gather.hip)
 int32_t scr_anchor_gather_stat_rows(int64_t V) { return anchor_gather_stat_rows(V > 0 ? V : 1); }
 int64_t scr_anchor_gather_stat_buffer_rows(int64_t V) { return anchor_gather_stat_buffer_rows(V > 0 ? V : 1); }

@@ -485,6 +485,12 @@ void launch_pair_l1_forward(int64_t n, const float* g1, const float* g2, const f
                             hipStream_t st);
 void launch_pair_l1_backward(int64_t n, const float* g1, const float* g2, const float* r1, const float* r2, const float* g, float* d1,
                              float* d2, hipStream_t st);
+size_t depth_loss_scratch_bytes(int H, int W);
+void launch_depth_loss_forward(int H, int W, const float* depth, const float* alpha, const float* target, const void* mask,
+                               int mask_kind, int mode, int align, float min_alpha, void* scratch, float* out4, hipStream_t st);
+void launch_depth_loss_backward(int H, int W, const float* depth, const float* alpha, const float* target, const void* mask,
+                                int mask_kind, int mode, float min_alpha, const void* scratch, const float* g, float* d_depth,
+                                float* d_alpha, hipStream_t st);
 void launch_scaling_reg_forward(int64_t P, const float* s, void* scratch, float* out, hipStream_t st);
 void launch_scaling_reg_backward(int64_t P, const float* s, const float* g, float* ds, hipStream_t st);
 void launch_l1_ssim_forward(int C, int H, int W, const float* img1, const float* img2, void* scratch,

@@ -197,3 +197,113 @@ def view_loss(image, gt_image, scaling, lambda_dssim=0.2):
     """Per-view training loss (train.py:192-196): 0.8 L1 + 0.2 (1 - SSIM) + 0.01 mean(prod(scaling))."""
     l1, s = l1_ssim(image, gt_image)
     return (1.0 - lambda_dssim) * l1 + lambda_dssim * (1.0 - s) + 0.01 * scaling_reg(scaling)
+
+
+_DEPTH_MODES = {"inverse": 0, "expected": 1}
+
+
+def _depth_loss_torch(depth, alpha, target, mask, mode, align, min_alpha):
+    """The definition of depth_loss in torch ops: float32 prediction, float64 moments, residual and sum.  Every hole is
+    replaced by finite values BEFORE anything is computed from it, so that neither its value nor 0 * its value reaches a
+    sum or a gradient."""
+    m = torch.ones_like(depth) if mask is None else (mask.to(depth.dtype) if mask.is_floating_point() else (mask != 0).to(depth.dtype))
+    valid = (m > 0) & torch.isfinite(target) & torch.isfinite(depth) & torch.isfinite(alpha) & (alpha >= min_alpha) & (depth > 0)
+    one, zero = torch.ones_like(depth), torch.zeros_like(depth)
+    D, A = torch.where(valid, depth, one), torch.where(valid, alpha, one)
+    g, m = torch.where(valid, target, zero).double(), torch.where(valid, m, zero).double()
+    p = (A / D if mode == "inverse" else D / A).double()
+    n_valid = valid.sum()
+    s, t = p.new_ones(()), p.new_zeros(())
+    if align:
+        with torch.no_grad():
+            S0, Sp, Spp, Sg, Spg = m.sum(), (m * p).sum(), (m * (p * p)).sum(), (m * g).sum(), (m * (p * g)).sum()
+            det = S0 * Spp - Sp * Sp
+            ok = (n_valid >= 2) & (det > 1e-12 * (S0 * Spp))
+            safe = torch.where(ok, det, torch.ones_like(det))
+            s_fit = (S0 * Spg - Sp * Sg) / safe
+            t_fit = (Sg - s_fit * Sp) / torch.where(ok, S0, torch.ones_like(S0))
+            s, t = torch.where(ok, s_fit, s), torch.where(ok, t_fit, t)
+    loss = ((m * ((s * p + t) - g).abs()).sum() / depth.numel()).float()
+    return loss, torch.stack((s.float(), t.float(), n_valid.float())).detach()
+
+
+class _DepthLoss(torch.autograd.Function):
+    """depth_loss on the GPU (csrc/depth_loss.hip): a moment pass and a residual pass with fixed-order float64 sums, one
+    element-wise backward pass; the gradient flows to depth and alpha only."""
+
+    @staticmethod
+    def forward(ctx, depth, alpha, target, mask, mode, align, min_alpha):
+        from . import _C
+        c = lambda t: t.detach().contiguous().float()
+        depth, alpha, target = c(depth), c(alpha), c(target)
+        kind = 0
+        if mask is not None:
+            mask = mask.detach().contiguous()
+            if mask.dtype == torch.bool:
+                mask = mask.view(torch.uint8)           # the same bytes: no conversion pass
+            if mask.dtype != torch.uint8:
+                mask = mask.float()
+            kind = 2 if mask.dtype == torch.uint8 else 1
+        H, W = depth.shape
+        dev = depth.device
+        scratch = torch.empty(_C.lib.scr_depth_loss_scratch_bytes(H, W), dtype=torch.uint8, device=dev)
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _C.check(_C.lib.scr_depth_loss_forward(H, W, depth.data_ptr(), alpha.data_ptr(), target.data_ptr(), _C.ptr(mask), kind,
+                                                   mode, int(align), min_alpha, scratch.data_ptr(), out.data_ptr(), _C.stream(dev)))
+        ctx.save_for_backward(depth, alpha, target, mask, scratch)
+        ctx.args = (kind, mode, min_alpha)
+        stats = out[1:]
+        ctx.mark_non_differentiable(stats)
+        return out[0], stats
+
+    @staticmethod
+    def backward(ctx, g, _):
+        from . import _C
+        depth, alpha, target, mask, scratch = ctx.saved_tensors
+        kind, mode, min_alpha = ctx.args
+        H, W = depth.shape
+        dev = depth.device
+        g = g.contiguous().float().reshape(1)
+        dd = torch.empty_like(depth) if ctx.needs_input_grad[0] else None
+        da = torch.empty_like(alpha) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(dev):
+            _C.check(_C.lib.scr_depth_loss_backward(H, W, depth.data_ptr(), alpha.data_ptr(), target.data_ptr(), _C.ptr(mask), kind,
+                                                    mode, min_alpha, scratch.data_ptr(), g.data_ptr(),
+                                                    None if dd is None else dd.data_ptr(), None if da is None else da.data_ptr(),
+                                                    _C.stream(dev)))
+        return dd, da, None, None, None, None, None
+
+
+def depth_loss(depth, alpha, target, mask=None, mode="inverse", align=True, min_alpha=0.5, return_stats=False):
+    """Depth supervision on the rasterizer's maps (render(aux=True): out["depth"] = sum w z, out["alpha"] = sum w), the
+    aligned inverse-depth L1 of upstream 3DGS (depth_l1_weight, invdepthmap, depth_mask).  All maps are [H, W].
+
+    A pixel is valid where mask > 0 (absent: everywhere; float weights >= 0, or bool / uint8 with nonzero = 1), target,
+    depth and alpha are finite, alpha >= min_alpha and depth > 0; every other pixel is a hole that adds nothing to the loss
+    and gets exactly zero gradient, whatever it holds.  The prediction is p = alpha / depth (mode "inverse": monocular or
+    inverse-depth priors) or depth / alpha (mode "expected": metric depth).  With align=True the scale and shift (s, t) that
+    minimise sum mask (s p + t - target)^2 over the valid pixels are solved in closed form in float64; they are CONSTANTS of
+    the backward pass (detached: no gradient flows through the fit), and (1, 0) where the fit is degenerate (fewer than two
+    valid pixels, or p constant).  The loss is sum_valid mask |s p + t - target| / (H W): the mean over ALL pixels, so a
+    hole never raises the weight of the others.
+
+    On the GPU this is the fused op of csrc/depth_loss.hip: float64 sums in a fixed order (the same bits run after run), no
+    host read; the gradient flows to depth and alpha.  On CPU tensors, and where target or mask wants a gradient, the same
+    definition runs in torch ops.  return_stats=True: also the detached device tensor (s, t, n_valid)."""
+    if mode not in _DEPTH_MODES:
+        raise ValueError(f"depth_loss: mode {mode!r} is not one of {sorted(_DEPTH_MODES)}")
+    min_alpha = float(min_alpha)
+    if not (0.0 <= min_alpha < float("inf")):
+        raise ValueError(f"depth_loss: min_alpha {min_alpha} must be finite and >= 0")
+    if depth.dim() != 2 or depth.numel() == 0:
+        raise ValueError(f"depth_loss: depth {tuple(depth.shape)} is not a non-empty [H, W] map")
+    for name, x in (("alpha", alpha), ("target", target), ("mask", mask)):
+        if x is not None and (x.shape != depth.shape or x.device != depth.device):
+            raise ValueError(f"depth_loss: {name} {tuple(x.shape)} on {x.device} does not match depth {tuple(depth.shape)} on {depth.device}")
+    wants = torch.is_grad_enabled() and (target.requires_grad or (mask is not None and mask.requires_grad))
+    if depth.is_cuda and not wants:
+        loss, stats = _DepthLoss.apply(depth, alpha, target, mask, _DEPTH_MODES[mode], bool(align), min_alpha)
+    else:
+        loss, stats = _depth_loss_torch(depth.float(), alpha.float(), target.float(), mask, mode, bool(align), min_alpha)
+    return (loss, stats) if return_stats else loss

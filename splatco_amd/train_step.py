@@ -10,7 +10,7 @@ train.py:219-236, logging and checkpoints are out of scope
 import torch
 import torch.distributed as dist
 
-from .losses import view_loss
+from .losses import depth_loss, view_loss
 from .multiview import GradArena, allreduce_gradients, collectives_on, consistency_loss, shard_views, world_info
 from .renderer import prefilter_voxel, render
 from .tv import tv_due
@@ -55,7 +55,8 @@ def sync_densification_stats(densifier, n_views, out, vis, device):
 
 
 def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, bucket=None,
-                       consistency_weight=0.0, densifier=None, arena=None, iteration=None, tv_weight=0.0, sparse_adam=False):
+                       consistency_weight=0.0, densifier=None, arena=None, iteration=None, tv_weight=0.0, sparse_adam=False,
+                       depth_targets=None, depth_masks=None, depth_weight=0.0, depth_options=None):
     """views / gt_images: the identically ordered mv view list every rank holds; gt_images[i] is the
     [3,H,W] target of views[i] (host or device).  densifier: a splatco_amd.densify.AnchorDensifier; its
     accumulators receive the statistics of the LAST view of the list on every rank (sync_densification_stats).
@@ -74,6 +75,11 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
     `optimizer.step(visible=union)`, which needs an adam.FusedAdam whose per-anchor groups carry "row_sparse": True (the
     anchors no view sees have exactly zero gradient rows; the dense step would still stream them and move them along stale
     momentum).  One rank only.
+    depth_targets / depth_masks / depth_weight / depth_options: depth supervision (losses.depth_loss).  With depth_weight > 0,
+    depth_targets[i] is the [H,W] target of views[i] (host or device), depth_masks[i] (optional list; an entry may be None) its
+    mask; every view is rendered with aux=True and depth_weight * depth_loss(out["depth"], out["alpha"], target, mask,
+    **depth_options) is added to that view's loss.  Both lists are sharded as gt_images.  With the default weight of 0 the
+    step is the one without these arguments, bit for bit: render() is called without aux and nothing else runs.
     Returns (local loss sum, last render dict, bucket or arena buffer)."""
     from .adam import FusedAdam, ShardedFusedAdam
     if sparse_adam:
@@ -86,6 +92,13 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
             raise NotImplementedError("collaborative_step: sparse_adam on more than one rank is not built: every rank must step with "
                                       "the SAME union, all-reduced over the ranks' views, and the sharded optimizer's flat slices "
                                       "need a row origin")
+    use_depth = depth_weight > 0
+    if use_depth:
+        if depth_targets is None:
+            raise ValueError("collaborative_step: depth_weight > 0 needs depth_targets")
+        for name, lst in (("depth_targets", depth_targets), ("depth_masks", depth_masks)):
+            if lst is not None and len(lst) != len(views):
+                raise ValueError(f"collaborative_step: {len(lst)} {name} for {len(views)} views")
     params = arena.params if arena is not None else [p for p in pc.parameters() if p.requires_grad]
     if arena is not None:
         # the per-anchor gradients (99 % of the arena) are written in place by the gather's backward kernel; the sink is
@@ -110,6 +123,8 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
     sharded = isinstance(optimizer, ShardedFusedAdam)
     want_union = arena is not None and arena.sparse_rows and arena.active      # (also under the sharded optimizer: set_row_union)
     union = None
+    local_targets = shard_views(depth_targets) if use_depth else None
+    local_masks = shard_views(depth_masks) if use_depth and depth_masks is not None else None
     try:
         # (stage(): opt-in roctx ranges, _C.markers_enable / SPLATCO_MARKERS=1; nothing when off)
         for k, (cam, gt) in enumerate(zip(shard_views(views), shard_views(gt_images))):
@@ -118,10 +133,15 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
             if want_union or sparse_adam:
                 union = vis.clone() if union is None else union.logical_or_(vis)
             with stage("render"):
-                out = render(cam, pc, pipe, bg_color, visible_mask=vis, retain_grad=True)
+                out = render(cam, pc, pipe, bg_color, visible_mask=vis, retain_grad=True, **({"aux": True} if use_depth else {}))
             with stage("loss"):
                 gt = gt.to(out["render"].device, non_blocking=True)
                 loss = view_loss(out["render"], gt, out["scaling"])
+                if use_depth:
+                    dev_k = out["render"].device
+                    mask = None if local_masks is None or local_masks[k] is None else local_masks[k].to(dev_k, non_blocking=True)
+                    loss = loss + depth_weight * depth_loss(out["depth"], out["alpha"], local_targets[k].to(dev_k, non_blocking=True),
+                                                            mask, **(depth_options or {}))
                 total = loss if total is None else total + loss
             if consistency_weight:
                 rendered.append((rank + k * world, out["render"], gt))
