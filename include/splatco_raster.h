@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SCR_ABI_VERSION 35
+#define SCR_ABI_VERSION 36
 #define SCR_TILE 16 /* 16x16-pixel tiles: part of the result contract (tile rects, ranges, sort keys) */
 
 /* The 12 fields of GaussianRasterizationSettings, same order (gaussian_renderer/__init__.py:145-158).
@@ -590,14 +590,23 @@ typedef struct scr_tv_plane {
 } scr_tv_plane;
 int scr_tv_add_grad(int32_t n_planes, const scr_tv_plane* planes, void* stream);
 
-/* ---- k nearest neighbours for GaussianModel.compute_curvature (scene/gaussian_model.py:1092-1110: sklearn on the host +
- * a Python loop over the anchors there).  The caller buckets the N points into a uniform grid (grid_host[7] = x0, y0, z0,
- * cell size h, nx, ny, nz -- HOST floats), sorts them by cell (sorted_pts[N,3], sorted_id[N] = original index,
- * cell_start[nx*ny*nz + 1]); scr_knn writes out_idx[N,k]: the k nearest OTHER points of every point, nearest first,
- * indexed by original point (k <= 16; exact).  scr_knn_curvature: lambda_min / trace of the covariance of those
- * neighbours (mean-centred, / (k-1)), per point. */
+/* ---- exact nearest neighbours over a uniform grid of cells (one search since ABI 36; kernels: csrc/knn_grid.h, host half:
+ * splatco_amd/knn_grid.py).  grid_host[8] = x0, y0, z0, cell size h, nx, ny, nz, slack (HOST floats; slack >= the rounding
+ * error of the cell function, as a length; at most 2^31 - 2 cells, N < 2^31).  scr_knn_cell_keys writes every point's cell
+ * (z * ny + y) * nx + x; the caller sorts the points by it (sorted_pts[N,3], sorted_id[N] = original index,
+ * cell_start[nx*ny*nz + 1]) and hands them to either search:
+ * scr_knn, for GaussianModel.compute_curvature (scene/gaussian_model.py:1092-1110: sklearn on the host + a Python loop over
+ * the anchors there): out_idx[N,k] = the k nearest OTHER points of every point, nearest first, indexed by original point
+ * (1 <= k <= 16, N > k; exact).
+ * scr_knn3_dist2, simple_knn's distCUDA2: out[N] = mean of the squared distances to the 3 nearest OTHER points (exact
+ * duplicates count, at 0): d = (ex*ex + ey*ey) + ez*ez, ((b0 + b1) + b2) / 3 of the three smallest, no contraction -- equal
+ * to a brute force bit for bit.  N >= 4.
+ * scr_knn_curvature: lambda_min / trace of the covariance of the neighbours idx[N,k] (mean-centred, / (k-1)), per point. */
+int scr_knn_cell_keys(int64_t N, const float* grid_host, const float* points, int64_t* keys, void* stream);
 int scr_knn(int64_t N, int32_t k, const float* grid_host, const float* sorted_pts, const int64_t* sorted_id,
             const int32_t* cell_start, int64_t* out_idx, void* stream);
+int scr_knn3_dist2(int64_t N, const float* grid_host, const float* sorted_pts, const int64_t* sorted_id,
+                   const int32_t* cell_start, float* out, void* stream);
 int scr_knn_curvature(int64_t N, int32_t k, const float* points, const int64_t* idx, float* curvature, void* stream);
 
 /* ---- a scene from a point cloud (ABI 29): GaussianModel.create_from_pcd (scene/gaussian_model.py:472-508) without the
@@ -612,13 +621,7 @@ int scr_knn_curvature(int64_t N, int32_t k, const float* points, const int64_t* 
  * bounding box and sorts the keys.
  * scr_voxel_unique_plan counts the distinct keys of the SORTED key array (one stream synchronisation, like
  * scr_expand_plan; scratch: scr_voxel_unique_scratch_bytes(N) bytes, passed on to _run); scr_voxel_unique_run writes
- * out_xyz[num_unique,3] = float(q) * voxel_size in key order.
- *
- * scr_knn3_dist2: out[N] = mean of the squared distances to the 3 nearest OTHER points (exact duplicates count, at 0):
- * d = (ex*ex + ey*ey) + ez*ez, ((b0 + b1) + b2) / 3 of the three smallest, no contraction -- equal to a brute force bit
- * for bit.  grid_host[8] = x0, y0, z0, cell size h, nx, ny, nz, slack (HOST floats; slack >= the rounding error of the
- * cell function, as a length); scr_knn3_cell_keys writes every point's cell (z * ny + y) * nx + x; the caller sorts the
- * points by it (sorted_pts[N,3], sorted_id[N] = original index, cell_start[nx*ny*nz + 1]).  N >= 4. */
+ * out_xyz[num_unique,3] = float(q) * voxel_size in key order.  The 3-NN distances are scr_knn3_dist2, above. */
 size_t scr_points_bounds_scratch_bytes(int64_t N);
 int scr_points_bounds(int64_t N, const float* points, void* scratch, float* out7, void* stream);
 size_t scr_voxel_unique_scratch_bytes(int64_t N);
@@ -627,9 +630,6 @@ int scr_voxel_keys(int64_t N, const float* points, float voxel_size, const int32
 int scr_voxel_unique_plan(int64_t N, const int64_t* sorted_keys, void* scratch, int64_t* num_unique_host, void* stream);
 int scr_voxel_unique_run(int64_t N, const int64_t* sorted_keys, const void* scratch, float voxel_size,
                          const int32_t* lo_host, float* out_xyz, void* stream);
-int scr_knn3_cell_keys(int64_t N, const float* grid_host, const float* points, int64_t* keys, void* stream);
-int scr_knn3_dist2(int64_t N, const float* grid_host, const float* sorted_pts, const int64_t* sorted_id,
-                   const int32_t* cell_start, float* out, void* stream);
 
 /* ---- measurement aid: a float4 grid-stride copy of `bytes` bytes (src -> dst, device pointers).  bench.py times it to
  * quote the HBM bandwidth a streaming kernel reaches on the box next to the 8 TB/s datasheet figure. */

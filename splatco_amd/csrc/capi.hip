@@ -1208,15 +1208,44 @@ int scr_tv_add_grad(int32_t n_planes, const scr_tv_plane* planes, void* stream) 
     return 0;
 }
 
+// the one grid descriptor of scr_knn_cell_keys, scr_knn and scr_knn3_dist2: the kernels index points and cells with int
+static int check_knn_grid(const char* who, int64_t N, const float* g) {
+    if (N <= 0 || N >= (1ll << 31)) return fail("%s: need 0 < N < 2^31", who);
+    if (!g) return fail("%s: grid_host is NULL", who);
+    if (!(g[3] > 0.0f) || g[4] < 1 || g[5] < 1 || g[6] < 1 || !(g[7] >= 0.0f)) return fail("%s: bad grid", who);
+    if ((double)g[4] * g[5] * g[6] >= 2147483647.0) return fail("%s: more than 2^31 - 2 cells", who);
+    return 0;
+}
+
+int scr_knn_cell_keys(int64_t N, const float* grid_host, const float* points, int64_t* keys, void* stream) {
+    SCR_MARK_FN;
+    if (check_knn_grid("scr_knn_cell_keys", N, grid_host)) return 1;
+    if (!points || !keys) return fail("scr_knn_cell_keys: NULL argument");
+    launch_knn_cell_keys(N, grid_host, points, keys, (hipStream_t)stream);
+    CHECK_LAUNCH("knn_cell_keys_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
 int scr_knn(int64_t N, int32_t k, const float* grid_host, const float* sorted_pts, const int64_t* sorted_id,
             const int32_t* cell_start, int64_t* out_idx, void* stream) {
     SCR_MARK_FN;
-    if (N <= 0 || k <= 0 || k > 16) return fail("scr_knn: need N > 0 and 1 <= k <= 16");
+    if (check_knn_grid("scr_knn", N, grid_host)) return 1;
+    if (k <= 0 || k > 16) return fail("scr_knn: need 1 <= k <= 16");
     if (N <= k) return fail("scr_knn: fewer than k + 1 points");
-    if (!grid_host || !sorted_pts || !sorted_id || !cell_start || !out_idx) return fail("NULL argument");
-    if (!(grid_host[3] > 0.0f) || grid_host[4] < 1 || grid_host[5] < 1 || grid_host[6] < 1) return fail("bad grid");
+    if (!sorted_pts || !sorted_id || !cell_start || !out_idx) return fail("scr_knn: NULL argument");
     launch_knn(N, k, grid_host, sorted_pts, sorted_id, cell_start, out_idx, (hipStream_t)stream);
     CHECK_LAUNCH("knn_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+int scr_knn3_dist2(int64_t N, const float* grid_host, const float* sorted_pts, const int64_t* sorted_id,
+                   const int32_t* cell_start, float* out, void* stream) {
+    SCR_MARK_FN;
+    if (check_knn_grid("scr_knn3_dist2", N, grid_host)) return 1;
+    if (N < 4) return fail("scr_knn3_dist2: fewer than 4 points");
+    if (!sorted_pts || !sorted_id || !cell_start || !out) return fail("scr_knn3_dist2: NULL argument");
+    launch_knn3_dist2(N, grid_host, sorted_pts, sorted_id, cell_start, out, (hipStream_t)stream);
+    CHECK_LAUNCH("knn3_dist2_kernel", 0, (hipStream_t)stream);
     return 0;
 }
 
@@ -1280,34 +1309,6 @@ int scr_voxel_unique_run(int64_t N, const int64_t* sorted_keys, const void* scra
     if (!sorted_keys || !scratch || !out_xyz) return fail("scr_voxel_unique_run: NULL argument");
     launch_voxel_unique_write(N, sorted_keys, (const uint32_t*)scratch, voxel_size, lo_host, out_xyz, (hipStream_t)stream);
     CHECK_LAUNCH("voxel_unique_write_kernel", 0, (hipStream_t)stream);
-    return 0;
-}
-
-static int check_knn3_grid(const char* who, int64_t N, const float* g) {
-    if (N <= 0 || N >= (1ll << 31)) return fail("%s: need 0 < N < 2^31", who);
-    if (!g) return fail("%s: grid_host is NULL", who);
-    if (!(g[3] > 0.0f) || g[4] < 1 || g[5] < 1 || g[6] < 1 || !(g[7] >= 0.0f)) return fail("%s: bad grid", who);
-    if ((double)g[4] * g[5] * g[6] >= 2147483647.0) return fail("%s: more than 2^31 - 2 cells", who);
-    return 0;
-}
-
-int scr_knn3_cell_keys(int64_t N, const float* grid_host, const float* points, int64_t* keys, void* stream) {
-    SCR_MARK_FN;
-    if (check_knn3_grid("scr_knn3_cell_keys", N, grid_host)) return 1;
-    if (!points || !keys) return fail("scr_knn3_cell_keys: NULL argument");
-    launch_knn3_cell_keys(N, grid_host, points, keys, (hipStream_t)stream);
-    CHECK_LAUNCH("knn3_cell_keys_kernel", 0, (hipStream_t)stream);
-    return 0;
-}
-
-int scr_knn3_dist2(int64_t N, const float* grid_host, const float* sorted_pts, const int64_t* sorted_id,
-                   const int32_t* cell_start, float* out, void* stream) {
-    SCR_MARK_FN;
-    if (check_knn3_grid("scr_knn3_dist2", N, grid_host)) return 1;
-    if (N < 4) return fail("scr_knn3_dist2: fewer than 4 points");
-    if (!sorted_pts || !sorted_id || !cell_start || !out) return fail("scr_knn3_dist2: NULL argument");
-    launch_knn3_dist2(N, grid_host, sorted_pts, sorted_id, cell_start, out, (hipStream_t)stream);
-    CHECK_LAUNCH("knn3_dist2_kernel", 0, (hipStream_t)stream);
     return 0;
 }
 

@@ -428,7 +428,7 @@ void launch_anchor_gather_backward(int64_t N, int64_t V, const int64_t* inv, con
                                    const float* d_g_fea, int ldg, float* g_feat, float* g_anchor, float* g_offset,
                                    float* g_scaling, int accumulate, const float* nl_coef, const float* nl_dy, int nl_lddy,
                                    const float* nl_x, int nl_ldx, hipStream_t st);
-void launch_knn(int64_t N, int k, const float* grid9, const float* sorted_pts, const int64_t* sorted_id,
+void launch_knn(int64_t N, int k, const float* grid8, const float* sorted_pts, const int64_t* sorted_id,
                 const int32_t* cell_start, int64_t* out_idx, hipStream_t st);
 void launch_knn_curvature(int64_t N, int k, const float* pts, const int64_t* idx, float* curvature, hipStream_t st);
 // scene_init.hip: voxelisation and the fused 3-NN mean squared distance
@@ -437,7 +437,7 @@ void launch_points_bounds(int64_t N, const float* pts, float* partial, float* ou
 void launch_voxel_keys(int64_t N, const float* pts, float v, const int32_t* lo, int packed, int64_t* out, hipStream_t st);
 void launch_voxel_unique_write(int64_t n, const int64_t* keys, const uint32_t* wg_offset, float v, const int32_t* lo,
                                float* out, hipStream_t st);
-void launch_knn3_cell_keys(int64_t N, const float* grid8, const float* pts, int64_t* keys, hipStream_t st);
+void launch_knn_cell_keys(int64_t N, const float* grid8, const float* pts, int64_t* keys, hipStream_t st);
 void launch_knn3_dist2(int64_t N, const float* grid8, const float* sorted_pts, const int64_t* sorted_id,
                        const int32_t* cell_start, float* out, hipStream_t st);
 size_t norm_linear_scratch_bytes(int64_t V);

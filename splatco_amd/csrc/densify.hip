@@ -15,7 +15,7 @@
 //
 // Every (anchor, slot) is touched by exactly one thread: no atomics, bit-reproducible.  HBM-bound:
 // compute reads 8 B per candidate + 9 B per rendered Gaussian, apply 8 B per candidate read-modify-write.
-#include "common.h"
+#include "knn_grid.h"
 
 namespace scr {
 
@@ -173,25 +173,45 @@ void launch_statis_apply(int64_t V, int k, const int64_t* visible_index, const f
 
 // ------------------------------------------------------------------ k nearest neighbours (compute_curvature)
 // GaussianModel.compute_curvature (scene/gaussian_model.py:1092-1110) asks sklearn for the k+1 nearest anchors of every
-// anchor on the HOST and loops over the anchors in Python.  Here: the anchors are bucketed into a uniform grid (cell
-// keys sorted by the caller with torch.sort, cell_start from the sorted keys), one thread per query walks the cells of
-// growing cubes around its own cell keeping its k best candidates in registers (insertion into a sorted list), and
-// stops as soon as the k-th best distance is inside the cube already searched.  Exact (same neighbour SET as a brute
-// force search; ties at equal distance aside).  knn_curvature_kernel then forms the neighbours' covariance and its
-// eigenvalues (closed form for a symmetric 3x3, in fp64) and returns lambda_min / sum(lambda).
+// anchor on the HOST and loops over the anchors in Python.  Here: the anchors are bucketed into a uniform grid and every
+// query runs the grid search of knn_grid.h, keeping its k best candidates in registers (insertion into a sorted list).
+// Exact (same neighbour SET as a brute force search; ties at equal distance aside).  knn_curvature_kernel then forms
+// the neighbours' covariance and its eigenvalues (closed form for a symmetric 3x3, in fp64) and returns
+// lambda_min / sum(lambda).
 namespace scr {
 
 constexpr int KNN_MAX_K = 16;
 
-struct KnnGrid {
-    float x0, y0, z0, inv_h, h;
-    int nx, ny, nz;
+// the K best (distance, sorted position) pairs so far, ascending, of which the first k <= K count (registers: every
+// index below is a compile-time constant)
+template <int K>
+struct BestK {
+    float bd[K];
+    int bp[K];
+    float kth = INFINITY;      // bd[k - 1]
+    int k;
+    __device__ __forceinline__ explicit BestK(int k_) : k(k_) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) { bd[j] = INFINITY; bp[j] = -1; }
+    }
+    __device__ __forceinline__ void offer(float d, int p) {
+        if (d < kth) {
+            float cd = d;                    // insertion into the ascending list
+            int cp = p;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const bool sw = cd < bd[j];
+                const float td = bd[j];
+                const int tp = bp[j];
+                bd[j] = sw ? cd : td; bp[j] = sw ? cp : tp;
+                cd = sw ? td : cd; cp = sw ? tp : cp;
+            }
+#pragma unroll
+            for (int j = 0; j < K; ++j) if (j == k - 1) kth = bd[j];
+        }
+    }
+    __device__ __forceinline__ float worst() const { return kth; }
 };
-
-__device__ __forceinline__ int knn_cell(float v, float lo, float inv_h, int n) {
-    const int c = (int)floorf((v - lo) * inv_h);
-    return c < 0 ? 0 : (c >= n ? n - 1 : c);
-}
 
 // sorted_pts: points in cell order (float x,y,z per point), sorted_id: original index of every sorted point,
 // cell_start[ncells + 1].  out_idx[q * k + j] = original index of the j-th nearest OTHER point of query q (by
@@ -202,60 +222,12 @@ knn_kernel(int64_t N, int k, KnnGrid gr, const float* __restrict__ sorted_pts, c
            const int32_t* __restrict__ cell_start, int64_t* __restrict__ out_idx) {
     const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;      // position in cell order: neighbours in memory
     if (s >= N) return;
-    const float qx = sorted_pts[3 * s], qy = sorted_pts[3 * s + 1], qz = sorted_pts[3 * s + 2];
-    const int cx = knn_cell(qx, gr.x0, gr.inv_h, gr.nx), cy = knn_cell(qy, gr.y0, gr.inv_h, gr.ny),
-              cz = knn_cell(qz, gr.z0, gr.inv_h, gr.nz);
-    float bd[K];          // the K best so far, ascending (K >= k; registers: every index below is a compile-time constant)
-    int64_t bi[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) { bd[j] = 3.0e38f; bi[j] = -1; }
-    float kth = 3.0e38f;  // bd[k - 1]
-    const int rmax = max(gr.nx, max(gr.ny, gr.nz));
-    // distance from the query to the faces of its own cell: the searched cube of radius r reaches at least r*h + that
-    const float fx = (qx - gr.x0) * gr.inv_h - (float)cx, fy = (qy - gr.y0) * gr.inv_h - (float)cy,
-                fz = (qz - gr.z0) * gr.inv_h - (float)cz;
-    const float margin = gr.h * fminf(fminf(fminf(fx, 1.0f - fx), fminf(fy, 1.0f - fy)), fminf(fz, 1.0f - fz));
-    for (int r = 0; r <= rmax; ++r) {
-        for (int dz = -r; dz <= r; ++dz) {
-            const int z = cz + dz;
-            if (z < 0 || z >= gr.nz) continue;
-            for (int dy = -r; dy <= r; ++dy) {
-                const int y = cy + dy;
-                if (y < 0 || y >= gr.ny) continue;
-                const bool shell_yz = (dz == -r || dz == r || dy == -r || dy == r);
-                for (int dx = -r; dx <= r; dx += (shell_yz || r == 0 ? 1 : 2 * r)) {     // only the cube's surface
-                    const int x = cx + dx;
-                    if (x < 0 || x >= gr.nx) continue;
-                    const int cell = (z * gr.ny + y) * gr.nx + x;
-                    for (int p = cell_start[cell]; p < cell_start[cell + 1]; ++p) {
-                        if (p == s) continue;
-                        const float ex = sorted_pts[3 * (int64_t)p] - qx, ey = sorted_pts[3 * (int64_t)p + 1] - qy,
-                                    ez = sorted_pts[3 * (int64_t)p + 2] - qz;
-                        const float d = (ex * ex + ey * ey) + ez * ez;
-                        if (d < kth) {
-                            float cd = d;                    // insertion into the ascending list
-                            int64_t ci = sorted_id[p];
-#pragma unroll
-                            for (int j = 0; j < K; ++j) {
-                                const bool sw = cd < bd[j];
-                                const float td = bd[j];
-                                const int64_t ti = bi[j];
-                                bd[j] = sw ? cd : td; bi[j] = sw ? ci : ti;
-                                cd = sw ? td : cd; ci = sw ? ti : ci;
-                            }
-#pragma unroll
-                            for (int j = 0; j < K; ++j) if (j == k - 1) kth = bd[j];
-                        }
-                    }
-                }
-            }
-        }
-        const float reach = fmaxf(0.0f, (float)r * gr.h + margin);      // everything closer than this has been seen
-        if (kth <= reach * reach) break;
-    }
+    BestK<K> best(k);
+    knn_grid_search(s, gr, sorted_pts, cell_start, best);
     const int64_t q = sorted_id[s];
 #pragma unroll
-    for (int j = 0; j < K; ++j) if (j < k) out_idx[q * k + j] = bi[j];
+    for (int j = 0; j < K; ++j)      // -1: fewer than k points at a finite squared distance
+        if (j < k) out_idx[q * k + j] = best.bp[j] < 0 ? -1 : sorted_id[best.bp[j]];
 }
 
 // curvature[q] = lambda_min / (lambda_0 + lambda_1 + lambda_2) of cov = C^T C / (k - 1), C = neighbours - their mean
@@ -296,11 +268,9 @@ knn_curvature_kernel(int64_t N, int k, const float* __restrict__ pts, const int6
     curvature[q] = (float)(lmin / tr);
 }
 
-void launch_knn(int64_t N, int k, const float* grid9, const float* sorted_pts, const int64_t* sorted_id,
+void launch_knn(int64_t N, int k, const float* grid8, const float* sorted_pts, const int64_t* sorted_id,
                 const int32_t* cell_start, int64_t* out_idx, hipStream_t st) {
-    KnnGrid g;
-    g.x0 = grid9[0]; g.y0 = grid9[1]; g.z0 = grid9[2]; g.h = grid9[3]; g.inv_h = 1.0f / grid9[3];
-    g.nx = (int)grid9[4]; g.ny = (int)grid9[5]; g.nz = (int)grid9[6];
+    const KnnGrid g = knn_grid(grid8);
     const unsigned grid = (unsigned)((N + 255) / 256);
     if (k <= 10) knn_kernel<10><<<grid, 256, 0, st>>>(N, k, g, sorted_pts, sorted_id, cell_start, out_idx);   // the reference's k
     else knn_kernel<KNN_MAX_K><<<grid, 256, 0, st>>>(N, k, g, sorted_pts, sorted_id, cell_start, out_idx);

@@ -10,16 +10,15 @@
 //                   three integers, for the caller's lexicographic row sort.  12 B read, 8 B written per point.
 //   voxel_unique    on the SORTED keys: head flags (key[i] != key[i-1]) compacted with the count / scan / write scheme
 //                   of compact.h, decode to float32(q) * v.  8 B read per key in each pass, 12 B written per survivor.
-//   knn3_dist2      mean of the squared distances to the 3 nearest OTHER points, fused: the points come bucketed in a
-//                   uniform grid (knn3_cell_keys, sorted by the caller), one thread per query in cell order walks the
-//                   cube of cells around its own -- each x-run of cells is ONE contiguous range of the sorted points --
-//                   keeping three distances in registers, and grows the cube shell by shell until the third-best
-//                   distance lies inside it.  Writes 4 B per point; no index array, no gather.
+//   knn_cell_keys   every point's cell of the uniform grid of knn_grid.h, for this file's search and for densify.hip's.
+//   knn3_dist2      mean of the squared distances to the 3 nearest OTHER points, fused: the grid search of knn_grid.h
+//                   keeping three distances in registers.  Writes 4 B per point; no index array, no gather.
 //
 // Arithmetic order is normative (-ffp-contract=off): e = p_j - p_i, d = (ex*ex + ey*ey) + ez*ez, ((b0 + b1) + b2) / 3.
 // The three smallest VALUES are unique whatever the tie-breaking, so the result is independent of the search order and
 // bit-identical to a brute force.  No atomics.
 #include "compact.h"
+#include "knn_grid.h"
 
 #include <math.h>
 
@@ -178,95 +177,48 @@ void launch_voxel_unique_write(int64_t n, const int64_t* keys, const uint32_t* w
 }
 
 // ------------------------------------------------------------------ fused 3-NN mean squared distance
-struct Knn3Grid {
-    float x0, y0, z0, inv_h, h, slack;
-    int nx, ny, nz;
-};
-
-static Knn3Grid knn3_grid(const float* g8) {
-    Knn3Grid g;
-    g.x0 = g8[0]; g.y0 = g8[1]; g.z0 = g8[2]; g.h = g8[3]; g.inv_h = 1.0f / g8[3];
-    g.nx = (int)g8[4]; g.ny = (int)g8[5]; g.nz = (int)g8[6]; g.slack = g8[7];
-    return g;
-}
-
-// the ONE cell function: the bucketing kernel and the search both call it, so a point's bucket is the cell the search
-// believes it is in
-__device__ __forceinline__ int knn3_cell(float v, float lo, float inv_h, int n) {
-    const int c = (int)floorf((v - lo) * inv_h);
-    return c < 0 ? 0 : (c >= n ? n - 1 : c);
-}
-
 __global__ void __launch_bounds__(SI_THREADS)
-knn3_cell_keys_kernel(int64_t N, Knn3Grid gr, const float* __restrict__ pts, int64_t* __restrict__ keys) {
+knn_cell_keys_kernel(int64_t N, KnnGrid gr, const float* __restrict__ pts, int64_t* __restrict__ keys) {
     const int64_t i = (int64_t)blockIdx.x * SI_THREADS + threadIdx.x;
     if (i >= N) return;
-    const int cx = knn3_cell(pts[3 * i], gr.x0, gr.inv_h, gr.nx), cy = knn3_cell(pts[3 * i + 1], gr.y0, gr.inv_h, gr.ny),
-              cz = knn3_cell(pts[3 * i + 2], gr.z0, gr.inv_h, gr.nz);
+    const int cx = knn_cell(pts[3 * i], gr.x0, gr.inv_h, gr.nx), cy = knn_cell(pts[3 * i + 1], gr.y0, gr.inv_h, gr.ny),
+              cz = knn_cell(pts[3 * i + 2], gr.z0, gr.inv_h, gr.nz);
     keys[i] = ((int64_t)cz * gr.ny + cy) * gr.nx + cx;
 }
+
+// the three smallest distances so far, ascending; values only
+struct Best3 {
+    float b0 = INFINITY, b1 = INFINITY, b2 = INFINITY;
+    __device__ __forceinline__ void offer(float d, int) {       // branch-free insertion into the ascending triple
+        float t = d;
+        const float n0 = fminf(b0, t); t = fmaxf(b0, t);
+        const float n1 = fminf(b1, t); t = fmaxf(b1, t);
+        b2 = fminf(b2, t); b1 = n1; b0 = n0;
+    }
+    __device__ __forceinline__ float worst() const { return b2; }
+};
 
 // sorted_pts: the points in cell order; sorted_id[s]: original index of sorted point s; cell_start[ncells + 1].
 // out[original index] = ((b0 + b1) + b2) / 3 of the three smallest squared distances to OTHER points (by position:
 // an exact duplicate is another point, at distance 0).
 __global__ void __launch_bounds__(SI_THREADS)
-knn3_dist2_kernel(int64_t N, Knn3Grid gr, const float* __restrict__ sorted_pts, const int64_t* __restrict__ sorted_id,
-                  const int32_t* __restrict__ cell_start, float* __restrict__ out) {
+knn3_dist2_kernel(int64_t N, KnnGrid gr, const float* __restrict__ sorted_pts, const int64_t* __restrict__ sorted_id,
+                 const int32_t* __restrict__ cell_start, float* __restrict__ out) {
     const int64_t s = (int64_t)blockIdx.x * SI_THREADS + threadIdx.x;      // position in cell order: neighbours in memory
     if (s >= N) return;
-    const float qx = sorted_pts[3 * s], qy = sorted_pts[3 * s + 1], qz = sorted_pts[3 * s + 2];
-    const int cx = knn3_cell(qx, gr.x0, gr.inv_h, gr.nx), cy = knn3_cell(qy, gr.y0, gr.inv_h, gr.ny),
-              cz = knn3_cell(qz, gr.z0, gr.inv_h, gr.nz);
-    float b0 = INFINITY, b1 = INFINITY, b2 = INFINITY;      // the three best so far, ascending
-    // the cells of one (y, z) row are contiguous in the sorted points: one range per row of the cube
-    auto scan = [&](int64_t row, int xa, int xb) {
-        const int p1 = cell_start[row + xb + 1];
-        for (int p = cell_start[row + xa]; p < p1; ++p) {
-            const float ex = sorted_pts[3 * (int64_t)p] - qx, ey = sorted_pts[3 * (int64_t)p + 1] - qy,
-                        ez = sorted_pts[3 * (int64_t)p + 2] - qz;
-            const float d = p == s ? INFINITY : (ex * ex + ey * ey) + ez * ez;
-            float t = d;                                    // branch-free insertion into the ascending triple
-            const float n0 = fminf(b0, t); t = fmaxf(b0, t);
-            const float n1 = fminf(b1, t); t = fmaxf(b1, t);
-            b2 = fminf(b2, t); b1 = n1; b0 = n0;
-        }
-    };
-    // distance from the query to the faces of its own cell, in cells: the cube of radius r reaches at least (r + that) * h
-    const float fx = (qx - gr.x0) * gr.inv_h - (float)cx, fy = (qy - gr.y0) * gr.inv_h - (float)cy,
-                fz = (qz - gr.z0) * gr.inv_h - (float)cz;
-    const float margin = gr.h * fminf(fminf(fminf(fx, 1.0f - fx), fminf(fy, 1.0f - fy)), fminf(fz, 1.0f - fz));
-    const int rmax = max(gr.nx, max(gr.ny, gr.nz));
-    for (int r = 1; r <= rmax; ++r) {                       // r = 1 takes the whole 3x3x3 cube, r > 1 the cube's surface
-        for (int dz = -r; dz <= r; ++dz) {
-            const int z = cz + dz;
-            if (z < 0 || z >= gr.nz) continue;
-            for (int dy = -r; dy <= r; ++dy) {
-                const int y = cy + dy;
-                if (y < 0 || y >= gr.ny) continue;
-                const int64_t row = ((int64_t)z * gr.ny + y) * gr.nx;
-                if (r == 1 || dz == -r || dz == r || dy == -r || dy == r) {
-                    scan(row, max(cx - r, 0), min(cx + r, gr.nx - 1));
-                } else {
-                    if (cx - r >= 0) scan(row, cx - r, cx - r);
-                    if (cx + r < gr.nx) scan(row, cx + r, cx + r);
-                }
-            }
-        }
-        // every point closer than `reach` has been seen; slack: the rounding of the cell function (scene_init.py)
-        const float reach = (float)r * gr.h + margin - gr.slack;
-        if (reach > 0.0f && b2 <= reach * reach) break;
-    }
-    out[sorted_id[s]] = ((b0 + b1) + b2) / 3.0f;
+    Best3 best;
+    knn_grid_search(s, gr, sorted_pts, cell_start, best);
+    out[sorted_id[s]] = ((best.b0 + best.b1) + best.b2) / 3.0f;
 }
 
-void launch_knn3_cell_keys(int64_t N, const float* grid8, const float* pts, int64_t* keys, hipStream_t st) {
-    knn3_cell_keys_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, st>>>(N, knn3_grid(grid8), pts, keys);
+void launch_knn_cell_keys(int64_t N, const float* grid8, const float* pts, int64_t* keys, hipStream_t st) {
+    knn_cell_keys_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, st>>>(N, knn_grid(grid8), pts, keys);
 }
 
 void launch_knn3_dist2(int64_t N, const float* grid8, const float* sorted_pts, const int64_t* sorted_id,
                        const int32_t* cell_start, float* out, hipStream_t st) {
-    knn3_dist2_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, st>>>(N, knn3_grid(grid8), sorted_pts,
-                                                                                          sorted_id, cell_start, out);
+    knn3_dist2_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, st>>>(N, knn_grid(grid8), sorted_pts,
+                                                                                         sorted_id, cell_start, out);
 }
 
 }  // namespace scr

@@ -14,6 +14,8 @@ Fixture: tests/golden/densify.npz (captured from the reference's own Python by t
 import torch
 from torch import nn
 
+from .knn_grid import buckets
+
 
 # optimizer param-group name -> model attribute (scene/gaussian_model.py:520-531)
 _PARAMS = {"anchor": "_anchor", "offset": "_offset", "anchor_feat": "_anchor_feat", "opacity": "_opacity",
@@ -25,42 +27,19 @@ def inverse_sigmoid(x):                      # utils/general_utils.py:17-18
     return torch.log(x / (1 - x))
 
 
-def _knn_grid(pts, per_cell=2.0):
-    """Uniform grid over the bounding box with about `per_cell` points per cell; returns (lo[3], h, n[3])."""
-    lo, hi = pts.amin(dim=0), pts.amax(dim=0)
-    ext = (hi - lo).double()
-    ext = torch.maximum(ext, ext.max().clamp_min(1e-30) * 1e-6)
-    N = pts.shape[0]
-    h = float((ext.prod() * per_cell / N) ** (1.0 / 3.0))
-    n = torch.ceil(ext / h).clamp_min(1)
-    over = float(n.prod()) / (4.0 * N + 64)              # flat / degenerate clouds: bound the cell count
-    if over > 1.0:
-        h *= over ** (1.0 / 3.0)
-        n = torch.ceil(ext / h).clamp_min(1)
-    return lo, h, [int(v) for v in n.tolist()]
-
-
 def _knn_indices(points, k):
     """indices [N, k] of the k nearest OTHER points, nearest first (column 0 of the k+1 query dropped,
-    as :1096-1100 does).  Device tensors: grid-bucketed exact search in csrc/densify.hip (any N; the reference
-    goes to sklearn on the host); CPU tensors (the golden tests): brute force."""
+    as :1096-1100 does).  Device tensors: grid-bucketed exact search (knn_grid.buckets + csrc/densify.hip; any N; the
+    reference goes to sklearn on the host); CPU tensors (the golden tests): brute force."""
     N = points.shape[0]
     if points.is_cuda:
         from . import _C
         if k > 16:
             raise ValueError("k <= 16")
         pts = points.detach().float().contiguous()
-        lo, h, (nx, ny, nz) = _knn_grid(pts)
-        cell = ((pts - lo) / h).floor().long()
-        cell = torch.minimum(cell.clamp_min(0), torch.tensor([nx - 1, ny - 1, nz - 1], device=pts.device))
-        key = (cell[:, 2] * ny + cell[:, 1]) * nx + cell[:, 0]
-        skey, order = torch.sort(key)
-        ncell = nx * ny * nz
-        cell_start = torch.searchsorted(skey, torch.arange(ncell + 1, device=pts.device)).int()
-        spts = pts.index_select(0, order).contiguous()
         out = torch.empty(N, k, dtype=torch.long, device=pts.device)
-        grid = _C.host_array((float(lo[0]), float(lo[1]), float(lo[2]), h, nx, ny, nz), _C.f32)
         with torch.cuda.device(pts.device):
+            grid, spts, order, cell_start = buckets(pts)
             _C.check(_C.lib.scr_knn(N, k, grid, spts.data_ptr(), order.data_ptr(), cell_start.data_ptr(), out.data_ptr(),
                                     _C.stream()))
         return out

@@ -23,7 +23,8 @@ def rel(a, b):
 def test_binding_and_header_declare_the_three_entry_points_at_abi_35():
     from splatco_amd import _C
     hdr = open(os.path.join(ROOT, "include", "splatco_raster.h")).read()
-    assert _C.ABI_VERSION == 35 and _C.lib.scr_abi_version() == 35 and "#define SCR_ABI_VERSION 35" in hdr
+    assert _C.ABI_VERSION >= 35 and _C.lib.scr_abi_version() == _C.ABI_VERSION
+    assert f"#define SCR_ABI_VERSION {_C.ABI_VERSION}" in hdr
     sig = {s[0]: s for s in _C.SIGNATURES}
     for name in NAMES:
         assert hasattr(_C.lib, name) and name in _C.SYMBOLS and re.search(rf"\b{name}\s*\(", hdr), name

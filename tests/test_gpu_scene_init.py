@@ -99,6 +99,95 @@ def test_dist2_device_equals_cpu_bit_for_bit(name):
     assert torch.equal(got.cpu(), want)
 
 
+KNN_KS = (1, 3, 10, 11, 16)          # 10 takes knn_kernel<10>; 11 and 16 take knn_kernel<16>
+KNN_REF = 17                          # reference distances kept per query: k + 1 at the largest k
+# cloud -> N.  The members of _dist2_clouds() ("N = 257" is small[:257]), then: the two far clusters (the per-axis bound sets
+# h, the walk crosses many empty shells), clusters without duplicates, one point 300 times (the [1, 1, 1] grid, every
+# distance 0), small[:k + 1] (every other point is a neighbour: rmax ends the walk, not the stop test) and the edges of the
+# 256-thread workgroup.
+KNN_CLOUDS = {"uniform 20011": 20011, "clustered, 10 % duplicates": 20000, "lattice": None, "sheet 20000": 20000, "line": 5000,
+              "N = 4": 4, "N = 63": 63, "N = 64": 64, "N = 65": 65, "N = 257": 257, "two clusters 3000 apart": 6200,
+              "clustered": 20000, "300 identical points": 300, "N = 255": 255, "N = 256": 256,
+              **{f"N = {k + 1}": k + 1 for k in KNN_KS if k != 3}}
+# (c) leaves out a row whose k + 1 smallest distances tie; on these clouds at most 1 % of the rows may be left out (the
+# reference alone has ties on 0.01 %, 0 %, 0.36 %, 0.01 % and 0 % of their rows, with 17 distances per row)
+KNN_FEW_TIES = ("uniform 20011", "sheet 20000", "line", "clustered") + tuple(n for n in KNN_CLOUDS if n.startswith("N = "))
+KNN_CASES = [(name, k) for name, n in KNN_CLOUDS.items() for k in KNN_KS if n is None or n > k]
+_knn_cache = {}
+
+
+def _knn_cloud(name):
+    """(points, the KNN_REF smallest squared distances of every query ascending, their indices): a float32 brute force on
+    the CPU with the kernel's arithmetic, the query masked by index; computed once per cloud."""
+    if name not in _knn_cache:
+        if not _knn_cache:
+            small = torch.rand(257, 3, generator=_gen(3)) * 2 - 1          # the `small` of _dist2_clouds()
+            _knn_cache[None] = {**_dist2_clouds(), "two clusters 3000 apart": _wide(), "clustered": _clustered(20000, 4, dup=0.0),
+                                "300 identical points": torch.tensor([[0.3, -1.2, 2.5]]).repeat(300, 1),
+                                **{f"N = {n}": small[:n].contiguous() for n in (2, 11, 12, 17, 255, 256)}}
+            assert torch.equal(_knn_cache[None]["N = 257"], small)
+        p = _knn_cache[None][name].float().contiguous()
+        N = p.shape[0]
+        m = min(KNN_REF, N)
+        ref_d, ref_i = torch.empty(N, m), torch.empty(N, m, dtype=torch.long)
+        x, y, z = p[:, 0].contiguous(), p[:, 1].contiguous(), p[:, 2].contiguous()
+        step = max(1, (1 << 23) // N)
+        for s in range(0, N, step):
+            e = min(s + step, N)
+            ex, ey, ez = x[None, :] - x[s:e, None], y[None, :] - y[s:e, None], z[None, :] - z[s:e, None]
+            d = (ex * ex + ey * ey) + ez * ez                     # separate torch ops: nothing is contracted
+            d[torch.arange(e - s), torch.arange(s, e)] = float("inf")
+            ref_d[s:e], ref_i[s:e] = d.topk(m, dim=1, largest=False, sorted=True)
+        _knn_cache[name] = (p, ref_d, ref_i)
+    return _knn_cache[name]
+
+
+@pytest.mark.parametrize("name,k", KNN_CASES)
+def test_knn_indices_device_equals_brute_force(name, k):
+    """densify._knn_indices on the device against the brute force: (a) well-formed indices, (b) the k distances bit for bit
+    and in order, (c) the indices themselves wherever the k + 1 smallest distances are distinct, (d) at k = 3 the mean of
+    (b)'s distances is dist2 on the device, bit for bit -- the two kernels share the search of csrc/knn_grid.h."""
+    from splatco_amd.densify import _knn_indices
+    from splatco_amd.scene_init import dist2
+    p, ref_d, ref_i = _knn_cloud(name)
+    N = p.shape[0]
+    assert KNN_CLOUDS[name] in (None, N) and N > k
+    got = _knn_indices(p.to(DEV), k)
+    torch.cuda.synchronize()
+    assert got.is_cuda and got.dtype == torch.long and tuple(got.shape) == (N, k)                     # (a)
+    idx = got.cpu()
+    assert int(idx.min()) >= 0 and int(idx.max()) < N
+    assert not bool((idx == torch.arange(N)[:, None]).any())
+    s = idx.sort(dim=1).values
+    assert not bool((s[:, 1:] == s[:, :-1]).any())
+    e = p[idx] - p[:, None, :]                                                                         # (b)
+    ex, ey, ez = e[..., 0], e[..., 1], e[..., 2]
+    d = (ex * ex + ey * ey) + ez * ez
+    bad = int((d != ref_d[:, :k]).any(dim=1).sum())
+    distinct = (ref_d[:, 1:k + 1] != ref_d[:, :k]).all(dim=1)                                          # (c)
+    tied = N - int(distinct.sum())
+    wrong = int((idx[distinct] != ref_i[distinct, :k]).any(dim=1).sum())
+    print(f"[{name}, k = {k}] N = {N}: {bad} rows differ in a distance; {tied} rows ({100 * tied / N:.2f} %) have a tie among "
+          f"their {k + 1} smallest; {wrong} of the others differ in an index")
+    assert torch.equal(d, ref_d[:, :k])
+    assert torch.equal(idx[distinct], ref_i[distinct, :k])
+    if name in KNN_FEW_TIES:
+        assert tied <= 0.01 * N
+    if k == 3:                                                                                         # (d)
+        t = (d[:, 0] + d[:, 1]) + d[:, 2]
+        assert torch.equal(t / torch.full_like(t, 3.0), dist2(p.to(DEV)).cpu())
+
+
+def test_knn_indices_refuses_non_finite_points():
+    from splatco_amd.densify import _knn_indices
+    p = _clustered(5000, 51, dup=0.0).to(DEV)
+    for bad_value in (float("nan"), float("inf"), -float("inf")):
+        bad = p.clone()
+        bad[4097, 2] = bad_value
+        with pytest.raises(ValueError):
+            _knn_indices(bad, 10)
+
+
 def _voxel_clouds():
     clouds = {"fixture": (torch.tensor(GOLDEN["points"]), [float(v) for v in GOLDEN["voxel_sizes"]])}
     clouds["uniform 200 k"] = (torch.rand(200_000, 3, generator=_gen(11)) * 4 - 2, [0.05, 0.01, 0.001])

@@ -7,7 +7,8 @@ for a uniform cloud in [-2, 2]^3 and a sheet (a sphere of radius 1.5) of the sam
              np.unique(np.round(p / v), axis=0) * v on this box's CPU (the only baseline that exists; run once, it takes
              tens of seconds);
   dist2      the fused 3-NN kernel alone and the whole call (bucketing included), alternated in one process with what the
-             library could do for the same result before: densify._knn_indices(points, 3), a torch gather and a mean.
+             library could do for the same result before: densify._knn_indices(points, 3), a torch gather and a mean;
+  kNN        densify._knn_indices(points, 10), the curvature pass's search: the whole call and scr_knn alone.
 
 Every device time is the median of --reps runs after --warmup; min and max are printed next to it.  Prints one line
 per measurement, the first a provenance stamp (tools/provenance.py).  No test asserts a speed."""
@@ -74,7 +75,7 @@ def main():
     ap.add_argument("--no-host", action="store_true", help="skip the numpy baseline")
     args = ap.parse_args()
     import provenance
-    from splatco_amd import _C, scene_init as si
+    from splatco_amd import _C, knn_grid, scene_init as si
     from splatco_amd.densify import _knn_indices
     print("# provenance: " + json.dumps(provenance.stamp(" ".join(["tools/time_scene_init.py"] + sys.argv[1:]))))
     dev = torch.device("cuda:0")
@@ -94,7 +95,7 @@ def main():
         return f"{nbytes / (statistics.median(ms) * 1e-3) / 1e12:.2f} TB/s, {100 * nbytes / (statistics.median(ms) * 1e-3) / peak:.0f} % of the copy peak"
 
     for name, p in clouds(N, dev).items():
-        t_bounds = timed(lambda: si._bounds(p), args.reps, args.warmup)
+        t_bounds = timed(lambda: knn_grid.bounds(p), args.reps, args.warmup)
         print(f"[{name}] bounding box + finite check (read back): {fmt(t_bounds)}  12 B / point: {share(12 * N, t_bounds)}")
         # ---- voxelize
         vv, lo, ext = si._voxel_range(p, v)
@@ -138,7 +139,7 @@ def main():
             e = p[idx] - p[:, None, :]
             return (e * e).sum(-1).mean(-1)
 
-        grid, spts, order, cell_start = si._knn3_buckets(p)
+        grid, spts, order, cell_start = knn_grid.buckets(p)
         res = torch.empty(N, device=dev)
         kernel = lambda: _C.check(_C.lib.scr_knn3_dist2(N, grid, spts.data_ptr(), order.data_ptr(), cell_start.data_ptr(),
                                                         res.data_ptr(), st))
@@ -155,6 +156,16 @@ def main():
         print(f"[{name}]   whole call (bucketing + kernel) {fmt(t_new)}")
         print(f"[{name}]   _knn_indices(p, 3) + gather + mean {fmt(t_old)}  -> {statistics.median(t_old) / statistics.median(t_new):.2f} x the fused call; "
               f"max relative difference of the two results {rel:.2e}")
+        # ---- the curvature pass's kNN, k = 10 (the same buckets, the same search, another policy of what to keep)
+        grid, spts, order, cell_start = knn_grid.buckets(p)
+        idx = torch.empty(N, 10, dtype=torch.long, device=dev)
+        knn = lambda: _C.check(_C.lib.scr_knn(N, 10, grid, spts.data_ptr(), order.data_ptr(), cell_start.data_ptr(),
+                                              idx.data_ptr(), st))
+        t_knn = timed(knn, args.reps, args.warmup)
+        del spts, order, cell_start, idx
+        t_knn_all = timed(lambda: _knn_indices(p, 10), args.reps, args.warmup)
+        print(f"[{name}] kNN k = 10, {N} points: scr_knn alone {fmt(t_knn)}  ({N / statistics.median(t_knn) / 1e6:.2f} G points / s)")
+        print(f"[{name}]   whole call _knn_indices(p, 10) {fmt(t_knn_all)}")
         del p
         torch.cuda.empty_cache()
 
