@@ -14,7 +14,7 @@
 // framework's cats are gone too.  Backward (tpa_bwd_*): dL/dsa -> through the sigmoid -> transposed 7x7 -> mean / max
 // routing -> dL/dy -> dL/dx and the per-channel sums dL/dca; the weight gradient of the 7x7 is a per-tile correlation.
 // Every reduction is two-level with a fixed order (per-block partials, summed in block order): bit-reproducible.
-#include "common.h"
+#include "wg.h"
 
 namespace scr {
 
@@ -26,9 +26,8 @@ struct TpaPlanes { const float* p[3]; };
 struct TpaOut { float* p[3]; };
 
 __device__ __forceinline__ float block_sum_256(float v, float* lds) {   // lds: 4 floats; all threads get the sum
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
-    __syncthreads();
+    v = wave_sum(v);
+    __syncthreads();   // the callers reuse lds from one call to the next
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
     __syncthreads();
     return (lds[0] + lds[1]) + (lds[2] + lds[3]);

@@ -13,7 +13,7 @@
 //               each instance's Gaussian-major index (where the backward pass puts its gradient
 //               record) from the Gaussian's tile rect, so no payload travels through the sort.
 // Both passes move 8-12 B per instance once instead of 6+ radix passes over 12 B.
-#include "compact.h"     // block_exclusive_scan
+#include "wg.h"          // block_exclusive_scan
 
 namespace scr {
 

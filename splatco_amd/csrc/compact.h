@@ -1,6 +1,6 @@
-// splatco_amd/csrc/compact.h -- order-preserving stream compaction on the device, written once (gfx950): the block scan,
-// and the count / scan / write scheme behind the expansion (expand.hip: opacity > 0), the mask -> index list (expand.hip)
-// and the distinct voxel keys (scene_init.hip: head flags on sorted keys).
+// splatco_amd/csrc/compact.h -- order-preserving stream compaction on the device, written once (gfx950): the
+// count / scan / write scheme behind the expansion (expand.hip: opacity > 0), the mask -> index list (expand.hip) and the
+// distinct voxel keys (scene_init.hip: head flags on sorted keys).  The block scan it rests on is wg.h's.
 //
 //   count   compact_count_kernel<Keep>: kept items per workgroup of 1024 items (256 threads x 4 rounds of 256 items)
 //   scan    compact_scan_kernel (one workgroup): exclusive prefix of the workgroup counts in place, the total to the
@@ -14,34 +14,9 @@
 //                 __device__ Operand load(int64_t c) const;              // c = min(i, n - 1): always in bounds
 //                 __device__ bool keep(const Operand& v, int64_t i) const; };      // asked for i < n only
 #pragma once
-#include "common.h"
+#include "wg.h"        // block_exclusive_scan
 
 namespace scr {
-
-// ------------------------------------------------------------------ block-wide exclusive scan
-template <int THREADS>
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds_waves /*[THREADS/64+1]*/,
-                                                         uint32_t& block_total) {
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        uint32_t n = __shfl_up(inc, d, WAVE);
-        if (lane >= d) inc += n;
-    }
-    if (lane == WAVE - 1) lds_waves[w] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < THREADS / WAVE; ++k) {
-        uint32_t s = lds_waves[k];
-        if (k < w) base += s;
-        tot += s;
-    }
-    block_total = tot;
-    __syncthreads();
-    return base + inc - v;
-}
 
 // ------------------------------------------------------------------ geometry and scratch
 constexpr int COMPACT_THREADS = 256;

@@ -12,11 +12,10 @@
 //              dA = -q D / A^2
 // In framework ops that is about twenty element-wise kernels and five reductions per view, with a float32 sum() whose order
 // is not fixed.  Here: a moment pass (only with alignment) and a residual pass, each one streaming read of the maps with one
-// record per workgroup, each followed by a one-workgroup fold, and one element-wise backward pass.  Every sum has a fixed
-// order -- a lane adds its pixels in index order, the wave over a butterfly, the workgroup's waves and then the records in
-// index order -- so a result is the same bits run after run.  No atomics, no memset: every scratch word that is read was
-// written by an earlier launch of the same call.
-#include "common.h"
+// record per workgroup, each followed by a one-workgroup fold, and one element-wise backward pass.  Every sum has the fixed
+// order of wg.h (wg_sum per workgroup, fold_sum over the records), so a result is the same bits run after run.  No atomics,
+// no memset: every scratch word that is read was written by an earlier launch of the same call.
+#include "wg.h"
 
 namespace scr {
 
@@ -59,21 +58,6 @@ __device__ __forceinline__ bool dl_pixel(int64_t e, const float* __restrict__ de
     return ok;
 }
 
-template <int K>
-__device__ __forceinline__ void dl_wg_reduce(double (&v)[K], double* __restrict__ red /*[4][K]*/, double* __restrict__ rec) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v[k] += __shfl_xor(v[k], d, WAVE);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) red[(threadIdx.x >> 6) * K + k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < K) rec[threadIdx.x] = ((red[threadIdx.x] + red[K + threadIdx.x]) + red[2 * K + threadIdx.x]) + red[3 * K + threadIdx.x];
-}
-
 // pass A: mom[block] = the moments of the block's DL_PER_WG pixels
 __global__ void __launch_bounds__(DL_THREADS)
 depth_loss_moments_kernel(int64_t n, const float* __restrict__ depth, const float* __restrict__ alpha,
@@ -95,37 +79,7 @@ depth_loss_moments_kernel(int64_t n, const float* __restrict__ depth, const floa
             v[5] += 1.0;
         }
     }
-    dl_wg_reduce<DL_MOM>(v, red, mom + (size_t)blockIdx.x * DL_MOM);
-}
-
-// One workgroup: acc[k] = the K columns of rec[nb][K], thread t over records t, t + 1024, ... in order, the wave over a
-// butterfly, the 16 waves in order.  The result is valid in thread 0.
-template <int K>
-__device__ __forceinline__ void dl_fold(int nb, const double* __restrict__ rec, double* __restrict__ red /*[16][K]*/, double (&acc)[K]) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = 0.0;
-    for (int b = threadIdx.x; b < nb; b += DL_FOLD) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc[k] += rec[(size_t)b * K + k];
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) acc[k] += __shfl_xor(acc[k], d, WAVE);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) red[(threadIdx.x >> 6) * K + k] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double t = 0.0;
-            for (int w = 0; w < DL_FOLD / WAVE; ++w) t += red[w * K + k];
-            acc[k] = t;
-        }
-    }
+    wg_sum<DL_THREADS / WAVE>(v, red, mom + (size_t)blockIdx.x * DL_MOM);
 }
 
 // fold of pass A: st = (s, t) of the weighted least-squares line, (1, 0) where the fit is degenerate
@@ -133,7 +87,7 @@ __global__ void __launch_bounds__(DL_FOLD)
 depth_loss_solve_kernel(int nb, const double* __restrict__ mom, double* __restrict__ st) {
     __shared__ double red[(DL_FOLD / WAVE) * DL_MOM];
     double a[DL_MOM];
-    dl_fold<DL_MOM>(nb, mom, red, a);
+    fold_sum<DL_FOLD>(nb, mom, red, a);
     if (threadIdx.x == 0) {
         const double S0 = a[0], Sp = a[1], Spp = a[2], Sg = a[3], Spg = a[4];
         const double det = S0 * Spp - Sp * Sp;
@@ -164,7 +118,7 @@ depth_loss_residual_kernel(int64_t n, const float* __restrict__ depth, const flo
             v[1] += 1.0;
         }
     }
-    dl_wg_reduce<DL_RES>(v, red, res + (size_t)blockIdx.x * DL_RES);
+    wg_sum<DL_THREADS / WAVE>(v, red, res + (size_t)blockIdx.x * DL_RES);
 }
 
 // fold of pass B: out4 = (L, s, t, n_valid); without alignment it also leaves (1, 0) in the header for the backward pass
@@ -173,7 +127,7 @@ depth_loss_finish_kernel(int nb, const double* __restrict__ res, double inv_n, i
                          float* __restrict__ out4) {
     __shared__ double red[(DL_FOLD / WAVE) * DL_RES];
     double a[DL_RES];
-    dl_fold<DL_RES>(nb, res, red, a);
+    fold_sum<DL_FOLD>(nb, res, red, a);
     if (threadIdx.x == 0) {
         double s = 1.0, t = 0.0;
         if (align) { s = st[0]; t = st[1]; }

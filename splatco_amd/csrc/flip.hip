@@ -14,7 +14,7 @@
 // keeps exactly: the vertical pass reads the horizontal results of clamped rows.
 #include <math.h>
 
-#include "common.h"
+#include "wg.h"
 
 namespace scr {
 
@@ -160,7 +160,7 @@ flip_kernel(int H, int W, const float* __restrict__ test, const float* __restric
             float* __restrict__ map, float2* __restrict__ partial) {
     __shared__ float st[FL_PLANES][FL_S][FL_S];
     __shared__ float hz[FL_HZ][FL_S][FL_T];
-    __shared__ float2 wsum[4];
+    __shared__ float wsum[4 * 2];
     const int n = blockIdx.z;
     const size_t plane = (size_t)H * W;
     const float* t_img = test + (size_t)n * 3 * plane;
@@ -193,18 +193,8 @@ flip_kernel(int H, int W, const float* __restrict__ test, const float* __restric
             sse += d * d;
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        fsum += __shfl_down(fsum, d, WAVE);
-        sse += __shfl_down(sse, d, WAVE);
-    }
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = make_float2(fsum, sse);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float2 r = wsum[0];
-        for (int w = 1; w < 4; ++w) { r.x += wsum[w].x; r.y += wsum[w].y; }
-        partial[((size_t)n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = r;
-    }
+    float v[2] = {fsum, sse};   // tile sums in the order of wg.h; threads 0 and 1 write the partial's x and y
+    wg_sum<4>(v, wsum, (float*)(partial + ((size_t)n * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x));
 }
 
 // grid N, 256 threads: image n's tile partials in a fixed order -> mean FLIP over H W, mean squared error over 3 H W

@@ -11,7 +11,7 @@
 // NORMATIVE ARITHMETIC: the integer outputs (radii, tile rect, depth bits) must be bit-identical
 // to the CPU oracle, so this file is compiled with -ffp-contract=off and every expression below
 // is written in the evaluation order of DESIGN.md "Normative arithmetic" (no FMA, IEEE sqrt/div).
-#include "common.h"
+#include "wg.h"         // wg_wave_parts (cam_workgroup_sum)
 
 namespace scr {
 
@@ -344,24 +344,19 @@ preprocess_kernel(int64_t P, int M, const float* __restrict__ means3D, const flo
 }
 
 // ------------------------------------------------------------------ backward: reduce + chain
-// Sum of each of the CAM_VALUES per-thread values over the PRE_BLOCK threads of the workgroup, in a fixed order: the lanes of
-// a wave by a shuffle tree, then the waves in ascending order (binning.hip's wave_sum scheme).  Every thread must call it.
+// Sum of each of the CAM_VALUES per-thread values over the PRE_BLOCK threads of the workgroup, in the order of wg.h, into a
+// row of CAM_ROW floats (columns CAM_VALUES.. are 0).  The waves are added from 0.0f, not from wave 0 as wg_sum does: v is
+// not an accumulator that started at +0, so a column may be -0 in every wave, and the row would then change sign.
+// Every thread must call it.
 constexpr int CAM_VALUES = 27, CAM_ROW = 32;
-__device__ __forceinline__ void cam_workgroup_sum(const float* v, float* __restrict__ row) {
-    __shared__ float wave_part[PRE_BLOCK / WAVE][CAM_ROW];
-#pragma unroll
-    for (int k = 0; k < CAM_VALUES; ++k) {
-        float s = v[k];
-#pragma unroll
-        for (int d = WAVE / 2; d > 0; d >>= 1) s += __shfl_down(s, d, WAVE);
-        if ((threadIdx.x & (WAVE - 1)) == 0) wave_part[threadIdx.x / WAVE][k] = s;
-    }
-    __syncthreads();
+__device__ __forceinline__ void cam_workgroup_sum(float (&v)[CAM_VALUES], float* __restrict__ row) {
+    __shared__ float wave_part[(PRE_BLOCK / WAVE) * CAM_VALUES];
+    wg_wave_parts<PRE_BLOCK / WAVE>(v, wave_part);
     if (threadIdx.x < CAM_ROW) {
         float tot = 0.0f;
         if (threadIdx.x < CAM_VALUES) {
 #pragma unroll
-            for (int w = 0; w < PRE_BLOCK / WAVE; ++w) tot += wave_part[w][threadIdx.x];
+            for (int w = 0; w < PRE_BLOCK / WAVE; ++w) tot += wave_part[w * CAM_VALUES + threadIdx.x];
         }
         row[threadIdx.x] = tot;
     }
@@ -374,7 +369,7 @@ __device__ __forceinline__ void cam_workgroup_sum(const float* v, float* __restr
 // z = ((V[2] x + V[6] y) + V[10] z) + V[14] in project().
 // POSE: the camera takes part in the loss.  Each thread also forms its Gaussian's 27 contributions to dL/dviewmatrix (12:
 // rows 0..3 x columns 0..2), dL/dprojmatrix (12: rows 0..3 x columns 0, 1, 3) and dL/dcampos (3) from the factors of the chain
-// below; the workgroup adds them up in a fixed order (lanes of a wave by shuffles, the four waves through LDS) and leaves one
+// below; the workgroup adds them up in a fixed order (cam_workgroup_sum) and leaves one
 // row of CAM_ROW floats in cam_partials[blockIdx.x], which camera_grad_finish_kernel sums.  EVERY thread of the workgroup
 // takes part: a thread past the end works on the last Gaussian's (valid) addresses, counts as invisible and stores nothing.
 // AA: the forward may have run in the antialiased mode, record opacity = o h (aa_factor).  Whether it did is read from the

@@ -6,13 +6,13 @@
 // forward+backward at 1080p -- 6x the whole rasterizer step.  Here each 16x16 output tile stages
 // its 26x26 halo of both images in LDS once, runs the separable window (11 + 11 taps) for the
 // five moments, evaluates the SSIM map and its three partial derivatives in registers, and
-// reduces the tile's L1 / SSIM sums deterministically (per-tile partials, fixed-order final sum).
+// reduces the tile's L1 / SSIM sums deterministically (per-tile partials in the order of wg.h, fixed-order final sum).
 // The backward is the transposed window applied to the three derivative maps.
 //
 //   mu1 = G*x, mu2 = G*y, E11 = G*x^2, E22 = G*y^2, E12 = G*xy
 //   ssim = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2)),  s.. = E.. - mu mu
 //   dL/dx(p) = sum_q G(q-p) [ dmu1(q) + 2 x(p) dE11(q) + y(p) dE12(q) ]
-#include "common.h"
+#include "wg.h"
 
 namespace scr {
 
@@ -33,7 +33,7 @@ l1_ssim_forward_kernel(int H, int W, const float* __restrict__ img1, const float
                        float2* __restrict__ partial) {
     __shared__ float t1[SS_H][SS_H + 1], t2[SS_H][SS_H + 1];
     __shared__ float hz[5][SS_H][SS_T + 1];  // horizontal pass: 5 moments, 26 rows x 16 columns
-    __shared__ float2 wsum[4];
+    __shared__ float wsum[4 * 2];
     const int c = blockIdx.z, C = gridDim.z;
     const size_t plane = (size_t)H * W;
     const float* x1 = img1 + c * plane;
@@ -88,19 +88,8 @@ l1_ssim_forward_kernel(int H, int W, const float* __restrict__ img1, const float
             dmaps[(2 * (size_t)C + c) * plane + o] = dE12;
         }
     }
-    // deterministic tile sums: wave shuffles, then 4 wave partials
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        l1 += __shfl_down(l1, d, WAVE);
-        ss += __shfl_down(ss, d, WAVE);
-    }
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = make_float2(l1, ss);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float2 r = wsum[0];
-        for (int w = 1; w < 4; ++w) { r.x += wsum[w].x; r.y += wsum[w].y; }
-        partial[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = r;
-    }
+    float v[2] = {l1, ss};   // tile sums in the order of wg.h; threads 0 and 1 write the partial's x and y
+    wg_sum<4>(v, wsum, (float*)(partial + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x));
 }
 
 // one workgroup: fixed-order sum of the tile partials -> out[0] = mean |x-y|, out[1] = mean ssim
@@ -211,26 +200,15 @@ scaling_reg_partial_kernel(int64_t P, const float* __restrict__ s, double* __res
     const int64_t r0 = (int64_t)blockIdx.x * SREG_ROWS;
     for (int64_t r = r0 + threadIdx.x; r < min(P, r0 + SREG_ROWS); r += 256)
         acc += (double)((s[3 * r] * s[3 * r + 1]) * s[3 * r + 2]);      // the product in binary32, as torch.prod forms it
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, WAVE);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    wg_wave_parts<4>(acc, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 __global__ void __launch_bounds__(1024)
 scaling_reg_finish_kernel(int nb, const double* __restrict__ partial, double inv_n, float* __restrict__ out) {
-    __shared__ double red[16];
-    double acc = 0.0;
-    for (int b = threadIdx.x; b < nb; b += 1024) acc += partial[b];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, WAVE);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < 16; ++w) t += red[w];
-        out[0] = (float)(t * inv_n);
-    }
+    __shared__ double red[1024 / WAVE];
+    double t[1];
+    fold_sum<1024>(nb, partial, red, t);
+    if (threadIdx.x == 0) out[0] = (float)(t[0] * inv_n);
 }
 __global__ void __launch_bounds__(256)
 scaling_reg_backward_kernel(int64_t P, const float* __restrict__ s, const float* __restrict__ g, float inv_n,
@@ -256,10 +234,7 @@ pair_l1_partial_kernel(int64_t n, const float* __restrict__ g1, const float* __r
     const int64_t e0 = (int64_t)blockIdx.x * PL1_PER_WG;
     for (int64_t e = e0 + threadIdx.x; e < min(n, e0 + PL1_PER_WG); e += 256)
         acc += (double)fabsf((r1[e] - r2[e]) - (g1[e] - g2[e]));
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, WAVE);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    wg_wave_parts<4>(acc, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 __global__ void __launch_bounds__(256)

@@ -64,6 +64,9 @@ __device__ __forceinline__ int tp_tile_of(float gx, float gy, int A, int B, int 
     return (a0 / TP_TILE) * tb + (b0 / TP_TILE);
 }
 
+// wg.h's block_exclusive_scan with the wave loop over blockDim.x, i.e. rolled.  Kept on purpose: with the trip count
+// known the compiler unrolls the 16 LDS reads, and tp_cell_gather_kernel sits at its 128-VGPR cap -- compiled that way,
+// four of its instantiations spill (20..32 bytes of scratch per lane) and tp_scan_kernel goes from 61 to 128 VGPRs.
 __device__ __forceinline__ uint32_t tp_block_scan(uint32_t v, uint32_t* lds_waves, uint32_t& total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     uint32_t inc = v;

@@ -521,6 +521,62 @@ def ssim_restated_f32(x, y, g_l1, g_ssim, fault=None, with_maps=False):
     return (L1, S, dx, maps) if with_maps else (L1, S, dx)
 
 
+# The summation order of csrc/wg.h, pinned where binary32 shows it: the L1 output of scr_l1_ssim_forward.  Shapes with
+# one live pixel, one tile, ragged tiles, several tiles, and 1083 tiles (the reduce workgroup's second stride).  For
+# every shape with more than one wave of live pixels the seed was chosen by a CPU search (lowest seed from 0) so that the
+# final bits under the documented order differ from those under BOTH alternatives of L1_ORDER_ALTERNATIVES: the final
+# rounding to binary32 hides most changes of order, and a test on a seed that hides them would pin nothing.
+# (3, 1, 1) has one live lane per tile: no order can differ, only equality is asked (seed None: no condition).
+L1_ORDER_SHAPES = [(3, 1, 1), (1, 16, 16), (3, 17, 33), (3, 48, 80), (3, 304, 304)]
+L1_ORDER_SEEDS = {(3, 1, 1): None, (1, 16, 16): 6, (3, 17, 33): 10, (3, 48, 80): 30, (3, 304, 304): 6}
+L1_ORDER_ALTERNATIVES = ("pairwise", "serial")
+
+
+def l1_order_inputs(shape):
+    """fp32 numpy (x, y) of one order-pin case: uniform noise and a noisy copy, from the shape's recorded seed."""
+    import numpy as np
+    rng = np.random.default_rng(L1_ORDER_SEEDS[shape] or 0)
+    x = rng.random(shape, dtype=np.float32)
+    y = np.clip(x + np.float32(0.15) * rng.standard_normal(shape, dtype=np.float32), 0, 1).astype(np.float32)
+    return x, y
+
+
+def l1_tile_order(x, y, order="wg.h"):
+    """numpy emulation of the L1 half of scr_l1_ssim_forward on fp32 [C,H,W] arrays, operation by operation: per 16 x 16
+    tile and channel thread ly * 16 + lx holds fabsf(x - y) in binary32 (0 outside the image); each of the 4 waves sums
+    by the xor butterfly over 32 .. 1; the waves are added in ascending order; tile partial ((c * gy + by) * gx + bx);
+    thread t of 1024 adds partials t, t + 1024, ... in binary64; the LDS tree over 512 .. 1; times 1 / (C H W), rounded
+    once to binary32.  order: "wg.h" (the documented one), or a tile sum the kernel must NOT have -- "pairwise"
+    ((w0 + w1) + (w2 + w3)) or "serial" (the 256 threads in ascending order)."""
+    import numpy as np
+    C, H, W = x.shape
+    T = SSIM_TILE
+    gy, gx = -(-H // T), -(-W // T)
+    d = np.zeros((C, gy * T, gx * T), np.float32)
+    d[:, :H, :W] = np.abs(x.astype(np.float32) - y.astype(np.float32))
+    v = d.reshape(C, gy, T, gx, T).transpose(0, 1, 3, 2, 4).reshape(C * gy * gx, 4, 64)     # [tile, wave, lane]
+    if order == "serial":
+        part = np.add.accumulate(v.reshape(-1, 256), axis=1, dtype=np.float32)[:, -1]
+    else:
+        lane = np.arange(64)
+        for s in (32, 16, 8, 4, 2, 1):
+            v = v + v[:, :, lane ^ s]
+        w = v[:, :, 0]
+        part = (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3]) if order == "pairwise" else ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+    assert part.dtype == np.float32
+    rows = -(-part.size // SSIM_REDUCE)
+    rec = np.zeros(rows * SSIM_REDUCE, np.float64)
+    rec[:part.size] = part
+    a = np.zeros(SSIM_REDUCE, np.float64)
+    for r in rec.reshape(rows, SSIM_REDUCE):
+        a = a + r
+    s = SSIM_REDUCE // 2
+    while s > 0:
+        a[:s] = a[:s] + a[s:2 * s]
+        s //= 2
+    return np.float32(a[0] * (1.0 / (float(C) * H * W)))
+
+
 def ssim_dx_floor(up, n):
     """Floor of the scale d x is measured against: (|g_l1| + |g_ssim|) / n, the size of a gradient that is not there.
     On identical images the true gradient is 1e-16 and a ratio to it is noise over nothing."""

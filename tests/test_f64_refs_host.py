@@ -355,3 +355,23 @@ def test_image_loss_inputs_hold_what_the_case_is_about():
         a, b, r1, r2 = R.pair_inputs(n)
         res = (r1 - r2) - (a - b)
         assert float(res[::R.PAIR_ZERO_STRIDE].abs().max()) <= 2.0 ** -22 and (n < 2 or float(res.abs().max()) > 0.1)
+
+
+@pytest.mark.parametrize("shape", R.L1_ORDER_SHAPES, ids=["%dx%dx%d" % s for s in R.L1_ORDER_SHAPES])
+def test_the_l1_order_emulator_is_a_mean_and_its_seeds_tell_the_orders_apart(shape):
+    """f64_refs.l1_tile_order (what test_gpu_f64_parity asks of the kernel bit for bit) is within 2^-22 mean + 1e-12 of the
+    float64 mean (a tile's 256 binary32 terms pass 8 tree levels of 2^-25 each at most, then one rounding of the mean;
+    the float64 fold adds nothing visible; these inputs come to 0.08 .. 0.15 of the bound) -- and on the recorded seeds
+    the two orders the kernel must not have end in other bits, so the GPU test's equality pins the order.  A shape
+    without a recorded seed has one live pixel per tile: no order can show."""
+    x, y = R.l1_order_inputs(shape)
+    assert x.dtype == y.dtype == np.float32 and x.shape == y.shape == shape
+    got = R.l1_tile_order(x, y)
+    mean = np.abs(x - y).astype(np.float64).mean()
+    print(f"l1 order {shape}: emulator {float(got):.9g}, float64 mean {mean:.9g}, |diff| {abs(float(got) - mean) / mean * 2 ** 22:.3f} x 2^-22 mean")
+    assert got.dtype == np.float32 and abs(float(got) - mean) <= 2.0 ** -22 * mean + 1e-12
+    others = [R.l1_tile_order(x, y, o) for o in R.L1_ORDER_ALTERNATIVES]
+    if R.L1_ORDER_SEEDS[shape] is None:
+        assert shape[1] * shape[2] == 1 and all(o.view(np.uint32) == got.view(np.uint32) for o in others)
+    else:
+        assert all(o.view(np.uint32) != got.view(np.uint32) for o in others), [float(o) for o in others]

@@ -358,6 +358,23 @@ def test_l1_ssim_entry_points():
         l1y.backward()
 
 
+@pytest.mark.parametrize("shape", R.L1_ORDER_SHAPES, ids=["%dx%dx%d" % s for s in R.L1_ORDER_SHAPES])
+def test_l1_has_the_documented_summation_order(shape):
+    """The L1 of l1_ssim equals f64_refs.l1_tile_order bit for bit: the order of csrc/wg.h (butterfly per wave, waves
+    ascending) and of l1_ssim_reduce_kernel, on one live pixel, one tile, ragged tiles, 45 tiles and 1083 tiles.  The
+    inputs' seeds are those on which a pairwise wave combine and a serial sum end in other bits
+    (tests/test_f64_refs_host.py checks that they do), so a changed order fails here, not only a wrong sum."""
+    import numpy as np
+    from splatco_amd.losses import l1_ssim
+    x, y = R.l1_order_inputs(shape)
+    want = R.l1_tile_order(x, y)
+    with torch.no_grad():
+        got = l1_ssim(torch.from_numpy(x).to(DEV), torch.from_numpy(y).to(DEV))[0].cpu().numpy()
+    print(f"l1 order {shape}: kernel {float(got):.9g} ({int(got.view(np.uint32)):#010x}), emulator {float(want):.9g} "
+          f"({int(want.view(np.uint32)):#010x})")
+    assert got.dtype == np.float32 and got.shape == () and got.view(np.uint32) == want.view(np.uint32)
+
+
 def test_l1_ssim_wrapper_refuses_a_mismatched_ground_truth(monkeypatch):
     """losses.l1_ssim hands the kernel gt_image as a bare pointer with image's extents.  A gt_image of another shape or
     on another device is a ValueError naming both, and one that requires grad goes to the framework chain and gets its
