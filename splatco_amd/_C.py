@@ -228,10 +228,46 @@ def check(rc):
         raise RuntimeError("splatco_raster: " + lib.scr_last_error().decode())
 
 
+_check = check          # call()'s `check` parameter shadows the function
+
+
 def stream(device=None):
     """The caller's current stream ON THE TENSORS' DEVICE (the process may have another device current).  Without a
     device: the current device's, for calls made inside a `torch.cuda.device(...)` block."""
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def call(name, *args, device=None, check=True):
+    """Launches the streamed entry point `name` (an scr_* function whose last header parameter is `void* stream`) with
+    `args` followed by the caller's current stream.  A tensor argument becomes its device address, None stays None (NULL),
+    everything else (numbers, ctypes arrays and structs, addresses already computed, `ptr(t)`) passes through.
+
+    Kernels launch on the CURRENT device and on the stream they are handed, so both are made the operands' here: the
+    device is `device` if given (calls whose operands arrive only in struct tables or pointer arrays must give it),
+    otherwise the first tensor argument's; it is current during the call, and the stream is the caller's current stream
+    on it.  Every tensor argument must live on that device: ValueError otherwise, before anything is launched.  A non-zero
+    status raises through check(); with check=False it is returned instead.  The function is looked up at call time."""
+    fn = getattr(lib, name)
+    if device is not None:
+        device = torch.device(device)
+    argv = list(args)
+    for i, a in enumerate(argv):
+        if isinstance(a, torch.Tensor):
+            if device is None:
+                device = a.device
+            elif a.device != device:
+                raise ValueError(f"{name}: argument {i} is on {a.device}, the launch is on {device}")
+            argv[i] = a.data_ptr()
+    if device is None:
+        raise ValueError(f"{name}: no tensor argument and no device= to launch on")
+    if device.index is not None and device.index == torch.cuda.current_device():
+        rc = fn(*argv, stream(device))          # already current (every single-GPU run): no guard to enter and leave
+    else:
+        with torch.cuda.device(device):
+            rc = fn(*argv, stream(device))
+    if check:
+        _check(rc)
+    return rc
 
 
 def ptr(t):

@@ -106,12 +106,10 @@ class FusedAdam(torch.optim.Optimizer):
                 e.numel = p.numel()
                 e.step_size = lr / (1.0 - b1 ** t)                     # doubles, as torch's Python forms them
                 e.bias_correction2_sqrt = math.sqrt(1.0 - b2 ** t)
-            with torch.cuda.device(dev):
-                if visible is not None and group.get("row_sparse", False):
-                    _C.check(_C.lib.scr_adam_step_rows(len(ps), table, _C.ptr(visible), visible.shape[0], b1, b2, float(group["eps"]),
-                                                       _C.stream(dev)))
-                else:
-                    _C.check(_C.lib.scr_adam_step(len(ps), table, b1, b2, float(group["eps"]), _C.stream(dev)))
+            if visible is not None and group.get("row_sparse", False):
+                _C.call("scr_adam_step_rows", len(ps), table, _C.ptr(visible), visible.shape[0], b1, b2, float(group["eps"]), device=dev)
+            else:
+                _C.call("scr_adam_step", len(ps), table, b1, b2, float(group["eps"]), device=dev)
             for p in ps:                        # the update is queued for every tensor of the group: the step counts move together
                 self.state[p]["step"] += 1
         return loss
@@ -126,8 +124,7 @@ def _adam_apply(entries, beta1, beta2, eps, device):
             raise ValueError("ShardedFusedAdam: parameters, gradients and moments must live on the GPU (no CPU path)")
         e.param, e.grad, e.exp_avg, e.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
         e.numel, e.step_size, e.bias_correction2_sqrt = p.numel(), step_size, bc2
-    with torch.cuda.device(device):
-        _C.check(_C.lib.scr_adam_step(len(entries), table, beta1, beta2, eps, _C.stream(device)))
+    _C.call("scr_adam_step", len(entries), table, beta1, beta2, eps, device=device)
 
 
 class ShardedFusedAdam:

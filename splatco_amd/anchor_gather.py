@@ -74,10 +74,16 @@ class DeferredDx:
         V, d = self.x.shape
         ld = (d + 3) // 4 * 4
         dx = torch.empty(V, ld, dtype=torch.float32, device=self.x.device)[:, :d]
-        with torch.cuda.device(self.x.device):
-            _C.check(_C.lib.scr_norm_linear_dx(V, d, self.x.data_ptr(), self.x.stride(0), self.dy.data_ptr(), self.dy.stride(0),
-                                               self.coef.data_ptr(), dx.data_ptr(), ld, _C.stream(self.x.device)))
+        _C.call("scr_norm_linear_dx", V, d, self.x, self.x.stride(0), self.dy, self.dy.stride(0), self.coef, dx, ld)
         return dx
+
+    @staticmethod
+    def kernel_args(box):
+        """The five arguments (coef, dy, ld dy, x, ld x) a producer's backward kernel takes to form the rows of dx itself;
+        all absent for no box or a box without coefficients."""
+        if box is None or box.coef is None:
+            return None, None, 0, None, 0
+        return box.coef, box.dy, box.dy.stride(0), box.x, box.x.stride(0)
 
     @staticmethod
     def is_token(t):
@@ -103,10 +109,7 @@ class _AnchorGather(torch.autograd.Function):
         # sums per workgroup): the fused BatchNorm-Linear skips its own pass over the matrix (gather_anchors hangs them on g_fea)
         stats = new(_C.lib.scr_anchor_gather_stat_buffer_rows(V), 2, 80) if V else new(0, 2, 80)
         if V:
-            with torch.cuda.device(dev):
-                _C.check(_C.lib.scr_anchor_gather(V, idx.data_ptr(), anchor_feat.data_ptr(), anchor.data_ptr(),
-                                                  offset.data_ptr(), scaling.data_ptr(), None, anc.data_ptr(),
-                                                  None, gs.data_ptr(), g72.data_ptr(), 72, stats.data_ptr(), _C.stream()))
+            _C.call("scr_anchor_gather", V, idx, anchor_feat, anchor, offset, scaling, None, anc, None, gs, g72, 72, stats)
         inv = getattr(idx, "_scr_inverse", None)       # left by expand.mask_indices: position of every anchor in idx, -1 = invisible
         if inv is not None and (inv.shape != (N,) or inv.device != dev):
             inv = None
@@ -129,12 +132,11 @@ class _AnchorGather(torch.autograd.Function):
             inv[idx] = torch.arange(V, device=dev)
         p = lambda t: None if t is None else t.contiguous().float()
         ldg = 71
-        box, nl = ctx.box, (None, None, 0, None, 0)
-        if box is not None and box.coef is not None:
-            # the BatchNorm-Linear's backward left its coefficients instead of dx: the kernel forms the rows (DeferredDx)
-            nl = (box.coef.data_ptr(), box.dy.data_ptr(), box.dy.stride(0), box.x.data_ptr(), box.x.stride(0))
-            if DeferredDx.is_token(d_g_fea):
-                d_g_fea = None                      # the stride-0 zeros it returned for g_fea: nothing else arrived
+        box = ctx.box
+        # where the BatchNorm-Linear's backward left its coefficients instead of dx, the kernel forms the rows (DeferredDx)
+        nl = DeferredDx.kernel_args(box)
+        if nl[0] is not None and DeferredDx.is_token(d_g_fea):
+            d_g_fea = None                          # the stride-0 zeros it returned for g_fea: nothing else arrived
         if d_g_fea is not None and d_g_fea.dtype == torch.float32 and d_g_fea.stride() == (72, 1):
             ldg = 72                                # rows as the fused BatchNorm-Linear backward leaves them: read in place
         else:
@@ -153,17 +155,16 @@ class _AnchorGather(torch.autograd.Function):
             new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
             g_feat, g_anchor, g_offset, g_scaling = new(N, 32), new(N, 3), new(N, 10, 3), new(N, 6)
             accumulate = 0
-        with torch.cuda.device(dev):
-            for r, (n0, n1) in enumerate(ranges):
-                # a range is the same kernel on offset pointers: a workgroup owns 64 consecutive anchors, their visible
-                # ones own consecutive upstream rows wherever the range starts (n0 is a multiple of 64)
-                if n1 > n0:
-                    _C.check(_C.lib.scr_anchor_gather_backward(
+        for r, (n0, n1) in enumerate(ranges):
+            # a range is the same kernel on offset pointers: a workgroup owns 64 consecutive anchors, their visible
+            # ones own consecutive upstream rows wherever the range starts (n0 is a multiple of 64)
+            if n1 > n0:
+                _C.call("scr_anchor_gather_backward",
                         n1 - n0, V, inv.data_ptr() + 8 * n0, _C.ptr(gs), _C.ptr(d_feat), _C.ptr(d_anc), _C.ptr(d_off),
                         _C.ptr(d_gs), _C.ptr(d_g_fea), ldg, g_feat.data_ptr() + 4 * 32 * n0, g_anchor.data_ptr() + 4 * 3 * n0,
-                        g_offset.data_ptr() + 4 * 30 * n0, g_scaling.data_ptr() + 4 * 6 * n0, accumulate, *nl, _C.stream(dev)))
-                if sink is not None and ranges is sink.ranges:
-                    sink.on_range(r)
+                        g_offset.data_ptr() + 4 * 30 * n0, g_scaling.data_ptr() + 4 * 6 * n0, accumulate, *nl, device=dev)
+            if sink is not None and ranges is sink.ranges:
+                sink.on_range(r)
         if box is not None:
             box.clear()                             # (the box outlives the graph on g_fea: let the tensors go)
         if sink is not None:

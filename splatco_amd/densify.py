@@ -38,10 +38,8 @@ def _knn_indices(points, k):
             raise ValueError("k <= 16")
         pts = points.detach().float().contiguous()
         out = torch.empty(N, k, dtype=torch.long, device=pts.device)
-        with torch.cuda.device(pts.device):
-            grid, spts, order, cell_start = buckets(pts)
-            _C.check(_C.lib.scr_knn(N, k, grid, spts.data_ptr(), order.data_ptr(), cell_start.data_ptr(), out.data_ptr(),
-                                    _C.stream()))
+        grid, spts, order, cell_start = buckets(pts)
+        _C.call("scr_knn", N, k, grid, spts, order, cell_start, out)
         return out
     out = torch.empty(N, k, dtype=torch.long, device=points.device)
     step = max(1, (1 << 24) // max(N, 1))
@@ -59,8 +57,7 @@ def compute_curvature(points, k=10):
         from . import _C
         p32 = pts.float().contiguous()
         out = torch.empty(p32.shape[0], dtype=torch.float32, device=p32.device)
-        with torch.cuda.device(p32.device):
-            _C.check(_C.lib.scr_knn_curvature(p32.shape[0], k, p32.data_ptr(), idx.data_ptr(), out.data_ptr(), _C.stream()))
+        _C.call("scr_knn_curvature", p32.shape[0], k, p32, idx, out)
         return out
     nb = pts[idx]                                                   # [N,k,3]
     c = nb - nb.mean(dim=1, keepdim=True)

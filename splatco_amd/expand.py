@@ -31,19 +31,16 @@ class _ExpandCompact(torch.autograd.Function):
         n = V * k
         scratch = _C.scratch(_C.lib.scr_expand_scratch_bytes(n), dev)
         cnt = C.c_int64(0)
-        with torch.cuda.device(dev):           # kernels launch on the CURRENT device: make it the tensors' device
-            _C.check(_C.lib.scr_expand_plan(n, _C.ptr(neural_opacity), scratch.data_ptr(), C.byref(cnt), _C.stream(dev)))
+        _C.call("scr_expand_plan", n, _C.ptr(neural_opacity), scratch, C.byref(cnt))
         P = int(cnt.value)
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         xyz, col, opa, sca, rot = new(P, 3), new(P, 3), new(P, 1), new(P, 3), new(P, 4)
         out_index = torch.empty(n, dtype=torch.int32, device=dev)
         mask = torch.empty(n, dtype=torch.bool, device=dev)
         if n:
-            with torch.cuda.device(dev):
-                _C.check(_C.lib.scr_expand_run(V, k, _C.ptr(neural_opacity), _C.ptr(color), _C.ptr(scale_rot), _C.ptr(offsets),
-                                               offsets.stride(0), _C.ptr(grid_scaling), _C.ptr(anchor), scratch.data_ptr(), out_index.data_ptr(),
-                                               mask.data_ptr(), _C.ptr(xyz), _C.ptr(col), _C.ptr(opa), _C.ptr(sca), _C.ptr(rot),
-                                               _C.stream(dev)))
+            _C.call("scr_expand_run", V, k, _C.ptr(neural_opacity), _C.ptr(color), _C.ptr(scale_rot), _C.ptr(offsets),
+                    offsets.stride(0), _C.ptr(grid_scaling), _C.ptr(anchor), scratch, out_index, mask, _C.ptr(xyz), _C.ptr(col),
+                    _C.ptr(opa), _C.ptr(sca), _C.ptr(rot))
         ctx.save_for_backward(scale_rot, offsets, grid_scaling, out_index)
         ctx.dims = (V, k)
         ctx.mark_non_differentiable(mask, out_index)
@@ -66,12 +63,9 @@ class _ExpandCompact(torch.autograd.Function):
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         d_no, d_col, d_sr, d_off, d_gs, d_an = new(n, 1), new(n, 3), new(n, 7), new(V, k, 3), new(V, 6), new(V, 3)
         if n:
-            with torch.cuda.device(dev):
-                _C.check(_C.lib.scr_expand_backward(V, k, _C.ptr(scale_rot), _C.ptr(offsets), offsets.stride(0), _C.ptr(grid_scaling),
-                                                    out_index.data_ptr(), _C.ptr(g_xyz), _C.ptr(g_col), _C.ptr(g_opa),
-                                                    _C.ptr(g_sca), _C.ptr(g_rot), d_no.data_ptr(), d_col.data_ptr(),
-                                                    d_sr.data_ptr(), d_off.data_ptr(), d_gs.data_ptr(), d_an.data_ptr(),
-                                                    _C.ptr(g_tap), P, _C.stream(dev)))
+            _C.call("scr_expand_backward", V, k, _C.ptr(scale_rot), _C.ptr(offsets), offsets.stride(0), _C.ptr(grid_scaling),
+                    out_index, _C.ptr(g_xyz), _C.ptr(g_col), _C.ptr(g_opa), _C.ptr(g_sca), _C.ptr(g_rot), d_no, d_col, d_sr, d_off,
+                    d_gs, d_an, _C.ptr(g_tap), P)
         return d_no, d_col, d_sr, d_off, d_gs, d_an, None
 
 
@@ -127,13 +121,11 @@ def mask_indices(mask, inverse=True):
     n = m.shape[0]
     scratch = _C.scratch(_C.lib.scr_expand_scratch_bytes(n), m.device)
     cnt = C.c_int64(0)
-    with torch.cuda.device(m.device):          # the plan call reads its count back on the host: one synchronisation
-        _C.check(_C.lib.scr_mask_index_plan(n, m.data_ptr(), scratch.data_ptr(), C.byref(cnt), _C.stream(m.device)))
-        idx = torch.empty(cnt.value, dtype=torch.int64, device=m.device)
-        inv = torch.empty(n, dtype=torch.int64, device=m.device) if inverse and n else None
-        if n and (cnt.value or inv is not None):
-            _C.check(_C.lib.scr_mask_index_run(n, m.data_ptr(), scratch.data_ptr(), idx.data_ptr() if cnt.value else None,
-                                               inv.data_ptr() if inv is not None else None, _C.stream(m.device)))
+    _C.call("scr_mask_index_plan", n, m, scratch, C.byref(cnt))      # reads its count back on the host: one synchronisation
+    idx = torch.empty(cnt.value, dtype=torch.int64, device=m.device)
+    inv = torch.empty(n, dtype=torch.int64, device=m.device) if inverse and n else None
+    if n and (cnt.value or inv is not None):
+        _C.call("scr_mask_index_run", n, m, scratch, _C.ptr(idx), inv)
     if inv is not None:
         idx._scr_inverse = inv
     return idx

@@ -15,9 +15,8 @@ def bounds(pts):
         from . import _C
         N, dev = pts.shape[0], pts.device
         out = torch.empty(7, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            scratch = _C.scratch(_C.lib.scr_points_bounds_scratch_bytes(N), dev)
-            _C.check(_C.lib.scr_points_bounds(N, pts.data_ptr(), scratch.data_ptr(), out.data_ptr(), _C.stream(dev)))
+        scratch = _C.scratch(_C.lib.scr_points_bounds_scratch_bytes(N), dev)
+        _C.call("scr_points_bounds", N, pts, scratch, out)
         out = out.cpu().numpy()
         lo, hi, bad = out[:3], out[3:6], out[6] > 0
     else:
@@ -62,14 +61,13 @@ def buckets(pts):
     from . import _C
     N, dev = pts.shape[0], pts.device
     lo, hi = bounds(pts)
-    st = _C.stream(dev)
     keys = torch.empty(N, dtype=torch.long, device=dev)
     h = None
     for attempt in range(2):
         h, (nx, ny, nz), slack = grid(lo, hi, N, h)
         ncell = nx * ny * nz
         grid_host = _C.host_array((float(lo[0]), float(lo[1]), float(lo[2]), float(h), nx, ny, nz, slack), _C.f32)
-        _C.check(_C.lib.scr_knn_cell_keys(N, grid_host, pts.data_ptr(), keys.data_ptr(), st))
+        _C.call("scr_knn_cell_keys", N, grid_host, pts, keys)
         counts = torch.bincount(keys, minlength=ncell)
         if attempt:
             break

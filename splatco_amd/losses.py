@@ -58,9 +58,7 @@ class _L1Ssim(torch.autograd.Function):
         C, H, W = x.shape
         scratch = torch.empty(_C.lib.scr_l1_ssim_scratch_bytes(C, H, W, int(need)), dtype=torch.uint8, device=x.device)
         out = torch.empty(2, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):      # kernels launch on the CURRENT device: make it the tensors' device
-            _C.check(_C.lib.scr_l1_ssim_forward(C, H, W, x.data_ptr(), y.data_ptr(), scratch.data_ptr(), int(need),
-                                                out.data_ptr(), _C.stream(x.device)))
+        _C.call("scr_l1_ssim_forward", C, H, W, x, y, scratch, int(need), out)
         ctx.save_for_backward(x, y, scratch)
         ctx.have_maps = need
         return out[0], out[1]
@@ -75,9 +73,7 @@ class _L1Ssim(torch.autograd.Function):
         g_l1 = g_l1.contiguous().float().reshape(1)
         g_ssim = g_ssim.contiguous().float().reshape(1)
         dx = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _C.check(_C.lib.scr_l1_ssim_backward(C, H, W, x.data_ptr(), y.data_ptr(), scratch.data_ptr(),
-                                                 g_l1.data_ptr(), g_ssim.data_ptr(), dx.data_ptr(), _C.stream(x.device)))
+        _C.call("scr_l1_ssim_backward", C, H, W, x, y, scratch, g_l1, g_ssim, dx)
         return dx, None
 
 
@@ -93,9 +89,7 @@ class _PairL1(torch.autograd.Function):
         n, dev = gen1.numel(), gen1.device
         scratch = torch.empty(_C.lib.scr_pair_l1_scratch_bytes(n), dtype=torch.uint8, device=dev)
         out = torch.empty(1, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_pair_l1_forward(n, gen1.data_ptr(), gen2.data_ptr(), real1.data_ptr(), real2.data_ptr(),
-                                                scratch.data_ptr(), out.data_ptr(), _C.stream(dev)))
+        _C.call("scr_pair_l1_forward", n, gen1, gen2, real1, real2, scratch, out)
         ctx.save_for_backward(gen1, gen2, real1, real2)
         return out.reshape(())
 
@@ -103,14 +97,11 @@ class _PairL1(torch.autograd.Function):
     def backward(ctx, g):
         from . import _C
         gen1, gen2, real1, real2 = ctx.saved_tensors
-        n, dev = gen1.numel(), gen1.device
+        n = gen1.numel()
         g = g.contiguous().float().reshape(1)
         d1 = torch.empty_like(gen1) if ctx.needs_input_grad[0] else None
         d2 = torch.empty_like(gen2) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_pair_l1_backward(n, gen1.data_ptr(), gen2.data_ptr(), real1.data_ptr(), real2.data_ptr(), g.data_ptr(),
-                                                 None if d1 is None else d1.data_ptr(), None if d2 is None else d2.data_ptr(),
-                                                 _C.stream(dev)))
+        _C.call("scr_pair_l1_backward", n, gen1, gen2, real1, real2, g, d1, d2)
         return d1, d2, None, None
 
 
@@ -145,8 +136,7 @@ class _ScalingReg(torch.autograd.Function):
         P = s.shape[0]
         scratch = torch.empty(_C.lib.scr_scaling_reg_scratch_bytes(P), dtype=torch.uint8, device=s.device)
         out = torch.empty(1, dtype=torch.float32, device=s.device)
-        with torch.cuda.device(s.device):
-            _C.check(_C.lib.scr_scaling_reg_forward(P, s.data_ptr(), scratch.data_ptr(), out.data_ptr(), _C.stream(s.device)))
+        _C.call("scr_scaling_reg_forward", P, s, scratch, out)
         ctx.save_for_backward(s)
         return out.reshape(())
 
@@ -156,8 +146,7 @@ class _ScalingReg(torch.autograd.Function):
         (s,) = ctx.saved_tensors
         g = g.contiguous().float().reshape(1)
         d = torch.empty_like(s)
-        with torch.cuda.device(s.device):
-            _C.check(_C.lib.scr_scaling_reg_backward(s.shape[0], s.data_ptr(), g.data_ptr(), d.data_ptr(), _C.stream(s.device)))
+        _C.call("scr_scaling_reg_backward", s.shape[0], s, g, d)
         return d
 
 
@@ -174,8 +163,7 @@ class _ScalingRegTap(torch.autograd.Function):
         P = s.shape[0]
         scratch = torch.empty(_C.lib.scr_scaling_reg_scratch_bytes(P), dtype=torch.uint8, device=s.device)
         out = torch.empty(1, dtype=torch.float32, device=s.device)
-        with torch.cuda.device(s.device):
-            _C.check(_C.lib.scr_scaling_reg_forward(P, s.data_ptr(), scratch.data_ptr(), out.data_ptr(), _C.stream(s.device)))
+        _C.call("scr_scaling_reg_forward", P, s, scratch, out)
         return out.reshape(())
 
     @staticmethod
@@ -248,9 +236,7 @@ class _DepthLoss(torch.autograd.Function):
         dev = depth.device
         scratch = torch.empty(_C.lib.scr_depth_loss_scratch_bytes(H, W), dtype=torch.uint8, device=dev)
         out = torch.empty(4, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_depth_loss_forward(H, W, depth.data_ptr(), alpha.data_ptr(), target.data_ptr(), _C.ptr(mask), kind,
-                                                   mode, int(align), min_alpha, scratch.data_ptr(), out.data_ptr(), _C.stream(dev)))
+        _C.call("scr_depth_loss_forward", H, W, depth, alpha, target, _C.ptr(mask), kind, mode, int(align), min_alpha, scratch, out)
         ctx.save_for_backward(depth, alpha, target, mask, scratch)
         ctx.args = (kind, mode, min_alpha)
         stats = out[1:]
@@ -263,15 +249,10 @@ class _DepthLoss(torch.autograd.Function):
         depth, alpha, target, mask, scratch = ctx.saved_tensors
         kind, mode, min_alpha = ctx.args
         H, W = depth.shape
-        dev = depth.device
         g = g.contiguous().float().reshape(1)
         dd = torch.empty_like(depth) if ctx.needs_input_grad[0] else None
         da = torch.empty_like(alpha) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_depth_loss_backward(H, W, depth.data_ptr(), alpha.data_ptr(), target.data_ptr(), _C.ptr(mask), kind,
-                                                    mode, min_alpha, scratch.data_ptr(), g.data_ptr(),
-                                                    None if dd is None else dd.data_ptr(), None if da is None else da.data_ptr(),
-                                                    _C.stream(dev)))
+        _C.call("scr_depth_loss_backward", H, W, depth, alpha, target, _C.ptr(mask), kind, mode, min_alpha, scratch, g, dd, da)
         return dd, da, None, None, None, None, None
 
 

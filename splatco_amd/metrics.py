@@ -68,11 +68,8 @@ def _flip_run(test, reference, pixels_per_degree, quantize, return_map):
     mean = torch.empty(N, dtype=torch.float32, device=dev)
     mse = torch.empty(N, dtype=torch.float32, device=dev)
     fmap = torch.empty(N, H, W, dtype=torch.float32, device=dev) if return_map else None
-    with torch.cuda.device(dev):
-        rc = _C.lib.scr_flip_forward(N, H, W, t.data_ptr(), r.data_ptr(), float(pixels_per_degree), int(bool(quantize)),
-                                     scratch.data_ptr(), mean.data_ptr(), mse.data_ptr(),
-                                     None if fmap is None else fmap.data_ptr(), _C.stream(dev))
-    if rc != 0:
+    if _C.call("scr_flip_forward", N, H, W, t, r, float(pixels_per_degree), int(bool(quantize)), scratch, mean, mse, fmap,
+                check=False) != 0:
         raise ValueError("flip: " + _C.lib.scr_last_error().decode())
     if single:
         mean, mse = mean[0], mse[0]
@@ -131,7 +128,5 @@ def ssim_value(a, b):
     Cc, H, W = x.shape
     scratch = torch.empty(_C.lib.scr_l1_ssim_scratch_bytes(Cc, H, W, 0), dtype=torch.uint8, device=x.device)
     out = torch.empty(2, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _C.check(_C.lib.scr_l1_ssim_forward(Cc, H, W, x.data_ptr(), y.data_ptr(), scratch.data_ptr(), 0, out.data_ptr(),
-                                            _C.stream(x.device)))
+    _C.call("scr_l1_ssim_forward", Cc, H, W, x, y, scratch, 0, out)
     return out[1]

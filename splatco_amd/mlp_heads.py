@@ -41,10 +41,7 @@ class _MlpHeads(torch.autograd.Function):
         out_o, out_c, out_v = new(V, 10), new(V, 30), new(V, 70)
         hidden = _C.scratch(_C.lib.scr_mlp_heads_hidden_bytes(V), dev)
         if V:
-            with torch.cuda.device(dev):
-                _C.check(_C.lib.scr_mlp_heads_forward(V, feat.data_ptr(), feat.stride(0), anchor.data_ptr(), campos.data_ptr(), geo_a.data_ptr(),
-                                                      geo_b.data_ptr(), *[t.data_ptr() for t in ws], hidden.data_ptr(), out_o.data_ptr(),
-                                                      out_c.data_ptr(), out_v.data_ptr(), _C.stream()))
+            _C.call("scr_mlp_heads_forward", V, feat, feat.stride(0), anchor, campos, geo_a, geo_b, *ws, hidden, out_o, out_c, out_v)
         ctx.save_for_backward(feat, anchor, campos, geo_a, geo_b, ws[0], ws[2], ws[4], ws[6], hidden, out_o, out_c)
         return out_o, out_c, out_v
 
@@ -63,13 +60,9 @@ class _MlpHeads(torch.autograd.Function):
                 t.zero_()
         else:
             partial = _C.scratch(_C.lib.scr_mlp_heads_partial_bytes(V), dev)
-            with torch.cuda.device(dev):
-                _C.check(_C.lib.scr_mlp_heads_backward(
-                    V, feat.data_ptr(), feat.stride(0), anchor.data_ptr(), campos.data_ptr(), geo_a.data_ptr(), geo_b.data_ptr(), w1.data_ptr(), w2o.data_ptr(),
-                    w2c.data_ptr(), w2v.data_ptr(), hidden.data_ptr(), out_o.data_ptr(), out_c.data_ptr(), g_o.data_ptr(),
-                    g_c.data_ptr(), g_v.data_ptr(), partial.data_ptr(), d_feat.data_ptr(), d_anchor.data_ptr(),
-                    d_geo_a.data_ptr(), d_geo_b.data_ptr(), d_w1.data_ptr(), d_b1.data_ptr(), d_w2o.data_ptr(), d_b2o.data_ptr(), d_w2c.data_ptr(),
-                    d_b2c.data_ptr(), d_w2v.data_ptr(), d_b2v.data_ptr(), _C.stream()))
+            _C.call("scr_mlp_heads_backward", V, feat, feat.stride(0), anchor, campos, geo_a, geo_b, w1, w2o, w2c, w2v, hidden,
+                    out_o, out_c, g_o, g_c, g_v, partial, d_feat, d_anchor, d_geo_a, d_geo_b, d_w1, d_b1, d_w2o, d_b2o, d_w2c, d_b2c,
+                    d_w2v, d_b2v)
         return d_feat, d_anchor, None, d_geo_a, d_geo_b, d_w1, d_b1, d_w2o, d_b2o, d_w2c, d_b2c, d_w2v, d_b2v
 
 

@@ -23,38 +23,26 @@ def _channel_mlp(avg, mx, w1, w2):
 class _AttendedPairs(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xy, xz, yz, w1, w2, wc):
-        with torch.cuda.device(xy.device):     # kernels launch on the CURRENT device: make it the tensors' device
-            return _AttendedPairs._forward(ctx, xy, xz, yz, w1, w2, wc)
-
-    @staticmethod
-    def _forward(ctx, xy, xz, yz, w1, w2, wc):
         R, H, W = xy.shape[1], xy.shape[2], xy.shape[3]
         dev, C3 = xy.device, 3 * R
         planes = [p.detach().contiguous().float() for p in (xy, xz, yz)]
         scratch = torch.empty(_C.lib.scr_tpa_scratch_bytes(R, H, W), dtype=torch.uint8, device=dev)
         avg, mx = torch.empty(C3, device=dev), torch.empty(C3, device=dev)
         arg = torch.empty(C3, dtype=torch.int32, device=dev)
-        _C.check(_C.lib.scr_tpa_stats(R, H, W, *(p.data_ptr() for p in planes), avg.data_ptr(), mx.data_ptr(),
-                                      arg.data_ptr(), scratch.data_ptr(), _C.stream()))
+        _C.call("scr_tpa_stats", R, H, W, *planes, avg, mx, arg, scratch)
         ca = _channel_mlp(avg, mx, w1.detach().float(), w2.detach().float()).contiguous()
         wcc = wc.detach().contiguous().float()
         s = torch.empty(2, H, W, device=dev)
         am = torch.empty(H * W, dtype=torch.uint8, device=dev)
         sa = torch.empty(H, W, device=dev)
         out = [torch.empty(1, 2 * R, H, W, device=dev) for _ in range(3)]
-        _C.check(_C.lib.scr_tpa_forward(R, H, W, *(p.data_ptr() for p in planes), ca.data_ptr(), wcc.data_ptr(),
-                                        s.data_ptr(), am.data_ptr(), sa.data_ptr(), *(o.data_ptr() for o in out), _C.stream()))
+        _C.call("scr_tpa_forward", R, H, W, *planes, ca, wcc, s, am, sa, *out)
         ctx.save_for_backward(*planes, w1, w2, wcc, avg, mx, arg, ca, s, am, sa)
         ctx.dims = (R, H, W)
         return tuple(out)
 
     @staticmethod
     def backward(ctx, g0, g1, g2):
-        with torch.cuda.device(g0.device):
-            return _AttendedPairs._backward(ctx, g0, g1, g2)
-
-    @staticmethod
-    def _backward(ctx, g0, g1, g2):
         p0, p1, p2, w1, w2, wcc, avg, mx, arg, ca, s, am, sa = ctx.saved_tensors
         R, H, W = ctx.dims
         dev, C3 = p0.device, 3 * R
@@ -62,17 +50,13 @@ class _AttendedPairs(torch.autograd.Function):
         d = [torch.empty(1, R, H, W, device=dev) for _ in range(3)]
         dca, dw = torch.empty(C3, device=dev), torch.empty(2 * 49, device=dev)
         scratch = torch.empty(_C.lib.scr_tpa_scratch_bytes(R, H, W), dtype=torch.uint8, device=dev)
-        _C.check(_C.lib.scr_tpa_backward(R, H, W, p0.data_ptr(), p1.data_ptr(), p2.data_ptr(), ca.data_ptr(), wcc.data_ptr(),
-                                         s.data_ptr(), am.data_ptr(), sa.data_ptr(), *(g.data_ptr() for g in gs),
-                                         *(t.data_ptr() for t in d), dca.data_ptr(), dw.data_ptr(), scratch.data_ptr(),
-                                         _C.stream()))
+        _C.call("scr_tpa_backward", R, H, W, p0, p1, p2, ca, wcc, s, am, sa, *gs, *d, dca, dw, scratch)
         # the 15-number MLP and its sigmoid: re-run under autograd (a dozen tiny kernels)
         with torch.enable_grad():
             a_, m_ = avg.detach().requires_grad_(True), mx.detach().requires_grad_(True)
             w1_, w2_ = w1.detach().float().requires_grad_(True), w2.detach().float().requires_grad_(True)
             davg, dmx, dw1, dw2 = torch.autograd.grad(_channel_mlp(a_, m_, w1_, w2_), (a_, m_, w1_, w2_), dca)
-        _C.check(_C.lib.scr_tpa_backward_stats(R, H, W, davg.contiguous().data_ptr(), dmx.contiguous().data_ptr(),
-                                               arg.data_ptr(), *(t.data_ptr() for t in d), _C.stream()))
+        _C.call("scr_tpa_backward_stats", R, H, W, davg.contiguous(), dmx.contiguous(), arg, *d)
         return d[0], d[1], d[2], dw1.reshape(w1.shape), dw2.reshape(w2.shape), dw.reshape(1, 2, 7, 7)
 
 

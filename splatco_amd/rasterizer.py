@@ -98,9 +98,8 @@ class RasterState:
         shape, dt = shapes[which]
         out = torch.empty(shape, dtype=dt, device=dev)
         if out.numel():
-          with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_debug_get(which, self.P, self.I, self.cs.H, self.cs.W, _C.ptr(self.geom),
-                                          _C.ptr(self.binning), _C.ptr(self.image), out.data_ptr(), _C.stream()))
+            _C.call("scr_debug_get", which, self.P, self.I, self.cs.H, self.cs.W, _C.ptr(self.geom), _C.ptr(self.binning),
+                    _C.ptr(self.image), out)
         return out
 
 
@@ -125,7 +124,7 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
     st.aux = None
     if aux:
         st.aux = (torch.empty(cs.H, cs.W, dtype=torch.float32, device=dev), torch.empty(cs.H, cs.W, dtype=torch.float32, device=dev))
-    maps = (None, None) if st.aux is None else (st.aux[0].data_ptr(), st.aux[1].data_ptr())
+    maps = st.aux or (None, None)
     mode = _C.MODE_ANTIALIASED if antialiased else 0
     plan = (C.c_int64 * 4)(0, 0, 0, 0)   # (tile instances, largest per-tile instance count, phase 2 already ran, plan flags)
     # The binning buffer's size is only known after the plan phase.  A guess from the previous call of this size (the
@@ -134,25 +133,21 @@ def rasterize_forward(cs, means3D, opacities, scales, rotations, cov3D_precomp, 
     key = (dev.index, cs.H, cs.W)
     guess = _plan_guess.get(key)      # (P, instances, largest tile) of the last forward at this resolution
     spec = None
-    with torch.cuda.device(dev):      # kernels launch on the CURRENT device: make it the tensors' device
-        if SPECULATE and guess is not None and guess[0] > 0 and 0.5 <= P / guess[0] <= 2.0:
-            scale = 1.06 * P / guess[0]
-            cap = _C.lib.scr_binning_bytes(min(int(guess[1] * scale) + 4096, (1 << 32) - 2), max(int(guess[2] * 1.25), guess[2] + 64))
-            spec = _C.scratch(cap, dev)
-        _C.check(_C.lib.scr_forward_plan_run(
-            mode, P, M, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D_precomp),
-            _C.ptr(opacities), _C.ptr(shs), _C.ptr(colors_precomp), cs.ref(),
-            st.geom.data_ptr(), _C.ptr(radii), plan, None if spec is None else spec.data_ptr(),
-            0 if spec is None else spec.numel(), st.image.data_ptr(), color.data_ptr(), *maps, _C.stream()))
-        st.I, st.max_tile, st.flags = int(plan[0]), int(plan[1]), int(plan[3])
-        _plan_guess[key] = (P, st.I, st.max_tile)
-        if plan[2]:
-            st.binning = spec
-        else:
-            del spec
-            st.binning = _C.scratch(_C.lib.scr_binning_bytes(st.I, st.max_tile), dev)
-            _C.check(_C.lib.scr_forward_run(P, st.I, st.max_tile, st.flags, cs.ref(), st.geom.data_ptr(), st.binning.data_ptr(),
-                                            st.image.data_ptr(), color.data_ptr(), *maps, _C.stream()))
+    if SPECULATE and guess is not None and guess[0] > 0 and 0.5 <= P / guess[0] <= 2.0:
+        scale = 1.06 * P / guess[0]
+        cap = _C.lib.scr_binning_bytes(min(int(guess[1] * scale) + 4096, (1 << 32) - 2), max(int(guess[2] * 1.25), guess[2] + 64))
+        spec = _C.scratch(cap, dev)
+    _C.call("scr_forward_plan_run", mode, P, M, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D_precomp),
+            _C.ptr(opacities), _C.ptr(shs), _C.ptr(colors_precomp), cs.ref(), st.geom, _C.ptr(radii), plan, spec,
+            0 if spec is None else spec.numel(), st.image, color, *maps)
+    st.I, st.max_tile, st.flags = int(plan[0]), int(plan[1]), int(plan[3])
+    _plan_guess[key] = (P, st.I, st.max_tile)
+    if plan[2]:
+        st.binning = spec
+    else:
+        del spec
+        st.binning = _C.scratch(_C.lib.scr_binning_bytes(st.I, st.max_tile), dev)
+        _C.call("scr_forward_run", P, st.I, st.max_tile, st.flags, cs.ref(), st.geom, st.binning, st.image, color, *maps)
     st.radii = radii
     return color, radii, st
 
@@ -259,13 +254,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             g_cam = tuple(cam_buf[lo:hi] if w else None for (lo, hi), w in zip(((0, 16), (16, 32), (32, 35)), want_cam))
         scratch = _C.scratch(_C.lib.scr_backward_scratch_bytes(st.I, P, int(aux), int(bool(g_cam))), dev)
         try:
-          with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_backward(
-                P, st.M, st.I, st.flags, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D),
-                _C.ptr(sh), cs.ref(), st.radii.data_ptr(), st.geom.data_ptr(), st.binning.data_ptr(), st.image.data_ptr(),
-                g.data_ptr(), _C.ptr(g_depth), _C.ptr(g_alpha), scratch.data_ptr(), g_means3D.data_ptr(),
-                g_means2D.data_ptr(), _C.ptr(g_col), _C.ptr(g_sh), g_op.data_ptr(), _C.ptr(g_scales), _C.ptr(g_rot),
-                _C.ptr(g_cov), *(_C.ptr(t) for t in g_cam or (None,) * 3), _C.stream()))
+            _C.call("scr_backward", P, st.M, st.I, st.flags, _C.ptr(means3D), _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D),
+                    _C.ptr(sh), cs.ref(), st.radii, st.geom, st.binning, st.image, g, _C.ptr(g_depth), _C.ptr(g_alpha), scratch,
+                    g_means3D, g_means2D, _C.ptr(g_col), _C.ptr(g_sh), g_op, _C.ptr(g_scales), _C.ptr(g_rot), _C.ptr(g_cov),
+                    *(_C.ptr(t) for t in g_cam or (None,) * 3))
         except RuntimeError as e:
             if ctx.raster_settings.debug:
                 raise RuntimeError(str(e) + _debug_dump("snapshot_bw.dump", ctx.raster_settings, means3D=means3D, sh=sh,
@@ -309,8 +301,7 @@ class GaussianRasterizer(nn.Module):
             out = torch.zeros(P, dtype=torch.uint8, device=positions.device)
             view = _dev_f32(self.raster_settings.viewmatrix, "viewmatrix")
             if P:
-                with torch.cuda.device(positions.device):
-                    _C.check(_C.lib.scr_mark_visible(P, positions.data_ptr(), view.data_ptr(), out.data_ptr(), _C.stream()))
+                _C.call("scr_mark_visible", P, positions, view, out)
             return out.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -342,7 +333,5 @@ class GaussianRasterizer(nn.Module):
             P = means3D.shape[0]
             radii = torch.empty(P, dtype=torch.int32, device=means3D.device)  # filter_kernel writes every entry
             if P:
-                with torch.cuda.device(means3D.device):
-                    _C.check(_C.lib.scr_visible_filter(P, means3D.data_ptr(), _C.ptr(scales), _C.ptr(rotations),
-                                                       _C.ptr(cov3D_precomp), cs.ref(), radii.data_ptr(), _C.stream()))
+                _C.call("scr_visible_filter", P, means3D, _C.ptr(scales), _C.ptr(rotations), _C.ptr(cov3D_precomp), cs.ref(), radii)
             return radii

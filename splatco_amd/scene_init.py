@@ -43,11 +43,9 @@ def _points(points):
 def _dist2_device(pts):
     from . import _C
     N, dev = pts.shape[0], pts.device
-    with torch.cuda.device(dev):
-        grid, spts, order, cell_start = buckets(pts)
-        out = torch.empty(N, dtype=torch.float32, device=dev)
-        _C.check(_C.lib.scr_knn3_dist2(N, grid, spts.data_ptr(), order.data_ptr(), cell_start.data_ptr(), out.data_ptr(),
-                                       _C.stream(dev)))
+    grid, spts, order, cell_start = buckets(pts)
+    out = torch.empty(N, dtype=torch.float32, device=dev)
+    _C.call("scr_knn3_dist2", N, grid, spts, order, cell_start, out)
     return out
 
 
@@ -103,20 +101,18 @@ def _unique_rows(q, v):
 def _voxelize_device(pts, v, lo, packed):
     from . import _C
     N, dev = pts.shape[0], pts.device
-    st = _C.stream(dev)
     lo_host = _C.host_array([int(a) for a in lo], _C.i32)
-    with torch.cuda.device(dev):
-        keys = torch.empty((N,) if packed else (N, 3), dtype=torch.long, device=dev)
-        _C.check(_C.lib.scr_voxel_keys(N, pts.data_ptr(), float(v), lo_host, int(packed), keys.data_ptr(), st))
-        if not packed:
-            return _unique_rows(keys, v)
-        skeys = torch.sort(keys).values
-        del keys
-        scratch = _C.scratch(_C.lib.scr_voxel_unique_scratch_bytes(N), dev)
-        cnt = C.c_int64(0)
-        _C.check(_C.lib.scr_voxel_unique_plan(N, skeys.data_ptr(), scratch.data_ptr(), C.byref(cnt), st))
-        out = torch.empty(cnt.value, 3, dtype=torch.float32, device=dev)
-        _C.check(_C.lib.scr_voxel_unique_run(N, skeys.data_ptr(), scratch.data_ptr(), float(v), lo_host, out.data_ptr(), st))
+    keys = torch.empty((N,) if packed else (N, 3), dtype=torch.long, device=dev)
+    _C.call("scr_voxel_keys", N, pts, float(v), lo_host, int(packed), keys)
+    if not packed:
+        return _unique_rows(keys, v)
+    skeys = torch.sort(keys).values
+    del keys
+    scratch = _C.scratch(_C.lib.scr_voxel_unique_scratch_bytes(N), dev)
+    cnt = C.c_int64(0)
+    _C.call("scr_voxel_unique_plan", N, skeys, scratch, C.byref(cnt))
+    out = torch.empty(cnt.value, 3, dtype=torch.float32, device=dev)
+    _C.call("scr_voxel_unique_run", N, skeys, scratch, float(v), lo_host, out)
     return out
 
 

@@ -129,11 +129,8 @@ class _NormLinearFn(torch.autograd.Function):
             # column statistics the producer of x formed on the way (anchor_gather): [rows, 2, 80] partial sums about x[0]
             ok_stats = (col_stats is not None and col_stats.is_cuda and col_stats.dtype == torch.float32 and col_stats.dim() == 3
                         and col_stats.shape[1:] == (2, 80) and col_stats.shape[0] > 0 and col_stats.is_contiguous())
-            with torch.cuda.device(x.device):
-                _C.check(_C.lib.scr_norm_linear_forward(V, d, x.data_ptr(), x.stride(0), Gc.data_ptr(), cc.data_ptr(), float(eps),
-                                                        y.data_ptr(), mean.data_ptr(), var.data_ptr(), inv.data_ptr(),
-                                                        scratch.data_ptr(), col_stats.data_ptr() if ok_stats else None,
-                                                        col_stats.shape[0] if ok_stats else 0, _C.stream()))
+            _C.call("scr_norm_linear_forward", V, d, x, x.stride(0), Gc, cc, float(eps), y, mean, var, inv, scratch,
+                    col_stats if ok_stats else None, col_stats.shape[0] if ok_stats else 0)
             ctx.save_for_backward(x, Gc, mean, inv)
             ctx.mark_non_differentiable(mean, var)
             return y, mean, var
@@ -162,11 +159,7 @@ class _NormLinearFn(torch.autograd.Function):
             dc = torch.empty(32, dtype=torch.float32, device=x.device)
             coef = torch.empty(34, 80, dtype=torch.float32, device=x.device) if defer is not None else None
             scratch = _C.scratch(_C.lib.scr_norm_linear_scratch_bytes(V), x.device)
-            with torch.cuda.device(x.device):
-                _C.check(_C.lib.scr_norm_linear_backward(V, d, x.data_ptr(), x.stride(0), dy.data_ptr(), dy.stride(0), G.data_ptr(),
-                                                         mean.data_ptr(), inv.data_ptr(), dx.data_ptr() if dx is not None else None,
-                                                         ldx, dG.data_ptr(), dc.data_ptr(), scratch.data_ptr(),
-                                                         coef.data_ptr() if coef is not None else None, _C.stream()))
+            _C.call("scr_norm_linear_backward", V, d, x, x.stride(0), dy, dy.stride(0), G, mean, inv, dx, ldx, dG, dc, scratch, coef)
             if defer is not None:
                 # the producer of x (the anchor gather) forms dx = k0 + x k1 + dy Gi inside its own backward kernel: it gets the
                 # coefficients, and autograd a gradient of zeros that occupies no memory (anchor_gather.DeferredDx)
@@ -202,9 +195,7 @@ class _NormFold(torch.autograd.Function):
         W, b, ga, be = ts[0::4], ts[1::4], ts[2::4], ts[3::4]
         G, c = torch.empty(32, d, device=dev), torch.empty(32, device=dev)
         wi, ci = _C.host_array(widths), _C.host_array(cols)
-        with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_norm_fold(L, d, wi, ci, at, _C.ptr_array(W), _C.ptr_array(b), _C.ptr_array(ga), _C.ptr_array(be),
-                                          G.data_ptr(), c.data_ptr(), _C.stream(dev)))
+        _C.call("scr_norm_fold", L, d, wi, ci, at, _C.ptr_array(W), _C.ptr_array(b), _C.ptr_array(ga), _C.ptr_array(be), G, c)
         ctx.save_for_backward(*W, *ga, *be)
         ctx.meta = (d, tuple(widths), tuple(cols), None if col_at is None else tuple(col_at))
         return G, c
@@ -224,10 +215,8 @@ class _NormFold(torch.autograd.Function):
         db = [torch.empty(32, device=dev) for _ in range(L)]
         dga, dbe = [torch.empty_like(g) for g in ga], [torch.empty_like(g) for g in be]
         wi, ci = _C.host_array(widths), _C.host_array(cols)
-        with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_norm_fold_backward(L, d, wi, ci, at, _C.ptr_array(W), _C.ptr_array(ga), _C.ptr_array(be), dG.data_ptr(),
-                                                   dc.data_ptr(), _C.ptr_array(dW), _C.ptr_array(db), _C.ptr_array(dga),
-                                                   _C.ptr_array(dbe), _C.stream(dev)))
+        _C.call("scr_norm_fold_backward", L, d, wi, ci, at, _C.ptr_array(W), _C.ptr_array(ga), _C.ptr_array(be), dG, dc,
+                 _C.ptr_array(dW), _C.ptr_array(db), _C.ptr_array(dga), _C.ptr_array(dbe), device=dev)
         out = []
         for i in range(L):
             out += [dW[i], db[i], dga[i], dbe[i]]
@@ -283,13 +272,11 @@ def _norm_linear(x, bns, linears, col_at=None):
             # nn.BatchNorm1d's running-statistics update for all pairs in one launch (six tiny kernels per BatchNorm otherwise)
             from . import _C
             L = len(bns)
-            with torch.cuda.device(x.device):
-                _C.check(_C.lib.scr_norm_running_stats(
-                    L, d, _C.host_array(widths), _C.host_array(cols),
+            _C.call("scr_norm_running_stats", L, d, _C.host_array(widths), _C.host_array(cols),
                     None if col_at is None else _C.host_array([int(v) for v in col_at], _C.u8),
                     _C.host_array([float(bn.momentum) for bn in bns], _C.f32),
                     _C.ptr_array([bn.running_mean for bn in bns]), _C.ptr_array([bn.running_var for bn in bns]),
-                    _C.ptr_array([bn.num_batches_tracked for bn in bns]), mean.data_ptr(), var.data_ptr(), n, _C.stream(x.device)))
+                    _C.ptr_array([bn.num_batches_tracked for bn in bns]), mean, var, n)
             return y
         if col_at is not None:                     # statistics back in the reference's column order
             if at_idx is None:
@@ -395,9 +382,7 @@ class PlaneGrid(nn.Module):                   # scene/grids.py:102-201
             b = self.bounds_key()
             p = p.contiguous()
             out = torch.empty_like(p)
-            with torch.cuda.device(p.device):
-                _C.check(_C.lib.scr_box_coords(p.shape[0], p.data_ptr(), _C.host_array(b[:3], _C.f32), _C.host_array(b[3:], _C.f32),
-                                               out.data_ptr(), _C.stream(p.device)))
+            _C.call("scr_box_coords", p.shape[0], p, _C.host_array(b[:3], _C.f32), _C.host_array(b[3:], _C.f32), out)
             return out
         return (p - self.xyz_min) / (self.xyz_max - self.xyz_min) * 2 - 1
 

@@ -52,12 +52,8 @@ def statis_increments(n_offsets, viewspace_point_grad, opacity, update_filter, o
     inc_op = torch.empty(V, dtype=torch.float32, device=dev)
     inc_g = torch.empty(V * k, dtype=torch.float32, device=dev)
     if V:
-        with torch.cuda.device(dev):
-            _C.check(_C.lib.scr_statis_compute(V, k, op.data_ptr(), out_index.data_ptr(),
-                                               upd.data_ptr() if upd.numel() else None,
-                                               grad.data_ptr() if grad.numel() else None,
-                                               grad.shape[1] if grad.dim() == 2 else 2,
-                                               inc_op.data_ptr(), inc_g.data_ptr(), _C.stream()))
+        _C.call("scr_statis_compute", V, k, op, out_index, _C.ptr(upd), _C.ptr(grad), grad.shape[1] if grad.dim() == 2 else 2,
+                 inc_op, inc_g)
     return inc_op, inc_g
 
 
@@ -73,10 +69,7 @@ def statis_apply(opacity_accum, anchor_demon, offset_gradient_accum, offset_deno
     V = int(visible_index.numel())
     if V:
         visible_index = visible_index.contiguous().long()
-        with torch.cuda.device(opacity_accum.device):
-            _C.check(_C.lib.scr_statis_apply(V, int(n_offsets), visible_index.data_ptr(), inc_opacity.data_ptr(),
-                                             inc_grad.data_ptr(), opacity_accum.data_ptr(), anchor_demon.data_ptr(),
-                                             offset_gradient_accum.data_ptr(), offset_denom.data_ptr(), _C.stream()))
+        _C.call("scr_statis_apply", V, int(n_offsets), visible_index, inc_opacity, inc_grad, *accs)
     return accs
 
 

@@ -12,6 +12,7 @@ The sample positions get no gradient: the reference detaches them (scene/gaussia
 import torch
 
 from . import _C
+from .anchor_gather import DeferredDx
 
 # (column of ind holding grid-x -> last plane dim, column holding grid-y) for xy / xz / yz (scene/grids.py:148-150)
 _PAIRS = ((1, 0), (2, 0), (2, 1))
@@ -37,15 +38,13 @@ def _forward_into(out, ind, cols, planes):
             def pairs(p):
                 p = p.contiguous()
                 rp = torch.empty(p.shape[2] - 1, p.shape[3], 2, R, dtype=torch.float32, device=p.device)
-                with torch.cuda.device(p.device):
-                    _C.check(_C.lib.scr_plane_row_pairs(R, p.shape[2], p.shape[3], p.data_ptr(), rp.data_ptr(), _C.stream(p.device)))
+                _C.call("scr_plane_row_pairs", R, p.shape[2], p.shape[3], p, rp)
                 return rp
             xy, xz, yz = pairs(xy), pairs(xz), pairs(yz)
         else:
             xy, xz, yz = (p.contiguous() for p in (xy, xz, yz))
-        _C.check(_C.lib.scr_triplane_forward(V, ind.data_ptr(), ind.stride(0), xy.data_ptr(), xz.data_ptr(), yz.data_ptr(),
-                                             R, X, Y, Z, cl, out.data_ptr(), out.stride(0), cols[t], cols[t + 1], cols[t + 2],
-                                             _C.stream()))
+        _C.call("scr_triplane_forward", V, ind, ind.stride(0), xy, xz, yz, R, X, Y, Z, cl, out, out.stride(0),
+                 cols[t], cols[t + 1], cols[t + 2])
 
 
 def _backward_from(g, ind, cols, shapes):
@@ -56,8 +55,8 @@ def _backward_from(g, ind, cols, shapes):
     R, X, Y, Z = shapes[0][1], shapes[0][2], shapes[0][3], shapes[1][3]
     gp = [torch.empty(s, dtype=torch.float32, device=g.device) for s in shapes]
     scratch = _C.scratch(_C.lib.scr_triplane_backward_scratch_bytes(V, X, Y, Z, R * (n // 3)), g.device)
-    _C.check(_C.lib.scr_triplane_backward(V, ind.data_ptr(), ind.stride(0), R, X, Y, Z, n // 3, g.data_ptr(), g.stride(0),
-                                          _C.host_array(cols), _C.ptr_array(gp), scratch.data_ptr(), _C.stream()))
+    _C.call("scr_triplane_backward", V, ind, ind.stride(0), R, X, Y, Z, n // 3, g, g.stride(0), _C.host_array(cols),
+             _C.ptr_array(gp), scratch)
     return gp
 
 
@@ -75,8 +74,7 @@ class _TriPlaneSample(torch.autograd.Function):
             ind, planes = tensors[k], tensors[k + 1:k + 1 + n]
             if out is None:
                 out = torch.empty(ind.shape[0], width, dtype=torch.float32, device=ind.device)
-            with torch.cuda.device(ind.device):
-                _forward_into(out, ind, cols, planes)
+            _forward_into(out, ind, cols, planes)
             inds.append(ind)
             shapes.append([tuple(p.shape) for p in planes])
             k += 1 + n
@@ -86,7 +84,6 @@ class _TriPlaneSample(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .anchor_gather import DeferredDx
         box = ctx.box
         nl = None
         if box is not None and box.coef is not None:
@@ -111,8 +108,7 @@ class _TriPlaneSample(torch.autograd.Function):
         grads, k = [], 0
         for (n, cols), ind, shapes in zip(ctx.meta, inds, ctx.shapes):
             need = ctx.needs_input_grad[3 + k + 1:3 + k + 1 + n]
-            with torch.cuda.device(ind.device):
-                gp = _backward_from(g, ind, cols, shapes) if any(need) else [None] * n
+            gp = _backward_from(g, ind, cols, shapes) if any(need) else [None] * n
             grads.append(None)
             grads.extend(t if nd else None for t, nd in zip(gp, need))
             k += 1 + n
@@ -138,15 +134,10 @@ def _backward_all(ctx, g, inds, nl=None):
     cR, cX, cY, cZ, ccol = map(_C.host_array, (R, X, Y, Z, col))
     dev = ind.device
     gp = [torch.empty(s, dtype=torch.float32, device=dev) for shapes in ctx.shapes for s in shapes]
-    ptrs = _C.ptr_array(gp)
-    nlargs = (None, None, 0, None, 0) if nl is None else (nl.coef.data_ptr(), nl.dy.data_ptr(), nl.dy.stride(0), nl.x.data_ptr(),
-                                                        nl.x.stride(0))
-    with torch.cuda.device(dev):
-        nbytes = _C.lib.scr_triplane_backward_multi_scratch_bytes(V, ng, cR, cX, cY, cZ)
-        scratch = _C.scratch(max(int(nbytes), 16), dev)
-        rc = _C.lib.scr_triplane_backward_multi(V, ind.data_ptr(), ind.stride(0), ng, cR, cX, cY, cZ, ccol,
-                                                None if g is None else g.data_ptr(), 0 if g is None else g.stride(0), ptrs,
-                                                scratch.data_ptr(), *nlargs, _C.stream())
+    nbytes = _C.lib.scr_triplane_backward_multi_scratch_bytes(V, ng, cR, cX, cY, cZ)
+    scratch = _C.scratch(max(int(nbytes), 16), dev)
+    rc = _C.call("scr_triplane_backward_multi", V, ind, ind.stride(0), ng, cR, cX, cY, cZ, ccol, g, 0 if g is None else g.stride(0),
+                 _C.ptr_array(gp), scratch, *DeferredDx.kernel_args(nl), check=False)
     if rc == 3:
         return None
     _C.check(rc)
@@ -175,7 +166,6 @@ def multi_triplane_sample(grids):
         flat.append(prepped[id(ind)])
         flat.extend(planes)
         width = max(width, max(cols) + R)
-    from .anchor_gather import DeferredDx
     box = DeferredDx(width) if torch.is_grad_enabled() else None
     out = _TriPlaneSample.apply(tuple(meta), width, box, *flat)
     if box is not None:
@@ -215,8 +205,5 @@ class _PlaneSample(torch.autograd.Function):
         g = g.contiguous().float()
         grad_plane = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
         scratch = _C.scratch(_C.lib.scr_plane_sample_scratch_bytes(V, A, B, R), g.device)
-        with torch.cuda.device(g.device):
-            _C.check(_C.lib.scr_plane_sample_backward(V, grid.data_ptr(), 2, 0, 1, R, A, B, 1, g.data_ptr(), g.data_ptr(),
-                                                      g.stride(0), grad_plane.data_ptr(), grad_plane.data_ptr(),
-                                                      scratch.data_ptr(), _C.stream(g.device)))
+        _C.call("scr_plane_sample_backward", V, grid, 2, 0, 1, R, A, B, 1, g, g, g.stride(0), grad_plane, grad_plane, scratch)
         return grad_plane, None

@@ -61,8 +61,7 @@ def tv_add_grad(entries):
         e.plane, e.grad = p.data_ptr(), g.data_ptr()
         e.channels, e.rows, e.cols = p.shape[1], p.shape[2], p.shape[3]
         e.coef = tv_coef(w)
-    with torch.cuda.device(dev):
-        _C.check(_C.lib.scr_tv_add_grad(len(entries), table, _C.stream(dev)))
+    _C.call("scr_tv_add_grad", len(entries), table, device=dev)
 
 
 def feature_planes_tv(feat, w):

@@ -66,14 +66,25 @@ def _binds(base, depth, got):
     return isinstance(got, type) and issubclass(got, ctypes._Pointer) and _binds(base, depth - 1, got._type_)
 
 
+def _header():
+    """(the header without comments, the same without preprocessor lines)."""
+    hdr = open(os.path.join(ROOT, "include", "splatco_raster.h")).read()
+    hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    return hdr, re.sub(r"^\s*#[^\n]*", "", hdr, flags=re.M)
+
+
+def _prototypes(code):
+    """[(return type, name, parameter text)] of the header's functions, in header order."""
+    rest = re.sub(r"typedef\s+struct.*?\}\s*\w+\s*;|\benum\s*\{.*?\}\s*;", "", code, flags=re.S)
+    return re.findall(r"([A-Za-z_][\w\s*]*?)\b(scr_\w+)\s*\(([^()]*)\)\s*;", rest)
+
+
 def test_c_abi_binding_matches_the_header():
     """_C.SIGNATURES, the three structs and the copied constants against include/splatco_raster.h: a prototype, field or
     value changed in the header without the binding fails here, on a CPU, instead of passing garbage arguments on the GPU."""
     from splatco_amd import _C
-    hdr = open(os.path.join(ROOT, "include", "splatco_raster.h")).read()
-    hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    hdr, code = _header()
     defines = {k: int(v) for k, v in re.findall(r"^\s*#\s*define\s+(\w+)\s+(-?\d+)\s*$", hdr, flags=re.M)}
-    code = re.sub(r"^\s*#[^\n]*", "", hdr, flags=re.M)
 
     enums, value = {}, 0
     for body in re.findall(r"\benum\s*\{(.*?)\}\s*;", code, flags=re.S):
@@ -105,8 +116,7 @@ def test_c_abi_binding_matches_the_header():
         for (name, got), (_, base, depth) in zip(cls._fields_, fields):
             assert _binds(base, depth, got), f"{tag}.{name}: {got.__name__} does not bind {base}{'*' * depth}"
 
-    rest = re.sub(r"typedef\s+struct.*?\}\s*\w+\s*;|\benum\s*\{.*?\}\s*;", "", code, flags=re.S)
-    protos = re.findall(r"([A-Za-z_][\w\s*]*?)\b(scr_\w+)\s*\(([^()]*)\)\s*;", rest)
+    protos = _prototypes(code)
     assert [name for _, name, _ in protos] == _C.SYMBOLS, "SIGNATURES must list the header's functions in header order"
     for (ret, name, params), (_, restype, *argtypes) in zip(protos, _C.SIGNATURES):
         params = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
@@ -116,6 +126,80 @@ def test_c_abi_binding_matches_the_header():
             assert _binds(*_c_type(p), got), f"{name} parameter {i} `{p}`: {got.__name__}"
         f = getattr(_C.lib, name)
         assert f.restype is restype and list(f.argtypes) == argtypes, f"{name}: not bound from SIGNATURES"
+
+
+_GUARD_ALLOWED = {}      # {(file under splatco_amd/, enclosing function): reason} for a torch.cuda.device(...) outside _C.py
+
+
+def test_streamed_entry_points_are_launched_through_call():
+    """Every launch in splatco_amd/ goes through _C.call (device guard, operands on one device, the caller's stream, status):
+    its first argument is a literal name of a header function that ends in `void* stream`, no such function is called
+    through `.lib` directly, and no module but _C.py makes a device current by hand."""
+    import ast
+    streamed = {name: "".join(params.split(",")[-1].split()) == "void*stream" for _, name, params in _prototypes(_header()[1])}
+    assert sum(streamed.values()) > 50 and not streamed["scr_flip_filters"] and not streamed["scr_geom_bytes"]
+
+    def dotted(node):
+        parts = []
+        while isinstance(node, ast.Attribute):
+            parts.append(node.attr)
+            node = node.value
+        return ".".join(reversed(parts + [node.id])) if isinstance(node, ast.Name) else ""
+
+    calls, pkg = 0, os.path.join(ROOT, "splatco_amd")
+    for f in sorted(f for f in os.listdir(pkg) if f.endswith(".py") and f != "_C.py"):
+        tree = ast.parse(open(os.path.join(pkg, f)).read())
+        owner = {}
+        for fn in ast.walk(tree):
+            if isinstance(fn, (ast.FunctionDef, ast.AsyncFunctionDef)):
+                for node in ast.walk(fn):
+                    owner[node] = fn.name      # the innermost function wins: ast.walk reaches it last
+        for node in ast.walk(tree):
+            if not isinstance(node, ast.Call):
+                continue
+            name, where = dotted(node.func), f"{f}:{node.lineno}"
+            if name in ("_C.call", "call"):
+                calls += 1
+                first = node.args[0] if node.args else None
+                assert isinstance(first, ast.Constant) and isinstance(first.value, str), f"{where}: the name is not a string literal"
+                assert first.value in streamed, f"{where}: {first.value} is not in the header"
+                assert streamed[first.value], f"{where}: {first.value} does not end in `void* stream`"
+            elif ".lib.scr_" in "." + name:
+                assert not streamed.get(name.rsplit(".", 1)[1], False), f"{where}: {name} takes a stream: launch it through _C.call"
+            elif name.endswith("cuda.device"):
+                assert (f, owner.get(node)) in _GUARD_ALLOWED, f"{where}: torch.cuda.device(...) outside _C.call"
+    assert calls > 40          # (the scan did see the package)
+
+
+class _Recorder:
+    """A stand-in for one entry point: records its arguments and returns `rc`."""
+
+    def __init__(self, rc=0):
+        self.rc, self.args = rc, None
+
+    def __call__(self, *args):
+        self.args = args
+        return self.rc
+
+
+def test_call_checks_name_and_devices_before_anything_is_launched(monkeypatch):
+    from splatco_amd import _C
+    rec = _Recorder()
+    monkeypatch.setattr(_C.lib, "scr_copy_probe", rec)
+    a, b = torch.zeros(4), torch.zeros(4, device="meta")
+    with pytest.raises(ValueError) as e:
+        _C.call("scr_copy_probe", a, 7, b, 16)
+    assert "scr_copy_probe" in str(e.value) and "argument 2" in str(e.value) and "cpu" in str(e.value) and "meta" in str(e.value)
+    with pytest.raises(ValueError) as e:
+        _C.call("scr_copy_probe", a, b, 16, device="meta")
+    assert "scr_copy_probe" in str(e.value) and "argument 0" in str(e.value)
+    with pytest.raises(ValueError) as e:
+        _C.call("scr_copy_probe", None, 3, 2.5)
+    assert "scr_copy_probe" in str(e.value) and "device" in str(e.value)
+    assert rec.args is None
+    with pytest.raises(AttributeError):
+        _C.call("scr_no_such_entry_point", a)
+    assert rec.args is None
 
 
 def test_stage_markers_are_off_by_default_and_load_roctx_on_demand():
