@@ -13,9 +13,11 @@
 //   m  = m + (1 - beta1) (g - m)                      v = beta2 v + ((1 - beta2) g) g          (1 - beta in double, then fp32)
 //   p -= (lr / bias1) * m / (sqrt(v) / sqrt(bias2) + eps)          bias_i = 1 - beta_i^step  (the two scalars formed in double by
 //   the caller, as torch's Python does, and rounded to fp32 once)
-#include "adam.h"
+#include "capi.h"
 
 namespace scr {
+
+constexpr int ADAM_MAX = 24;      // tensors per launch (the table travels in the kernel arguments: 1.4 KB)
 
 typedef float adam_f4 __attribute__((ext_vector_type(4)));
 
@@ -75,36 +77,6 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamArgs a) {
             v[e] = V;
         }
     }
-}
-
-int launch_adam(int n, const scr_adam_tensor* ts, double beta1, double beta2, double eps, hipStream_t st) {
-    for (int t0 = 0; t0 < n; t0 += ADAM_MAX) {
-        AdamArgs a;
-        a.n = min(ADAM_MAX, n - t0);
-        a.beta1 = (float)beta1;
-        a.beta2 = (float)beta2;
-        a.omb1 = (float)(1.0 - beta1);
-        a.omb2 = (float)(1.0 - beta2);
-        a.eps = (float)eps;
-        uint64_t blocks = 0;
-        for (int t = 0; t < a.n; ++t) {
-            const scr_adam_tensor& x = ts[t0 + t];
-            a.first_block[t] = (uint32_t)blocks;
-            blocks += (uint64_t)((x.numel + 1023) / 1024);     // 256 lanes x one float4
-            if (blocks > 0x7fffffffull) return 1;
-            a.p[t] = x.param;
-            a.g[t] = x.grad;
-            a.m[t] = x.exp_avg;
-            a.v[t] = x.exp_avg_sq;
-            a.numel[t] = x.numel;
-            a.step_size[t] = (float)x.step_size;
-            a.bias2_sqrt[t] = (float)x.bias_correction2_sqrt;
-            a.aligned[t] = ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 15u) == 0);
-        }
-        a.first_block[a.n] = (uint32_t)blocks;
-        if (blocks) adam_kernel<<<(unsigned)blocks, 256, 0, st>>>(a);
-    }
-    return 0;
 }
 
 // ---- row-sparse step: the same update on the rows a byte mask marks visible, every other row left alone (bit for bit).
@@ -182,35 +154,90 @@ __global__ void __launch_bounds__(256) adam_rows_kernel(const AdamRowsArgs ra) {
     }
 }
 
-int launch_adam_rows(int n, const scr_adam_tensor* ts, const uint8_t* row_mask, int64_t n_rows, double beta1, double beta2,
-                     double eps, hipStream_t st) {
-    for (int t = 0; t < n; ++t)
-        if (ts[t].numel > 0xffffffffll) return 2;
-    for (int t0 = 0; t0 < n; t0 += ADAM_MAX) {
+// the launch table of tensors ts[0 .. a.n - 1] (a.n set by the caller); false: more than 2^31 workgroups in one launch
+static bool adam_table(AdamArgs& a, const scr_adam_tensor* ts, double beta1, double beta2, double eps) {
+    a.beta1 = (float)beta1;
+    a.beta2 = (float)beta2;
+    a.omb1 = (float)(1.0 - beta1);
+    a.omb2 = (float)(1.0 - beta2);
+    a.eps = (float)eps;
+    uint64_t blocks = 0;
+    for (int t = 0; t < a.n; ++t) {
+        const scr_adam_tensor& x = ts[t];
+        a.first_block[t] = (uint32_t)blocks;
+        blocks += (uint64_t)((x.numel + 1023) / 1024);     // 256 lanes x one float4
+        if (blocks > 0x7fffffffull) return false;
+        a.p[t] = x.param;
+        a.g[t] = x.grad;
+        a.m[t] = x.exp_avg;
+        a.v[t] = x.exp_avg_sq;
+        a.numel[t] = x.numel;
+        a.step_size[t] = (float)x.step_size;
+        a.bias2_sqrt[t] = (float)x.bias_correction2_sqrt;
+        a.aligned[t] = ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 15u) == 0);
+    }
+    a.first_block[a.n] = (uint32_t)blocks;
+    return true;
+}
+
+}  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+int scr_adam_step(int32_t n_tensors, const scr_adam_tensor* tensors, double beta1, double beta2, double eps, void* stream) {
+    SCR_MARK_FN;
+    if (n_tensors < 0) return fail("scr_adam_step: n_tensors < 0");
+    if (n_tensors == 0) return 0;
+    if (!tensors) return fail("scr_adam_step: tensors is NULL");
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0)) return fail("scr_adam_step: bad beta / eps");
+    for (int t = 0; t < n_tensors; ++t) {
+        const scr_adam_tensor& x = tensors[t];
+        if (x.numel < 0 || (x.numel > 0 && (!x.param || !x.grad || !x.exp_avg || !x.exp_avg_sq))) return fail("scr_adam_step: NULL tensor");
+        if (!(x.step_size >= 0.0) || !(x.step_size < 1e30) || !(x.bias_correction2_sqrt > 0.0))
+            return fail("scr_adam_step: step_size must be finite and >= 0, bias_correction2_sqrt > 0 (step >= 1)");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MAX) {
+        AdamArgs a;
+        a.n = min(ADAM_MAX, n_tensors - t0);
+        if (!adam_table(a, tensors + t0, beta1, beta2, eps)) return fail("scr_adam_step: more than 2^31 workgroups in one launch");
+        if (a.first_block[a.n]) adam_kernel<<<a.first_block[a.n], 256, 0, st>>>(a);
+    }
+    CHECK_LAUNCH("adam_kernel", 0, st);
+    return 0;
+}
+
+// the same update on the rows of [n_rows, numel / n_rows] tensors that row_mask marks (nonzero), nothing else touched
+int scr_adam_step_rows(int32_t n_tensors, const scr_adam_tensor* tensors, const uint8_t* row_mask, int64_t n_rows,
+                       double beta1, double beta2, double eps, void* stream) {
+    SCR_MARK_FN;
+    if (n_tensors < 0) return fail("scr_adam_step_rows: n_tensors < 0");
+    if (n_rows < 0) return fail("scr_adam_step_rows: n_rows < 0");
+    if (n_tensors > 0 && !tensors) return fail("scr_adam_step_rows: tensors is NULL");
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0)) return fail("scr_adam_step_rows: bad beta / eps");
+    if (n_rows > 0 && !row_mask) return fail("scr_adam_step_rows: row_mask is NULL");
+    int64_t total = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+        const scr_adam_tensor& x = tensors[t];
+        if (x.numel < 0 || (x.numel > 0 && (!x.param || !x.grad || !x.exp_avg || !x.exp_avg_sq))) return fail("scr_adam_step_rows: NULL tensor");
+        if (!(x.step_size >= 0.0) || !(x.step_size < 1e30) || !(x.bias_correction2_sqrt > 0.0))
+            return fail("scr_adam_step_rows: step_size must be finite and >= 0, bias_correction2_sqrt > 0 (step >= 1)");
+        if (n_rows == 0 ? x.numel != 0 : x.numel % n_rows != 0) return fail("scr_adam_step_rows: numel is not a multiple of n_rows");
+        if (x.numel > 0xffffffffll) return fail("scr_adam_step_rows: numel of 2^32 or more (32-bit element index)");
+        total += x.numel;
+    }
+    if (total == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    for (int t0 = 0; t0 < n_tensors; t0 += ADAM_MAX) {
         AdamRowsArgs ra;
         AdamArgs& a = ra.a;
         ra.mask = row_mask;
-        a.n = min(ADAM_MAX, n - t0);
-        a.beta1 = (float)beta1;
-        a.beta2 = (float)beta2;
-        a.omb1 = (float)(1.0 - beta1);
-        a.omb2 = (float)(1.0 - beta2);
-        a.eps = (float)eps;
-        uint64_t blocks = 0;
+        a.n = min(ADAM_MAX, n_tensors - t0);
+        if (!adam_table(a, tensors + t0, beta1, beta2, eps)) return fail("scr_adam_step_rows: more than 2^31 workgroups in one launch");
         for (int t = 0; t < a.n; ++t) {
-            const scr_adam_tensor& x = ts[t0 + t];
-            a.first_block[t] = (uint32_t)blocks;
-            blocks += (uint64_t)((x.numel + 1023) / 1024);     // 256 lanes x one float4
-            if (blocks > 0x7fffffffull) return 1;
-            a.p[t] = x.param;
-            a.g[t] = x.grad;
-            a.m[t] = x.exp_avg;
-            a.v[t] = x.exp_avg_sq;
-            a.numel[t] = x.numel;
-            a.step_size[t] = (float)x.step_size;
-            a.bias2_sqrt[t] = (float)x.bias_correction2_sqrt;
-            a.aligned[t] = ((((uintptr_t)x.param | (uintptr_t)x.grad | (uintptr_t)x.exp_avg | (uintptr_t)x.exp_avg_sq) & 15u) == 0);
-            const uint32_t w = x.numel > 0 ? (uint32_t)(x.numel / n_rows) : 1u;      // an empty tensor launches nothing
+            const uint32_t w = a.numel[t] > 0 ? (uint32_t)(a.numel[t] / n_rows) : 1u;      // an empty tensor launches nothing
             uint32_t L = 0;
             while (L < 32 && (1ull << L) < w) ++L;
             ra.width[t] = w;
@@ -218,10 +245,10 @@ int launch_adam_rows(int n, const scr_adam_tensor* ts, const uint8_t* row_mask, 
             ra.sh1[t] = (uint8_t)(L < 1 ? L : 1);
             ra.sh2[t] = (uint8_t)(L > 1 ? L - 1 : 0);
         }
-        a.first_block[a.n] = (uint32_t)blocks;
-        if (blocks) adam_rows_kernel<<<(unsigned)blocks, 256, 0, st>>>(ra);
+        if (a.first_block[a.n]) adam_rows_kernel<<<a.first_block[a.n], 256, 0, st>>>(ra);
     }
+    CHECK_LAUNCH("adam_rows_kernel", 0, st);
     return 0;
 }
 
-}  // namespace scr
+}  // extern "C"

@@ -18,7 +18,7 @@
 //             index is ascending), so those rows are loaded as contiguous chunks into LDS, summed (d g_fea + d part),
 //             d exp applied, and the four parameter-gradient chunks are written whole -- zeros for invisible anchors:
 //             every element exactly once, no atomics, no memset.
-#include "common.h"
+#include "capi.h"
 
 namespace scr {
 
@@ -72,11 +72,11 @@ constexpr int AG_MAX_WGS = SCR_AG_MAX_WGS;
 #define SCR_AG_TPW 8
 #endif
 constexpr int AG_TPW = SCR_AG_TPW;      // consecutive 64-row tiles per workgroup: one row of statistics (and its reduction) per workgroup
-int anchor_gather_stat_rows(int64_t V) {      // rows the consumer reads
+static int anchor_gather_stat_rows(int64_t V) {      // rows the consumer reads
     const int64_t tiles = (V + AG_ROWS * AG_TPW - 1) / (AG_ROWS * AG_TPW);
     return (int)(tiles < AG_MAX_WGS ? (tiles > 0 ? tiles : 1) : AG_MAX_WGS);
 }
-int64_t anchor_gather_stat_buffer_rows(int64_t V) {      // rows of the buffer: the consumer's, then one per workgroup when a second kernel reduces them
+static int64_t anchor_gather_stat_buffer_rows(int64_t V) {      // rows of the buffer: the consumer's, then one per workgroup when a second kernel reduces them
     const int64_t tiles = (V + AG_ROWS * AG_TPW - 1) / (AG_ROWS * AG_TPW);
     return tiles <= AG_MAX_WGS ? (tiles > 0 ? tiles : 1) : AG_MAX_WGS + tiles;
 }
@@ -415,34 +415,69 @@ anchor_gather_backward_kernel(int64_t N, int64_t V, const int64_t* __restrict__ 
   }
 }
 
-void launch_anchor_gather(int64_t V, const int64_t* idx, const float* p_feat, const float* p_anchor, const float* p_offset,
-                          const float* p_scaling, float* feat, float* anchor, float* offsets, float* grid_scaling,
-                          float* g_fea, int ldg, float* stats, hipStream_t st) {
-    if (V <= 0) return;
-    const int64_t tiles = (V + AG_ROWS * AG_TPW - 1) / (AG_ROWS * AG_TPW);      // workgroups
-    // per-workgroup statistics rows: the consumer's rows themselves up to AG_MAX_WGS workgroups, behind them otherwise
-    float* tile_stats = stats ? stats + (tiles <= AG_MAX_WGS ? 0 : (size_t)AG_MAX_WGS * 2 * NL_DP) : nullptr;
-    anchor_gather_kernel<<<(unsigned)tiles, AG_THREADS, 0, st>>>(
-        V, idx, p_feat, p_anchor, p_offset, p_scaling, feat, anchor, offsets, grid_scaling, g_fea, ldg, tile_stats);
-    if (stats && tiles > AG_MAX_WGS) anchor_gather_stat_reduce_kernel<<<AG_MAX_WGS, 2 * NL_DP, 0, st>>>(tiles, stats);
-}
-
 constexpr int AG_DX_BPW = 1;      // blocks of 64 anchors per workgroup of the dx-forming instantiation
 
-void launch_anchor_gather_backward(int64_t N, int64_t V, const int64_t* inv, const float* grid_scaling, const float* d_feat,
-                                   const float* d_anchor, const float* d_offsets, const float* d_grid_scaling,
-                                   const float* d_g_fea, int ldg, float* g_feat, float* g_anchor, float* g_offset,
-                                   float* g_scaling, int accumulate, const float* nl_coef, const float* nl_dy, int nl_lddy,
-                                   const float* nl_x, int nl_ldx, hipStream_t st) {
-    if (N <= 0) return;
+}  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+int32_t scr_anchor_gather_stat_rows(int64_t V) { return anchor_gather_stat_rows(V > 0 ? V : 1); }
+int64_t scr_anchor_gather_stat_buffer_rows(int64_t V) { return anchor_gather_stat_buffer_rows(V > 0 ? V : 1); }
+
+int scr_anchor_gather(int64_t V, const int64_t* visible_index, const float* anchor_feat, const float* anchor,
+                      const float* offset, const float* scaling, float* feat_out, float* anchor_out, float* offsets_out,
+                      float* grid_scaling_out, float* g_fea_out, int32_t g_fea_ld, float* col_stats_out, void* stream) {
+    SCR_MARK_FN;
+    if (V < 0) return fail("V < 0");
+    if (g_fea_ld != 71 && g_fea_ld != 72) return fail("g_fea row stride must be 71 (packed) or 72 (16-byte aligned rows)");
+    if (V == 0) return 0;
+    if (!visible_index || !anchor_feat || !anchor || !offset || !scaling || !anchor_out || !grid_scaling_out || !g_fea_out)
+        return fail("NULL argument");
+    if ((!feat_out || !offsets_out) && g_fea_ld != 72)
+        return fail("feat_out / offsets_out may be NULL (their consumers read the columns of g_fea) only with 16-byte aligned g_fea rows (ld 72)");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t tiles = (V + AG_ROWS * AG_TPW - 1) / (AG_ROWS * AG_TPW);      // workgroups
+    // per-workgroup statistics rows: the consumer's rows themselves up to AG_MAX_WGS workgroups, behind them otherwise
+    float* tile_stats = col_stats_out ? col_stats_out + (tiles <= AG_MAX_WGS ? 0 : (size_t)AG_MAX_WGS * 2 * NL_DP) : nullptr;
+    anchor_gather_kernel<<<(unsigned)tiles, AG_THREADS, 0, st>>>(
+        V, visible_index, anchor_feat, anchor, offset, scaling, feat_out, anchor_out, offsets_out, grid_scaling_out, g_fea_out,
+        g_fea_ld, tile_stats);
+    if (col_stats_out && tiles > AG_MAX_WGS) anchor_gather_stat_reduce_kernel<<<AG_MAX_WGS, 2 * NL_DP, 0, st>>>(tiles, col_stats_out);
+    CHECK_LAUNCH("anchor_gather_kernel", 0, st);
+    return 0;
+}
+
+int scr_anchor_gather_backward(int64_t N, int64_t V, const int64_t* inverse_index, const float* grid_scaling, const float* d_feat,
+                               const float* d_anchor, const float* d_offsets, const float* d_grid_scaling,
+                               const float* d_g_fea, int32_t g_fea_ld, float* g_anchor_feat, float* g_anchor,
+                               float* g_offset, float* g_scaling, int32_t accumulate, const float* nl_coef, const float* nl_dy,
+                               int32_t nl_lddy, const float* nl_x, int32_t nl_ldx, void* stream) {
+    SCR_MARK_FN;
+    if (N < 0 || V < 0) return fail("bad sizes");      // V may exceed N: N can be a range of the anchors (see the header)
+    if (g_fea_ld != 71 && g_fea_ld != 72) return fail("g_fea row stride must be 71 (packed) or 72 (16-byte aligned rows)");
+    if (N == 0) return 0;
+    if (!inverse_index || !g_anchor_feat || !g_anchor || !g_offset || !g_scaling) return fail("NULL argument");
+    if (d_grid_scaling || d_g_fea || nl_coef) { if (!grid_scaling) return fail("grid_scaling is needed for d exp"); }
+    if (nl_coef) {
+        if (!nl_dy || !nl_x || nl_lddy < 32 || nl_ldx < 71) return fail("fused dx: dy [V,32] and x = g_fea [V,71] are needed");
+        if (nl_lddy % 4 != 0 || ((uintptr_t)nl_dy & 15) != 0 || ((uintptr_t)nl_coef & 15) != 0)
+            return fail("fused dx: dy and the coefficients must be 16-byte aligned, dy's row stride a multiple of 4 floats");
+    }
+    hipStream_t st = (hipStream_t)stream;
     const int64_t blocks = (N + AG_ROWS - 1) / AG_ROWS;
     const AgDx nl{nl_coef, nl_dy, nl_x, nl_lddy, nl_ldx};
     if (nl_coef)
         anchor_gather_backward_kernel<true, AG_DX_BPW><<<(unsigned)((blocks + AG_DX_BPW - 1) / AG_DX_BPW), AG_THREADS, 0, st>>>(
-            N, V, inv, grid_scaling, d_feat, d_anchor, d_offsets, d_grid_scaling, d_g_fea, ldg, g_feat, g_anchor, g_offset, g_scaling, accumulate, nl);
+            N, V, inverse_index, grid_scaling, d_feat, d_anchor, d_offsets, d_grid_scaling, d_g_fea, g_fea_ld, g_anchor_feat, g_anchor,
+            g_offset, g_scaling, accumulate, nl);
     else
         anchor_gather_backward_kernel<false, 1><<<(unsigned)blocks, AG_THREADS, 0, st>>>(
-            N, V, inv, grid_scaling, d_feat, d_anchor, d_offsets, d_grid_scaling, d_g_fea, ldg, g_feat, g_anchor, g_offset, g_scaling, accumulate, nl);
+            N, V, inverse_index, grid_scaling, d_feat, d_anchor, d_offsets, d_grid_scaling, d_g_fea, g_fea_ld, g_anchor_feat, g_anchor,
+            g_offset, g_scaling, accumulate, nl);
+    CHECK_LAUNCH("anchor_gather_backward_kernel", 0, st);
+    return 0;
 }
 
-}  // namespace scr
+}  // extern "C"

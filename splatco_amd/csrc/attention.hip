@@ -14,6 +14,7 @@
 // framework's cats are gone too.  Backward (tpa_bwd_*): dL/dsa -> through the sigmoid -> transposed 7x7 -> mean / max
 // routing -> dL/dy -> dL/dx and the per-channel sums dL/dca; the weight gradient of the 7x7 is a per-tile correlation.
 // Every reduction is two-level with a fixed order (per-block partials, summed in block order): bit-reproducible.
+#include "capi.h"
 #include "wg.h"
 
 namespace scr {
@@ -272,10 +273,22 @@ tpa_bwd_stats_kernel(int R, int64_t HW, const float* __restrict__ davg, const fl
         d[i] += add + (i == a ? m : 0.0f);
 }
 
-// ---------------------------------------------------------------- launchers
+// ---------------------------------------------------------------- entry points
 static dim3 tpa_tiles(int H, int W) { return dim3((W + TPA_TW - 1) / TPA_TW, (H + TPA_TH - 1) / TPA_TH); }
 
-size_t tpa_scratch_bytes(int R, int H, int W) {
+static int tpa_bad(int32_t R, int32_t H, int32_t W) {
+    if (R <= 0 || 3 * R > 24) return fail("plane attention: 3 R stacked channels must be 3..24");
+    if (H <= 0 || W <= 0 || (int64_t)H * W >= (1ll << 31)) return fail("plane attention: bad plane size");
+    return 0;
+}
+
+}  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+size_t scr_tpa_scratch_bytes(int32_t R, int32_t H, int32_t W) {
     const dim3 t = tpa_tiles(H, W);
     const size_t nblk = (size_t)t.x * t.y;
     const size_t stats = (size_t)3 * R * TPA_STAT_BLOCKS * 12;
@@ -283,29 +296,48 @@ size_t tpa_scratch_bytes(int R, int H, int W) {
     return align_up(stats > bwd ? stats : bwd);
 }
 
-void launch_tpa_stats(int R, int64_t HW, const float* p0, const float* p1, const float* p2, float* avg, float* mx,
-                      int* arg, void* scratch, hipStream_t st) {
+int scr_tpa_stats(int32_t R, int32_t H, int32_t W, const float* p0, const float* p1, const float* p2, float* avg,
+                  float* mx, int32_t* arg, void* scratch, void* stream) {
+    SCR_MARK_FN;
+    if (tpa_bad(R, H, W)) return 1;
+    if (!p0 || !p1 || !p2 || !avg || !mx || !arg || !scratch) return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t HW = (int64_t)H * W;
     const int C = 3 * R;
     float* psum = (float*)scratch;
     float* pmax = psum + (size_t)C * TPA_STAT_BLOCKS;
     int* parg = (int*)(pmax + (size_t)C * TPA_STAT_BLOCKS);
     const TpaPlanes x{{p0, p1, p2}};
-    tpa_stats_partial_kernel<<<dim3(TPA_STAT_BLOCKS, C), 256, 0, st>>>(R, HW, x, psum, pmax, parg);
-    tpa_stats_finish_kernel<<<1, 64, 0, st>>>(C, TPA_STAT_BLOCKS, HW, psum, pmax, parg, avg, mx, arg);
+    { ProfScope ps_(SCR_PROF_PLANE_ATTENTION, st);
+      tpa_stats_partial_kernel<<<dim3(TPA_STAT_BLOCKS, C), 256, 0, st>>>(R, HW, x, psum, pmax, parg);
+      tpa_stats_finish_kernel<<<1, 64, 0, st>>>(C, TPA_STAT_BLOCKS, HW, psum, pmax, parg, avg, mx, arg); }
+    CHECK_LAUNCH("tpa_stats_kernels", 0, st);
+    return 0;
 }
 
-void launch_tpa_forward(int R, int H, int W, const float* p0, const float* p1, const float* p2, const float* ca,
-                        const float* w, float* s, uint8_t* am, float* sa, float* o0, float* o1, float* o2, hipStream_t st) {
+int scr_tpa_forward(int32_t R, int32_t H, int32_t W, const float* p0, const float* p1, const float* p2, const float* ca,
+                    const float* w, float* s, uint8_t* am, float* sa, float* pair0, float* pair1, float* pair2, void* stream) {
+    SCR_MARK_FN;
+    if (tpa_bad(R, H, W)) return 1;
+    if (!p0 || !p1 || !p2 || !ca || !w || !s || !am || !sa || !pair0 || !pair1 || !pair2) return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
     const int64_t HW = (int64_t)H * W;
     const TpaPlanes x{{p0, p1, p2}};
-    tpa_reduce_kernel<<<(unsigned)((HW + 255) / 256), 256, 0, st>>>(R, HW, x, ca, s, am);
-    tpa_apply_kernel<<<tpa_tiles(H, W), 256, 0, st>>>(R, H, W, x, ca, w, s, sa, TpaOut{{o0, o1, o2}});
+    { ProfScope ps_(SCR_PROF_PLANE_ATTENTION, st);
+      tpa_reduce_kernel<<<(unsigned)((HW + 255) / 256), 256, 0, st>>>(R, HW, x, ca, s, am);
+      tpa_apply_kernel<<<tpa_tiles(H, W), 256, 0, st>>>(R, H, W, x, ca, w, s, sa, TpaOut{{pair0, pair1, pair2}}); }
+    CHECK_LAUNCH("tpa_apply_kernel", 0, st);
+    return 0;
 }
 
-void launch_tpa_backward(int R, int H, int W, const float* p0, const float* p1, const float* p2, const float* ca,
-                         const float* w, const float* s, const uint8_t* am, const float* sa, const float* g0,
-                         const float* g1, const float* g2, float* d0, float* d1, float* d2, float* dca, float* dw,
-                         void* scratch, hipStream_t st) {
+int scr_tpa_backward(int32_t R, int32_t H, int32_t W, const float* p0, const float* p1, const float* p2, const float* ca,
+                     const float* w, const float* s, const uint8_t* am, const float* sa, const float* g0, const float* g1,
+                     const float* g2, float* d0, float* d1, float* d2, float* dca, float* dw, void* scratch, void* stream) {
+    SCR_MARK_FN;
+    if (tpa_bad(R, H, W)) return 1;
+    if (!p0 || !p1 || !p2 || !ca || !w || !s || !am || !sa || !g0 || !g1 || !g2 || !d0 || !d1 || !d2 || !dca || !dw || !scratch)
+        return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
     const int64_t HW = (int64_t)H * W;
     const int C = 3 * R, NT = 2 * TPA_K * TPA_K;
     const dim3 t = tpa_tiles(H, W);
@@ -314,21 +346,31 @@ void launch_tpa_backward(int R, int H, int W, const float* p0, const float* p1, 
     float* dca_part = dpre + HW;
     float* dw_part = dca_part + (size_t)nblk * C;
     const TpaPlanes x{{p0, p1, p2}}, g{{g0, g1, g2}};
-    tpa_bwd_pre_kernel<<<(unsigned)((HW + 255) / 256), 256, 0, st>>>(R, HW, x, ca, sa, g, dpre);
     const TpaOut dx{{d0, d1, d2}};
-    switch (R) {   // the per-channel sums live in registers: the channel count is a template parameter
+    { ProfScope ps_(SCR_PROF_PLANE_ATTENTION, st);
+      tpa_bwd_pre_kernel<<<(unsigned)((HW + 255) / 256), 256, 0, st>>>(R, HW, x, ca, sa, g, dpre);
+      switch (R) {   // the per-channel sums live in registers: the channel count is a template parameter
 #define SCR_TPA_CASE(r) case r: tpa_bwd_apply_kernel<r><<<t, 256, 0, st>>>(H, W, x, ca, w, sa, am, dpre, g, dx, dca_part); break;
-        SCR_TPA_CASE(1) SCR_TPA_CASE(2) SCR_TPA_CASE(3) SCR_TPA_CASE(4) SCR_TPA_CASE(5) SCR_TPA_CASE(6) SCR_TPA_CASE(7) SCR_TPA_CASE(8)
+          SCR_TPA_CASE(1) SCR_TPA_CASE(2) SCR_TPA_CASE(3) SCR_TPA_CASE(4) SCR_TPA_CASE(5) SCR_TPA_CASE(6) SCR_TPA_CASE(7) SCR_TPA_CASE(8)
 #undef SCR_TPA_CASE
-    }
-    tpa_bwd_weight_kernel<<<t, 256, 0, st>>>(H, W, s, dpre, dw_part);
-    tpa_sum_partials_kernel<<<C, 256, 0, st>>>(nblk, C, dca_part, dca);
-    tpa_sum_partials_kernel<<<NT, 256, 0, st>>>(nblk, NT, dw_part, dw);
+      }
+      tpa_bwd_weight_kernel<<<t, 256, 0, st>>>(H, W, s, dpre, dw_part);
+      tpa_sum_partials_kernel<<<C, 256, 0, st>>>(nblk, C, dca_part, dca);
+      tpa_sum_partials_kernel<<<NT, 256, 0, st>>>(nblk, NT, dw_part, dw); }
+    CHECK_LAUNCH("tpa_bwd_kernels", 0, st);
+    return 0;
 }
 
-void launch_tpa_backward_stats(int R, int64_t HW, const float* davg, const float* dmx, const int* arg, float* d0,
-                               float* d1, float* d2, hipStream_t st) {
-    tpa_bwd_stats_kernel<<<dim3(64, 3 * R), 256, 0, st>>>(R, HW, davg, dmx, arg, TpaOut{{d0, d1, d2}});
+int scr_tpa_backward_stats(int32_t R, int32_t H, int32_t W, const float* davg, const float* dmax, const int32_t* arg,
+                           float* d0, float* d1, float* d2, void* stream) {
+    SCR_MARK_FN;
+    if (tpa_bad(R, H, W)) return 1;
+    if (!davg || !dmax || !arg || !d0 || !d1 || !d2) return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    { ProfScope ps_(SCR_PROF_PLANE_ATTENTION, st);
+      tpa_bwd_stats_kernel<<<dim3(64, 3 * R), 256, 0, st>>>(R, (int64_t)H * W, davg, dmax, arg, TpaOut{{d0, d1, d2}}); }
+    CHECK_LAUNCH("tpa_bwd_stats_kernel", 0, st);
+    return 0;
 }
 
-}  // namespace scr
+}  // extern "C"

@@ -347,17 +347,8 @@ inline void ZeroList::add(void* ptr, size_t bytes, hipStream_t st) {
 // attribute shows up as the error of the launch that follows.  (capi.hip)
 void allow_dynamic_lds(const void* kernel, size_t bytes);
 
-// launchers (defined in the .hip files)
-void launch_box_coords(int64_t V, const float* xyz, const float* lo, const float* hi, float* out, hipStream_t st);
-int launch_nl_fold(int L, int d, const int* dd, const int* col, const unsigned char* col_at, const float* const* W,
-                   const float* const* b, const float* const* gamma, const float* const* beta, float* G, float* c,
-                   hipStream_t st);
-int launch_nl_fold_backward(int L, int d, const int* dd, const int* col, const unsigned char* col_at, const float* const* W,
-                            const float* const* gamma, const float* const* beta, const float* dG, const float* dc,
-                            float* const* dW, float* const* db, float* const* dgamma, float* const* dbeta, hipStream_t st);
-int launch_nl_running_stats(int L, int d, const int* dd, const int* col, const unsigned char* col_at, const float* momentum,
-                            float* const* run_mean, float* const* run_var, long long* const* batches, const float* mean,
-                            const float* var, int64_t n, hipStream_t st);
+// launchers of the rasterizer pipeline (preprocess.hip, binning.hip, blend.hip), orchestrated by capi.hip.  Every other
+// operator family keeps its launches next to its entry points, in its own .hip file.
 void launch_filter(int64_t P, const float* means3D, const float* scales, const float* rotations,
                    const float* cov3D, const KSettings& ks, int32_t* radii, hipStream_t st);
 void launch_mark_visible(int64_t P, const float* means3D, const float* view, uint8_t* out, hipStream_t st);
@@ -389,132 +380,6 @@ size_t camera_partials_bytes(int64_t P);
 void launch_camera_grad_finish(int64_t P, const float* cam_partials, float* dL_dview, float* dL_dproj, float* dL_dcampos,
                                hipStream_t st);
 
-// the count passes of the three compactions (compact.h; the scratch view is compact_scratch()'s)
-struct CompactScratch;
-void launch_expand_count(int64_t n, const float* neural_opacity, const CompactScratch& s, unsigned long long* mailbox,
-                         unsigned long long seq, hipStream_t st);
-void launch_mask_count(int64_t n, const uint8_t* mask, const CompactScratch& s, unsigned long long* mailbox,
-                       unsigned long long seq, hipStream_t st);
-void launch_voxel_unique_count(int64_t n, const int64_t* keys, const CompactScratch& s, unsigned long long* mailbox,
-                               unsigned long long seq, hipStream_t st);
-void launch_mask_index(int64_t n, const uint8_t* mask, const uint32_t* wg_offset, int64_t* index, int64_t* inverse,
-                       hipStream_t st);
-void launch_expand_run(int64_t n, int k, const float* neural_opacity, const float* color, const float* scale_rot,
-                       const float* offsets, int ldo, const float* grid_scaling, const float* anchor,
-                       const uint32_t* wg_offset, int32_t* out_index, uint8_t* mask_out, float* xyz,
-                       float* color_out, float* opacity, float* scaling, float* rot, hipStream_t st);
-void launch_expand_backward(int64_t V, int k, const float* scale_rot, const float* offsets, int ldo,
-                            const float* grid_scaling, const int32_t* out_index, const float* g_xyz,
-                            const float* g_color, const float* g_opacity, const float* g_scaling,
-                            const float* g_rot, float* d_neural_opacity, float* d_color, float* d_scale_rot,
-                            float* d_offsets, float* d_grid_scaling, float* d_anchor, const float* g_reg, int64_t P,
-                            hipStream_t st);
-
-void launch_statis_compute(int64_t V, int k, const float* neural_opacity, const int32_t* out_index,
-                           const uint8_t* update_filter, const float* grad, int gstride, float* inc_opacity,
-                           float* inc_grad, hipStream_t st);
-void launch_statis_apply(int64_t V, int k, const int64_t* visible_index, const float* inc_opacity, const float* inc_grad,
-                         float* opacity_accum, float* anchor_demon, float* offset_gradient_accum, float* offset_denom,
-                         hipStream_t st);
-
 constexpr int NL_DP = 80;               // padded width of the BatchNorm-Linear's coefficient rows AND of a row of column statistics
-int anchor_gather_stat_rows(int64_t V);  // rows of column statistics the gather hands to the BatchNorm-Linear
-int64_t anchor_gather_stat_buffer_rows(int64_t V);      // rows of the buffer it needs for them (per-tile rows behind the result)
-void launch_anchor_gather(int64_t V, const int64_t* idx, const float* p_feat, const float* p_anchor, const float* p_offset,
-                          const float* p_scaling, float* feat, float* anchor, float* offsets, float* grid_scaling,
-                          float* g_fea, int ldg, float* stats, hipStream_t st);
-void launch_anchor_gather_backward(int64_t N, int64_t V, const int64_t* inv, const float* grid_scaling, const float* d_feat,
-                                   const float* d_anchor, const float* d_offsets, const float* d_grid_scaling,
-                                   const float* d_g_fea, int ldg, float* g_feat, float* g_anchor, float* g_offset,
-                                   float* g_scaling, int accumulate, const float* nl_coef, const float* nl_dy, int nl_lddy,
-                                   const float* nl_x, int nl_ldx, hipStream_t st);
-void launch_knn(int64_t N, int k, const float* grid8, const float* sorted_pts, const int64_t* sorted_id,
-                const int32_t* cell_start, int64_t* out_idx, hipStream_t st);
-void launch_knn_curvature(int64_t N, int k, const float* pts, const int64_t* idx, float* curvature, hipStream_t st);
-// scene_init.hip: voxelisation and the fused 3-NN mean squared distance
-size_t points_bounds_nwg(int64_t N);
-void launch_points_bounds(int64_t N, const float* pts, float* partial, float* out, hipStream_t st);
-void launch_voxel_keys(int64_t N, const float* pts, float v, const int32_t* lo, int packed, int64_t* out, hipStream_t st);
-void launch_voxel_unique_write(int64_t n, const int64_t* keys, const uint32_t* wg_offset, float v, const int32_t* lo,
-                               float* out, hipStream_t st);
-void launch_knn_cell_keys(int64_t N, const float* grid8, const float* pts, int64_t* keys, hipStream_t st);
-void launch_knn3_dist2(int64_t N, const float* grid8, const float* sorted_pts, const int64_t* sorted_id,
-                       const int32_t* cell_start, float* out, hipStream_t st);
-size_t norm_linear_scratch_bytes(int64_t V);
-int launch_norm_linear_forward(int64_t V, int d, const float* x, int ldx, const float* G, const float* c, float eps, float* y,
-                               float* mean, float* var, float* inv, void* scratch, const float* stats, int stat_rows,
-                               hipStream_t st);
-int launch_norm_linear_backward(int64_t V, int d, const float* x, int ldx, const float* dy, int lddy, const float* G,
-                                const float* mean, const float* inv, float* dx, int lddx, float* dG, float* dc, void* scratch,
-                                float* coef_out, hipStream_t st);
-size_t mlp_heads_hidden_bytes(int64_t V);
-size_t mlp_heads_partial_bytes(int64_t V);
-void launch_mlp_heads_forward(int64_t V, const float* feat, int ldf, const float* anchor, const float* campos, const float* geo_a, const float* geo_b,
-                              const float* w1, const float* b1, const float* w2o, const float* b2o, const float* w2c,
-                              const float* b2c, const float* w2v, const float* b2v, void* hidden_save, float* out_o,
-                              float* out_c, float* out_v, hipStream_t st);
-void launch_mlp_heads_backward(int64_t V, const float* feat, int ldf, const float* anchor, const float* campos, const float* geo_a, const float* geo_b,
-                               const float* w1, const float* w2o, const float* w2c, const float* w2v,
-                               const void* hidden_save, const float* out_o, const float* out_c, const float* g_o,
-                               const float* g_c, const float* g_v, void* partial, float* d_feat, float* d_anchor,
-                               float* d_geo_a, float* d_geo_b, float* d_w1, float* d_b1, float* d_w2o, float* d_b2o, float* d_w2c,
-                               float* d_b2c, float* d_w2v, float* d_b2v, hipStream_t st);
-
-// plane attention of the level-0 grid (attention.hip)
-size_t tpa_scratch_bytes(int R, int H, int W);
-void launch_tpa_stats(int R, int64_t HW, const float* p0, const float* p1, const float* p2, float* avg, float* mx,
-                      int* arg, void* scratch, hipStream_t st);
-void launch_tpa_forward(int R, int H, int W, const float* p0, const float* p1, const float* p2, const float* ca,
-                        const float* w, float* s, uint8_t* am, float* sa, float* o0, float* o1, float* o2, hipStream_t st);
-void launch_tpa_backward(int R, int H, int W, const float* p0, const float* p1, const float* p2, const float* ca,
-                         const float* w, const float* s, const uint8_t* am, const float* sa, const float* g0,
-                         const float* g1, const float* g2, float* d0, float* d1, float* d2, float* dca, float* dw,
-                         void* scratch, hipStream_t st);
-void launch_tpa_backward_stats(int R, int64_t HW, const float* davg, const float* dmx, const int* arg, float* d0,
-                               float* d1, float* d2, hipStream_t st);
-
-size_t l1_ssim_scratch_bytes(int C, int H, int W, int with_grad);
-int flip_radii(double ppd, int* rc, int* rf);
-int flip_filters(double ppd, double* w, int* radii, double* scalars);
-size_t flip_scratch_bytes(int N, int H, int W);
-int launch_flip_forward(int N, int H, int W, const float* test, const float* ref, double ppd, int quantize,
-                        void* scratch, float* mean_out, float* mse_out, float* map_out, hipStream_t st);
-size_t scaling_reg_scratch_bytes(int64_t P);
-size_t pair_l1_scratch_bytes(int64_t n);
-void launch_pair_l1_forward(int64_t n, const float* g1, const float* g2, const float* r1, const float* r2, void* scratch, float* out,
-                            hipStream_t st);
-void launch_pair_l1_backward(int64_t n, const float* g1, const float* g2, const float* r1, const float* r2, const float* g, float* d1,
-                             float* d2, hipStream_t st);
-size_t depth_loss_scratch_bytes(int H, int W);
-void launch_depth_loss_forward(int H, int W, const float* depth, const float* alpha, const float* target, const void* mask,
-                               int mask_kind, int mode, int align, float min_alpha, void* scratch, float* out4, hipStream_t st);
-void launch_depth_loss_backward(int H, int W, const float* depth, const float* alpha, const float* target, const void* mask,
-                                int mask_kind, int mode, float min_alpha, const void* scratch, const float* g, float* d_depth,
-                                float* d_alpha, hipStream_t st);
-void launch_scaling_reg_forward(int64_t P, const float* s, void* scratch, float* out, hipStream_t st);
-void launch_scaling_reg_backward(int64_t P, const float* s, const float* g, float* ds, hipStream_t st);
-void launch_l1_ssim_forward(int C, int H, int W, const float* img1, const float* img2, void* scratch,
-                            int with_grad, float* out2, hipStream_t st);
-void launch_l1_ssim_backward(int C, int H, int W, const float* img1, const float* img2, const void* scratch,
-                             const float* g_l1, const float* g_ssim, float* dimg1, hipStream_t st);
-size_t triplane_multi_scratch_bytes(int64_t V, int ngrids, const int* R, const int* X, const int* Y, const int* Z);
-int launch_triplane_backward_multi(int64_t V, const float* coords, int cs, int ngrids, const int* R, const int* X, const int* Y,
-                                   const int* Z, const int* col, const float* grad, int ld, float* const* grad_planes,
-                                   void* scratch, const float* nl_coef, const float* nl_dy, int nl_lddy, const float* nl_x,
-                                   int nl_ldx, hipStream_t st);
-int launch_norm_linear_dx(int64_t V, int d, const float* x, int ldx, const float* dy, int lddy, const float* coef3, float* dx,
-                          int lddx, hipStream_t st);
-int launch_plane_row_pairs(int R, int A, int B, const float* plane, float* pairs, hipStream_t st);
-size_t triplane_scratch_bytes(int64_t V, int A, int B, int channels);
-size_t triplane_backward_scratch_bytes(int64_t V, int X, int Y, int Z, int channels);
-int launch_triplane_backward(int64_t V, const float* coords, int cs, int R, int X, int Y, int Z, int planes,
-                             const float* grad_out, int ld, const int* cols, float* const* grad_planes, void* scratch,
-                             hipStream_t st);
-int launch_plane_sample_backward(int64_t V, const float* coords, int cs, int cx, int cy, int R, int A, int B, int planes,
-                                 const float* grad_out0, const float* grad_out1, int ld, float* grad_plane0,
-                                 float* grad_plane1, void* scratch, hipStream_t st);
-int launch_triplane_forward(int64_t V, const float* coords, int cs, const float* xy, const float* xz, const float* yz,
-                             int R, int X, int Y, int Z, int channel_last, float* out, int ld, int col_xy, int col_xz,
-                             int col_yz, hipStream_t st);
 
 }  // namespace scr

@@ -4,7 +4,7 @@
 //
 //   count   compact_count_kernel<Keep>: kept items per workgroup of 1024 items (256 threads x 4 rounds of 256 items)
 //   scan    compact_scan_kernel (one workgroup): exclusive prefix of the workgroup counts in place, the total to the
-//           scratch and to the host's pinned mailbox (capi.hip reads it there to size the outputs)
+//           scratch and to the host's pinned mailbox (compact_plan() of capi.h reads it there to size the outputs)
 //   write   the user's own kernel, same launch shape; compact_rank() gives every item its `keep` and its output position
 //           = workgroup offset + kept items of earlier rounds + of earlier waves of this round + of lower lanes
 //

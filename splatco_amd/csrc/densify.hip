@@ -135,40 +135,6 @@ static inline bool statis_pairs_ok(int k, const void* a, const void* b, const vo
     return k % 2 == 0 && k <= 512 && ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 7u) == 0);
 }
 
-void launch_statis_compute(int64_t V, int k, const float* neural_opacity, const int32_t* out_index,
-                           const uint8_t* update_filter, const float* grad, int gstride, float* inc_opacity,
-                           float* inc_grad, hipStream_t st) {
-    const int64_t n = V * k;
-    if (n <= 0) return;
-    // (the pair kernel reads entry 0 of update_filter / grad for unselected candidates: both must exist)
-    if (statis_pairs_ok(k, neural_opacity, out_index, inc_grad, inc_grad) && update_filter && grad) {
-        const int per2 = (512 / k) * k;
-        statis_compute2_kernel<<<(unsigned)((n + per2 - 1) / per2), 256, 0, st>>>(V, k, per2, neural_opacity, out_index, update_filter,
-                                                                                 grad, gstride, inc_opacity, inc_grad);
-        return;
-    }
-    const int per = k <= 256 ? (256 / k) * k : 0;
-    if (!per) return;      // scr_statis_compute rejects k > 256
-    statis_compute_kernel<<<(unsigned)((n + per - 1) / per), 256, 0, st>>>(V, k, per, neural_opacity, out_index, update_filter,
-                                                                         grad, gstride, inc_opacity, inc_grad);
-}
-
-void launch_statis_apply(int64_t V, int k, const int64_t* visible_index, const float* inc_opacity, const float* inc_grad,
-                         float* opacity_accum, float* anchor_demon, float* offset_gradient_accum, float* offset_denom,
-                         hipStream_t st) {
-    const int64_t n = V * k;
-    if (n <= 0) return;
-    if (statis_pairs_ok(k, inc_grad, offset_gradient_accum, offset_denom, inc_grad)) {
-        statis_apply2_kernel<<<(unsigned)((n / 2 + 255) / 256), 256, 0, st>>>(V, k, visible_index, inc_opacity, inc_grad,
-                                                                           opacity_accum, anchor_demon, offset_gradient_accum,
-                                                                           offset_denom);
-        return;
-    }
-    statis_apply_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(V, k, visible_index, inc_opacity, inc_grad,
-                                                                   opacity_accum, anchor_demon, offset_gradient_accum,
-                                                                   offset_denom);
-}
-
 }  // namespace scr
 
 // ------------------------------------------------------------------ k nearest neighbours (compute_curvature)
@@ -268,16 +234,83 @@ knn_curvature_kernel(int64_t N, int k, const float* __restrict__ pts, const int6
     curvature[q] = (float)(lmin / tr);
 }
 
-void launch_knn(int64_t N, int k, const float* grid8, const float* sorted_pts, const int64_t* sorted_id,
-                const int32_t* cell_start, int64_t* out_idx, hipStream_t st) {
-    const KnnGrid g = knn_grid(grid8);
+}  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+// ---- densification statistics
+int scr_statis_compute(int64_t V, int32_t k, const float* neural_opacity, const int32_t* out_index,
+                       const uint8_t* update_filter, const float* viewspace_grad, int32_t grad_stride,
+                       float* inc_opacity, float* inc_grad, void* stream) {
+    SCR_MARK_FN;
+    if (V < 0 || k <= 0 || k > 256 || grad_stride < 2) return fail("bad V / k (1..256) / grad_stride");
+    if (V == 0) return 0;
+    if (!neural_opacity || !out_index || !inc_opacity || !inc_grad) return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = V * k;
+    // (the pair kernel reads entry 0 of update_filter / grad for unselected candidates: both must exist)
+    if (statis_pairs_ok(k, neural_opacity, out_index, inc_grad, inc_grad) && update_filter && viewspace_grad) {
+        const int per2 = (512 / k) * k;
+        statis_compute2_kernel<<<(unsigned)((n + per2 - 1) / per2), 256, 0, st>>>(V, k, per2, neural_opacity, out_index, update_filter,
+                                                                                 viewspace_grad, grad_stride, inc_opacity, inc_grad);
+    } else {
+        const int per = (256 / k) * k;
+        statis_compute_kernel<<<(unsigned)((n + per - 1) / per), 256, 0, st>>>(V, k, per, neural_opacity, out_index, update_filter,
+                                                                             viewspace_grad, grad_stride, inc_opacity, inc_grad);
+    }
+    CHECK_LAUNCH("statis_compute_kernel", 0, st);
+    return 0;
+}
+
+int scr_statis_apply(int64_t V, int32_t k, const int64_t* visible_index, const float* inc_opacity, const float* inc_grad,
+                     float* opacity_accum, float* anchor_demon, float* offset_gradient_accum, float* offset_denom,
+                     void* stream) {
+    SCR_MARK_FN;
+    if (V < 0 || k <= 0) return fail("bad V / k");
+    if (V == 0) return 0;
+    if (!visible_index || !inc_opacity || !inc_grad || !opacity_accum || !anchor_demon || !offset_gradient_accum ||
+        !offset_denom)
+        return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = V * k;
+    if (statis_pairs_ok(k, inc_grad, offset_gradient_accum, offset_denom, inc_grad))
+        statis_apply2_kernel<<<(unsigned)((n / 2 + 255) / 256), 256, 0, st>>>(V, k, visible_index, inc_opacity, inc_grad,
+                                                                           opacity_accum, anchor_demon, offset_gradient_accum,
+                                                                           offset_denom);
+    else
+        statis_apply_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(V, k, visible_index, inc_opacity, inc_grad,
+                                                                       opacity_accum, anchor_demon, offset_gradient_accum,
+                                                                       offset_denom);
+    CHECK_LAUNCH("statis_apply_kernel", 0, st);
+    return 0;
+}
+
+// ---- k nearest neighbours and the curvature of their covariance
+int scr_knn(int64_t N, int32_t k, const float* grid_host, const float* sorted_pts, const int64_t* sorted_id,
+            const int32_t* cell_start, int64_t* out_idx, void* stream) {
+    SCR_MARK_FN;
+    if (check_knn_grid("scr_knn", N, grid_host)) return 1;
+    if (k <= 0 || k > 16) return fail("scr_knn: need 1 <= k <= 16");
+    if (N <= k) return fail("scr_knn: fewer than k + 1 points");
+    if (!sorted_pts || !sorted_id || !cell_start || !out_idx) return fail("scr_knn: NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const KnnGrid g = knn_grid(grid_host);
     const unsigned grid = (unsigned)((N + 255) / 256);
     if (k <= 10) knn_kernel<10><<<grid, 256, 0, st>>>(N, k, g, sorted_pts, sorted_id, cell_start, out_idx);   // the reference's k
     else knn_kernel<KNN_MAX_K><<<grid, 256, 0, st>>>(N, k, g, sorted_pts, sorted_id, cell_start, out_idx);
+    CHECK_LAUNCH("knn_kernel", 0, st);
+    return 0;
 }
 
-void launch_knn_curvature(int64_t N, int k, const float* pts, const int64_t* idx, float* curvature, hipStream_t st) {
-    knn_curvature_kernel<<<(unsigned)((N + 255) / 256), 256, 0, st>>>(N, k, pts, idx, curvature);
+int scr_knn_curvature(int64_t N, int32_t k, const float* points, const int64_t* idx, float* curvature, void* stream) {
+    SCR_MARK_FN;
+    if (N <= 0 || k < 2) return fail("bad N / k");
+    if (!points || !idx || !curvature) return fail("NULL argument");
+    knn_curvature_kernel<<<(unsigned)((N + 255) / 256), 256, 0, (hipStream_t)stream>>>(N, k, points, idx, curvature);
+    CHECK_LAUNCH("knn_curvature_kernel", 0, (hipStream_t)stream);
+    return 0;
 }
 
-}  // namespace scr
+}  // extern "C"

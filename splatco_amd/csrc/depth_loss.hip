@@ -15,6 +15,7 @@
 // record per workgroup, each followed by a one-workgroup fold, and one element-wise backward pass.  Every sum has the fixed
 // order of wg.h (wg_sum per workgroup, fold_sum over the records), so a result is the same bits run after run.  No atomics,
 // no memset: every scratch word that is read was written by an earlier launch of the same call.
+#include "capi.h"
 #include "wg.h"
 
 namespace scr {
@@ -167,28 +168,60 @@ depth_loss_backward_kernel(int64_t n, const float* __restrict__ depth, const flo
     }
 }
 
-size_t depth_loss_scratch_bytes(int H, int W) { return dl_layout(nullptr, (int64_t)H * W).bytes; }
-
-void launch_depth_loss_forward(int H, int W, const float* depth, const float* alpha, const float* target, const void* mask,
-                               int mask_kind, int mode, int align, float min_alpha, void* scratch, float* out4, hipStream_t st) {
-    const int64_t n = (int64_t)H * W;
-    const int nb = (int)dl_blocks(n);
-    const DlScratch sc = dl_layout(scratch, n);
-    if (align) {
-        depth_loss_moments_kernel<<<nb, DL_THREADS, 0, st>>>(n, depth, alpha, target, mask, mask_kind, mode, min_alpha, sc.mom);
-        depth_loss_solve_kernel<<<1, DL_FOLD, 0, st>>>(nb, sc.mom, sc.st);
-    }
-    depth_loss_residual_kernel<<<nb, DL_THREADS, 0, st>>>(n, depth, alpha, target, mask, mask_kind, mode, min_alpha,
-                                                         align ? sc.st : nullptr, sc.res);
-    depth_loss_finish_kernel<<<1, DL_FOLD, 0, st>>>(nb, sc.res, 1.0 / (double)n, align, sc.st, out4);
-}
-
-void launch_depth_loss_backward(int H, int W, const float* depth, const float* alpha, const float* target, const void* mask,
-                                int mask_kind, int mode, float min_alpha, const void* scratch, const float* g, float* d_depth,
-                                float* d_alpha, hipStream_t st) {
-    const int64_t n = (int64_t)H * W;
-    depth_loss_backward_kernel<<<(int)dl_blocks(n), DL_THREADS, 0, st>>>(n, depth, alpha, target, mask, mask_kind, mode, min_alpha,
-                                                                         (const double*)scratch, g, 1.0 / (double)n, d_depth, d_alpha);
+static int depth_loss_args(int32_t H, int32_t W, const void* mask, int32_t mask_kind, int32_t mode, float min_alpha) {
+    if (H < 1 || W < 1) return fail("depth_loss: bad image size H = %d, W = %d", H, W);
+    if ((int64_t)H * W > 2147483647LL) return fail("depth_loss: H W = %lld exceeds 2^31 - 1", (long long)H * W);
+    if (mask_kind < 0 || mask_kind > 2) return fail("depth_loss: mask_kind %d (0 none, 1 float32, 2 uint8)", mask_kind);
+    if (mask_kind != 0 && !mask) return fail("depth_loss: mask is NULL with mask_kind %d", mask_kind);
+    if (mode != 0 && mode != 1) return fail("depth_loss: mode %d (0 inverse, 1 expected)", mode);
+    if (!(min_alpha >= 0.0f) || !(min_alpha <= 3.402823466e38f)) return fail("depth_loss: min_alpha %g must be finite and >= 0", (double)min_alpha);
+    return 0;
 }
 
 }  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+size_t scr_depth_loss_scratch_bytes(int32_t H, int32_t W) { return dl_layout(nullptr, (int64_t)(H > 0 ? H : 1) * (W > 0 ? W : 1)).bytes; }
+
+int scr_depth_loss_forward(int32_t H, int32_t W, const float* depth, const float* alpha, const float* target, const void* mask,
+                           int32_t mask_kind, int32_t mode, int32_t align, float min_alpha, void* scratch, float* out4,
+                           void* stream) {
+    SCR_MARK_FN;
+    if (depth_loss_args(H, W, mask, mask_kind, mode, min_alpha)) return 1;
+    if (!depth || !alpha || !target || !scratch || !out4) return fail("depth_loss: NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = (int64_t)H * W;
+    const int nb = (int)dl_blocks(n);
+    const DlScratch sc = dl_layout(scratch, n);
+    { ProfScope ps_(SCR_PROF_L1_SSIM, st);
+      if (align) {
+          depth_loss_moments_kernel<<<nb, DL_THREADS, 0, st>>>(n, depth, alpha, target, mask, mask_kind, mode, min_alpha, sc.mom);
+          depth_loss_solve_kernel<<<1, DL_FOLD, 0, st>>>(nb, sc.mom, sc.st);
+      }
+      depth_loss_residual_kernel<<<nb, DL_THREADS, 0, st>>>(n, depth, alpha, target, mask, mask_kind, mode, min_alpha,
+                                                           align ? sc.st : nullptr, sc.res);
+      depth_loss_finish_kernel<<<1, DL_FOLD, 0, st>>>(nb, sc.res, 1.0 / (double)n, align != 0, sc.st, out4); }
+    CHECK_LAUNCH("depth_loss_residual_kernel", 0, st);
+    return 0;
+}
+
+int scr_depth_loss_backward(int32_t H, int32_t W, const float* depth, const float* alpha, const float* target, const void* mask,
+                            int32_t mask_kind, int32_t mode, float min_alpha, const void* scratch, const float* g, float* d_depth,
+                            float* d_alpha, void* stream) {
+    SCR_MARK_FN;
+    if (depth_loss_args(H, W, mask, mask_kind, mode, min_alpha)) return 1;
+    if (!depth || !alpha || !target || !scratch || !g) return fail("depth_loss: NULL argument");
+    if (!d_depth && !d_alpha) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = (int64_t)H * W;
+    { ProfScope ps_(SCR_PROF_L1_SSIM_BACKWARD, st);
+      depth_loss_backward_kernel<<<(int)dl_blocks(n), DL_THREADS, 0, st>>>(n, depth, alpha, target, mask, mask_kind, mode, min_alpha,
+                                                                           (const double*)scratch, g, 1.0 / (double)n, d_depth, d_alpha); }
+    CHECK_LAUNCH("depth_loss_backward_kernel", 0, st);
+    return 0;
+}
+
+}  // extern "C"

@@ -14,7 +14,7 @@
 // Compaction = the count / scan / write scheme of compact.h (count pass reads 4 B per candidate); this file
 // supplies the predicates, the write kernels and the scheme's one scan kernel.  Backward is one thread per candidate;
 // the per-anchor sums over its k candidates go through LDS in slot order -> no atomics, deterministic.
-#include "compact.h"
+#include "capi.h"
 
 namespace scr {
 
@@ -199,41 +199,103 @@ expand_backward_kernel(int64_t V, int k, int apw, const float* __restrict__ scal
     }
 }
 
-void launch_expand_count(int64_t n, const float* neural_opacity, const CompactScratch& s, unsigned long long* mailbox,
-                         unsigned long long seq, hipStream_t st) {
-    launch_compact_count(n, KeepOpacity{neural_opacity}, s, mailbox, seq, st);
+}  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+size_t scr_expand_scratch_bytes(int64_t n) { return compact_scratch_bytes(n); }
+
+int scr_expand_plan(int64_t n, const float* neural_opacity, void* scratch, int64_t* num_selected_host,
+                    void* stream) {
+    SCR_MARK_FN;
+    if (!num_selected_host) return fail("num_selected_host is NULL");
+    *num_selected_host = 0;
+    if (n < 0) return fail("n < 0");
+    if (n == 0) return 0;
+    if (!neural_opacity || !scratch) return fail("NULL argument");
+    if (n >= (1ll << 31)) return fail("more than 2^31 candidates");
+    hipStream_t st = (hipStream_t)stream;
+    return compact_plan("compact_count_kernel<KeepOpacity>", n, scratch, num_selected_host, st,
+                        [&](const CompactScratch& s, unsigned long long* mb, unsigned long long seq) {
+                            ProfScope ps_(SCR_PROF_EXPAND, st);
+                            launch_compact_count(n, KeepOpacity{neural_opacity}, s, mb, seq, st);
+                        });
 }
 
-void launch_mask_count(int64_t n, const uint8_t* mask, const CompactScratch& s, unsigned long long* mailbox,
-                       unsigned long long seq, hipStream_t st) {
-    launch_compact_count(n, KeepMask{mask}, s, mailbox, seq, st);
-}
-void launch_mask_index(int64_t n, const uint8_t* mask, const uint32_t* wg_offset, int64_t* index, int64_t* inverse,
-                       hipStream_t st) {
-    mask_index_kernel<<<(uint32_t)compact_nwg(n), COMPACT_THREADS, 0, st>>>(n, KeepMask{mask}, wg_offset, index, inverse);
+// mask -> index list with the expansion's count / scan / write scheme (scratch: scr_expand_scratch_bytes(n))
+int scr_mask_index_plan(int64_t n, const uint8_t* mask, void* scratch, int64_t* num_set_host, void* stream) {
+    SCR_MARK_FN;
+    if (!num_set_host) return fail("num_set_host is NULL");
+    *num_set_host = 0;
+    if (n < 0) return fail("n < 0");
+    if (n == 0) return 0;
+    if (!mask || !scratch) return fail("NULL argument");
+    if (n >= (1ll << 31)) return fail("more than 2^31 mask entries");
+    hipStream_t st = (hipStream_t)stream;
+    return compact_plan("compact_count_kernel<KeepMask>", n, scratch, num_set_host, st,
+                        [&](const CompactScratch& s, unsigned long long* mb, unsigned long long seq) {
+                            ProfScope ps_(SCR_PROF_EXPAND, st);
+                            launch_compact_count(n, KeepMask{mask}, s, mb, seq, st);
+                        });
 }
 
-void launch_expand_run(int64_t n, int k, const float* neural_opacity, const float* color, const float* scale_rot,
-                       const float* offsets, int ldo, const float* grid_scaling, const float* anchor,
-                       const uint32_t* wg_offset, int32_t* out_index, uint8_t* mask_out, float* xyz,
-                       float* color_out, float* opacity, float* scaling, float* rot, hipStream_t st) {
-    expand_run_kernel<<<(uint32_t)compact_nwg(n), COMPACT_THREADS, 0, st>>>(n, k, neural_opacity, color, scale_rot, offsets, ldo,
-                                                                            grid_scaling, anchor, wg_offset, out_index, mask_out,
-                                                                            xyz, color_out, opacity, scaling, rot);
+int scr_mask_index_run(int64_t n, const uint8_t* mask, const void* scratch, int64_t* index, int64_t* inverse, void* stream) {
+    SCR_MARK_FN;
+    if (n <= 0) return n < 0 ? fail("n < 0") : 0;
+    if (!mask || !scratch || (!index && !inverse)) return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    { ProfScope ps_(SCR_PROF_EXPAND, st);
+      mask_index_kernel<<<(uint32_t)compact_nwg(n), COMPACT_THREADS, 0, st>>>(n, KeepMask{mask}, (const uint32_t*)scratch, index, inverse); }
+    CHECK_LAUNCH("mask_index_kernel", 0, st);
+    return 0;
 }
 
-void launch_expand_backward(int64_t V, int k, const float* scale_rot, const float* offsets, int ldo,
-                            const float* grid_scaling, const int32_t* out_index, const float* g_xyz,
-                            const float* g_color, const float* g_opacity, const float* g_scaling,
-                            const float* g_rot, float* d_neural_opacity, float* d_color, float* d_scale_rot,
-                            float* d_offsets, float* d_grid_scaling, float* d_anchor, const float* g_reg, int64_t P,
-                            hipStream_t st) {
+int scr_expand_run(int64_t V, int32_t k, const float* neural_opacity, const float* color,
+                   const float* scale_rot, const float* offsets, int32_t offsets_ld, const float* grid_scaling,
+                   const float* anchor, const void* scratch, int32_t* out_index, uint8_t* mask_out,
+                   float* xyz, float* color_out, float* opacity, float* scaling, float* rot, void* stream) {
+    SCR_MARK_FN;
+    if (V < 0 || k <= 0) return fail("bad V / k");
+    if (offsets_ld < 3 * k) return fail("offsets_ld %d: the offset rows of an anchor are 3 k = %d floats long", offsets_ld, 3 * k);
+    if (V == 0) return 0;
+    if (!neural_opacity || !color || !scale_rot || !offsets || !grid_scaling || !anchor || !scratch || !out_index)
+        return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = V * k;
+    { ProfScope ps_(SCR_PROF_EXPAND, st);
+      expand_run_kernel<<<(uint32_t)compact_nwg(n), COMPACT_THREADS, 0, st>>>(n, k, neural_opacity, color, scale_rot, offsets, offsets_ld,
+                                                                              grid_scaling, anchor, (const uint32_t*)scratch, out_index,
+                                                                              mask_out, xyz, color_out, opacity, scaling, rot); }
+    CHECK_LAUNCH("expand_run_kernel", 0, st);
+    return 0;
+}
+
+int scr_expand_backward(int64_t V, int32_t k, const float* scale_rot, const float* offsets, int32_t offsets_ld,
+                        const float* grid_scaling, const int32_t* out_index, const float* g_xyz,
+                        const float* g_color, const float* g_opacity, const float* g_scaling,
+                        const float* g_rot, float* d_neural_opacity, float* d_color, float* d_scale_rot,
+                        float* d_offsets, float* d_grid_scaling, float* d_anchor, const float* g_reg, int64_t P,
+                        void* stream) {
+    SCR_MARK_FN;
+    if (V < 0 || k <= 0) return fail("bad V / k");
+    if (g_reg && P <= 0) return fail("scr_expand_backward: g_reg needs P = the number of selected candidates");
+    if (offsets_ld < 3 * k) return fail("offsets_ld %d: the offset rows of an anchor are 3 k = %d floats long", offsets_ld, 3 * k);
+    if (V == 0) return 0;
+    if (!scale_rot || !offsets || !grid_scaling || !out_index || !d_neural_opacity || !d_color || !d_scale_rot ||
+        !d_offsets || !d_grid_scaling || !d_anchor)
+        return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
     const int apw = max(1, min(32, (48 * 1024) / (k * 9 * (int)sizeof(float))));
     const int threads = min(1024, ((apw * k + 63) / 64) * 64);
-    expand_backward_kernel<<<(unsigned)((V + apw - 1) / apw), threads, (size_t)apw * k * 9 * sizeof(float), st>>>(
-        V, k, apw, scale_rot, offsets, ldo, grid_scaling, out_index, g_xyz, g_color, g_opacity, g_scaling, g_rot,
-        d_neural_opacity, d_color, d_scale_rot, d_offsets, d_grid_scaling, d_anchor, g_reg,
-        P > 0 ? (float)(1.0 / (double)P) : 0.0f);
+    { ProfScope ps_(SCR_PROF_EXPAND_BACKWARD, st);
+      expand_backward_kernel<<<(unsigned)((V + apw - 1) / apw), threads, (size_t)apw * k * 9 * sizeof(float), st>>>(
+          V, k, apw, scale_rot, offsets, offsets_ld, grid_scaling, out_index, g_xyz, g_color, g_opacity, g_scaling, g_rot,
+          d_neural_opacity, d_color, d_scale_rot, d_offsets, d_grid_scaling, d_anchor, g_reg,
+          P > 0 ? (float)(1.0 / (double)P) : 0.0f); }
+    CHECK_LAUNCH("expand_backward_kernel", 0, st);
+    return 0;
 }
 
-}  // namespace scr
+}  // extern "C"

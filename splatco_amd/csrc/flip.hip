@@ -14,6 +14,7 @@
 // keeps exactly: the vertical pass reads the horizontal results of clamped rows.
 #include <math.h>
 
+#include "capi.h"
 #include "wg.h"
 
 namespace scr {
@@ -221,7 +222,7 @@ flip_reduce_kernel(int tiles, const float2* __restrict__ partial, double inv_hw,
 constexpr double FL_PI = 3.14159265358979323846;
 
 // radii for `ppd`: 0 on success, -1 when ppd is not a finite value >= 1 or a radius exceeds FL_RMAX
-int flip_radii(double ppd, int* rc, int* rf) {
+static int flip_radii(double ppd, int* rc, int* rf) {
     if (!(ppd >= 1.0) || !std::isfinite(ppd)) return -1;
     // CSF: 3 standard deviations of the widest Gaussian (b = 0.04 of the BY CSF); features: 3 sd of the detector
     const double c = ceil(3.0 * sqrt(0.04 / (2.0 * FL_PI * FL_PI)) * ppd);
@@ -234,7 +235,7 @@ int flip_radii(double ppd, int* rc, int* rf) {
 
 // binary64 1-D weights [7][FL_NW] (a, rg, by1, by2, edge, point, gauss; tap k at offset k - r, zero beyond 2r),
 // scalars [3] = (by_c1, by_c2, cmax)
-int flip_filters(double ppd, double* w, int* radii, double* scalars) {
+static int flip_filters(double ppd, double* w, int* radii, double* scalars) {
     int rc, rf;
     if (flip_radii(ppd, &rc, &rf)) return -1;
     for (int i = 0; i < 7 * FL_NW; ++i) w[i] = 0.0;
@@ -300,16 +301,29 @@ int flip_filters(double ppd, double* w, int* radii, double* scalars) {
     return 0;
 }
 
-size_t flip_scratch_bytes(int N, int H, int W) {
+}  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+size_t scr_flip_scratch_bytes(int32_t N, int32_t H, int32_t W) {
+    if (N <= 0 || H <= 0 || W <= 0) return 0;
     const size_t tiles = (size_t)((W + FL_T - 1) / FL_T) * ((H + FL_T - 1) / FL_T);
     return align_up(tiles * N * sizeof(float2));
 }
 
-int launch_flip_forward(int N, int H, int W, const float* test, const float* ref, double ppd, int quantize,
-                        void* scratch, float* mean_out, float* mse_out, float* map_out, hipStream_t st) {
+int scr_flip_forward(int32_t N, int32_t H, int32_t W, const float* test, const float* ref, double pixels_per_degree,
+                     int32_t quantize, void* scratch, float* mean_out, float* mse_out, float* map_out, void* stream) {
+    SCR_MARK_FN;
+    if (N <= 0 || H <= 0 || W <= 0) return fail("bad image size");
+    if (N > 65535 || (H + 15) / 16 > 65535) return fail("N = %d / H = %d exceed the launch grid", N, H);
+    if (!test || !ref || !scratch || !mean_out) return fail("NULL argument");
     double w[7 * FL_NW], sc[3];
     int radii[2];
-    if (flip_filters(ppd, w, radii, sc)) return -1;
+    if (flip_filters(pixels_per_degree, w, radii, sc))
+        return fail("pixels_per_degree %g: must be >= 1 with filter radii <= %d", pixels_per_degree, SCR_FLIP_MAX_RADIUS);
+    hipStream_t st = (hipStream_t)stream;
     FlipFilters F;
     F.rc = radii[0];
     F.rf = radii[1];
@@ -324,9 +338,18 @@ int launch_flip_forward(int N, int H, int W, const float* test, const float* ref
     F.quantize = quantize ? 1 : 0;
     const dim3 grid((W + FL_T - 1) / FL_T, (H + FL_T - 1) / FL_T, N);
     float2* partial = (float2*)scratch;
-    flip_kernel<<<grid, 256, 0, st>>>(H, W, test, ref, F, map_out, partial);
-    flip_reduce_kernel<<<N, 256, 0, st>>>((int)(grid.x * grid.y), partial, 1.0 / ((double)H * W), mean_out, mse_out);
+    { ProfScope ps_(SCR_PROF_FLIP, st);
+      flip_kernel<<<grid, 256, 0, st>>>(H, W, test, ref, F, map_out, partial);
+      flip_reduce_kernel<<<N, 256, 0, st>>>((int)(grid.x * grid.y), partial, 1.0 / ((double)H * W), mean_out, mse_out); }
+    CHECK_LAUNCH("flip_kernel", 0, st);
     return 0;
 }
 
-}  // namespace scr
+int scr_flip_filters(double pixels_per_degree, double* weights, int32_t* radii, double* scalars) {
+    if (!weights || !radii || !scalars) return fail("NULL argument");
+    if (flip_filters(pixels_per_degree, weights, radii, scalars))
+        return fail("pixels_per_degree %g: must be >= 1 with filter radii <= %d", pixels_per_degree, SCR_FLIP_MAX_RADIUS);
+    return 0;
+}
+
+}  // extern "C"

@@ -12,7 +12,7 @@
 //                 __device__ float worst() const; };            // the search may stop once worst() <= reach^2
 // Arithmetic order is normative (-ffp-contract=off): e = p_j - p_i, d = (ex*ex + ey*ey) + ez*ez.
 #pragma once
-#include "common.h"
+#include "capi.h"        // fail(): both users define entry points
 
 #include <math.h>
 
@@ -29,6 +29,15 @@ inline __host__ KnnGrid knn_grid(const float* g8) {
     g.x0 = g8[0]; g.y0 = g8[1]; g.z0 = g8[2]; g.h = g8[3]; g.inv_h = 1.0f / g8[3];
     g.nx = (int)g8[4]; g.ny = (int)g8[5]; g.nz = (int)g8[6]; g.slack = g8[7];
     return g;
+}
+
+// the one grid descriptor check of scr_knn_cell_keys, scr_knn and scr_knn3_dist2: the kernels index points and cells with int
+inline __host__ int check_knn_grid(const char* who, int64_t N, const float* g) {
+    if (N <= 0 || N >= (1ll << 31)) return fail("%s: need 0 < N < 2^31", who);
+    if (!g) return fail("%s: grid_host is NULL", who);
+    if (!(g[3] > 0.0f) || g[4] < 1 || g[5] < 1 || g[6] < 1 || !(g[7] >= 0.0f)) return fail("%s: bad grid", who);
+    if ((double)g[4] * g[5] * g[6] >= 2147483647.0) return fail("%s: more than 2^31 - 2 cells", who);
+    return 0;
 }
 
 // the ONE cell function: the bucketing kernel and the search both call it, so a point's bucket is the cell the search

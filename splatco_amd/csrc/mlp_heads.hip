@@ -26,7 +26,7 @@
 // gradients, whose contraction runs over the anchors: their operands go through a wave-private LDS transpose.
 // Weight-gradient partial sums stay in registers for all tiles of a wave, are written once per wave and summed in
 // wave order by a second kernel: no atomics, bit-reproducible.
-#include "common.h"
+#include "capi.h"
 
 namespace scr {
 
@@ -516,39 +516,66 @@ mlp_heads_reduce_kernel(int nparts, const float* __restrict__ partial, float* __
     }
 }
 
-// ---------------------------------------------------------------- launchers
+// ---------------------------------------------------------------- entry points
 static int mh_grid(int64_t V, int per_cu = 1) {
     const int64_t tiles = (V + 15) / 16;
     const int64_t want = (tiles + MH_WAVES - 1) / MH_WAVES, cap = 256 * per_cu;
     return (int)(want < cap ? (want > 0 ? want : 1) : cap);      // `per_cu` workgroups per CU, grid-stride over the tiles
 }
 
-size_t mlp_heads_hidden_bytes(int64_t V) { return align_up((size_t)((V + 15) / 16) * MH_MT * 64 * sizeof(f4)); }
-size_t mlp_heads_partial_bytes(int64_t V) { return align_up((size_t)mh_grid(V) * MH_WAVES * MH_PART * sizeof(float)); }
+}  // namespace scr
 
-void launch_mlp_heads_forward(int64_t V, const float* feat, int ldf, const float* anchor, const float* campos, const float* geo_a,
-                              const float* geo_b, const float* w1, const float* b1, const float* w2o, const float* b2o, const float* w2c,
-                              const float* b2c, const float* w2v, const float* b2v, void* hidden_save, float* out_o,
-                              float* out_c, float* out_v, hipStream_t st) {
+using namespace scr;
+
+extern "C" {
+
+size_t scr_mlp_heads_hidden_bytes(int64_t V) { return align_up((size_t)(((V > 0 ? V : 1) + 15) / 16) * MH_MT * 64 * sizeof(f4)); }
+size_t scr_mlp_heads_partial_bytes(int64_t V) { return align_up((size_t)mh_grid(V > 0 ? V : 1) * MH_WAVES * MH_PART * sizeof(float)); }
+
+int scr_mlp_heads_forward(int64_t V, const float* feat, int32_t feat_ld, const float* anchor, const float* campos, const float* geo_a, const float* geo_b,
+                          const float* w1, const float* b1, const float* w2o, const float* b2o, const float* w2c,
+                          const float* b2c, const float* w2v, const float* b2v, void* hidden_save, float* out_opacity,
+                          float* out_color, float* out_cov, void* stream) {
+    SCR_MARK_FN;
+    if (V < 0) return fail("V < 0");
+    if (feat_ld < 32 || feat_ld % 4 != 0 || ((uintptr_t)feat & 15) != 0) return fail("feat rows: 32 floats, 16-byte aligned, feat_ld a multiple of 4 (got %d)", feat_ld);
+    if (V == 0) return 0;
+    if (!feat || !anchor || !campos || !geo_a || !geo_b || !w1 || !b1 || !w2o || !b2o || !w2c || !b2c || !w2v || !b2v || !hidden_save ||
+        !out_opacity || !out_color || !out_cov)
+        return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
     MhWeights w{w1, b1, {w2o, w2c, w2v}, {b2o, b2c, b2v}};
-    mlp_heads_forward_kernel<<<mh_grid(V, 2), 64 * MH_WAVES, 0, st>>>(V, feat, ldf, anchor, campos, geo_a, geo_b, w, (f4*)hidden_save, out_o,
-                                                                   out_c, out_v);
+    { ProfScope ps_(SCR_PROF_MLP_HEADS, st);
+      mlp_heads_forward_kernel<<<mh_grid(V, 2), 64 * MH_WAVES, 0, st>>>(V, feat, feat_ld, anchor, campos, geo_a, geo_b, w, (f4*)hidden_save,
+                                                                     out_opacity, out_color, out_cov); }
+    CHECK_LAUNCH("mlp_heads_forward_kernel", 0, st);
+    return 0;
 }
 
-void launch_mlp_heads_backward(int64_t V, const float* feat, int ldf, const float* anchor, const float* campos, const float* geo_a,
-                               const float* geo_b, const float* w1, const float* w2o, const float* w2c, const float* w2v,
-                               const void* hidden_save, const float* out_o, const float* out_c, const float* g_o,
-                               const float* g_c, const float* g_v, void* partial, float* d_feat, float* d_anchor,
-                               float* d_geo_a, float* d_geo_b, float* d_w1, float* d_b1, float* d_w2o, float* d_b2o, float* d_w2c,
-                               float* d_b2c, float* d_w2v, float* d_b2v, hipStream_t st) {
+int scr_mlp_heads_backward(int64_t V, const float* feat, int32_t feat_ld, const float* anchor, const float* campos, const float* geo_a, const float* geo_b,
+                           const float* w1, const float* w2o, const float* w2c, const float* w2v, const void* hidden_save,
+                           const float* out_opacity, const float* out_color, const float* g_opacity, const float* g_color,
+                           const float* g_cov, void* partial, float* d_feat, float* d_anchor, float* d_geo_a, float* d_geo_b, float* d_w1,
+                           float* d_b1, float* d_w2o, float* d_b2o, float* d_w2c, float* d_b2c, float* d_w2v, float* d_b2v,
+                           void* stream) {
+    SCR_MARK_FN;
+    if (V <= 0) return fail("V <= 0");
+    if (feat_ld < 32 || feat_ld % 4 != 0 || ((uintptr_t)feat & 15) != 0) return fail("feat rows: 32 floats, 16-byte aligned, feat_ld a multiple of 4 (got %d)", feat_ld);
+    if (!feat || !anchor || !campos || !geo_a || !geo_b || !w1 || !w2o || !w2c || !w2v || !hidden_save || !out_opacity || !out_color ||
+        !g_opacity || !g_color || !g_cov || !partial || !d_feat || !d_anchor || !d_geo_a || !d_geo_b || !d_w1 || !d_b1 || !d_w2o || !d_b2o ||
+        !d_w2c || !d_b2c || !d_w2v || !d_b2v)
+        return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
     MhWeights w{w1, nullptr, {w2o, w2c, w2v}, {nullptr, nullptr, nullptr}};
     const int grid = mh_grid(V);
-    mlp_heads_backward_kernel<<<grid, 64 * MH_WAVES, 0, st>>>(V, feat, ldf, anchor, campos, geo_a, geo_b, w, (const f4*)hidden_save,
-                                                              out_o, out_c, g_o, g_c, g_v, d_feat, d_anchor, d_geo_a, d_geo_b,
-                                                              (float*)partial);
-    mlp_heads_reduce_kernel<<<(MH_PART + 31) / 32, 256, 0, st>>>(grid * MH_WAVES, (const float*)partial, d_w1, d_b1, d_w2o,
-                                                                  d_b2o, d_w2c, d_b2c, d_w2v, d_b2v);
+    { ProfScope ps_(SCR_PROF_MLP_HEADS_BACKWARD, st);
+      mlp_heads_backward_kernel<<<grid, 64 * MH_WAVES, 0, st>>>(V, feat, feat_ld, anchor, campos, geo_a, geo_b, w, (const f4*)hidden_save,
+                                                                out_opacity, out_color, g_opacity, g_color, g_cov, d_feat, d_anchor,
+                                                                d_geo_a, d_geo_b, (float*)partial);
+      mlp_heads_reduce_kernel<<<(MH_PART + 31) / 32, 256, 0, st>>>(grid * MH_WAVES, (const float*)partial, d_w1, d_b1, d_w2o,
+                                                                    d_b2o, d_w2c, d_b2c, d_w2v, d_b2v); }
+    CHECK_LAUNCH("mlp_heads_backward_kernel", 0, st);
+    return 0;
 }
 
-
-}  // namespace scr
+}  // extern "C"

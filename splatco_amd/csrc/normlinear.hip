@@ -20,7 +20,7 @@
 // Rows ("anchors") lie along N, features along M, so a lane's four accumulator registers are four consecutive
 // features of one row: 16-byte stores.  A lane loads 16 bytes of a row (columns 16 q + 4 g .. + 3 for g = lane >> 4)
 // and feeds them to four MFMA steps; the contraction index is permuted accordingly on the weight side.
-#include "common.h"
+#include "capi.h"
 #include <mutex>
 #include <unordered_map>
 
@@ -47,11 +47,6 @@ static inline int nl_stat_wgs(int64_t V) { return (int)((V + NL_SLAB - 1) / NL_S
 static inline int nl_bwd_wgs(int64_t V) {
     const int64_t blocks = (V + 63) / 64;           // a wave takes 16 rows per step, a workgroup 64
     return (int)(blocks < 1024 ? (blocks > 0 ? blocks : 1) : 1024);
-}
-
-size_t norm_linear_scratch_bytes(int64_t V) {
-    return align_up((size_t)NLC_END * 4) + align_up((size_t)nl_stat_wgs(V) * 2 * NL_DP * 4) +
-           align_up((size_t)nl_bwd_wgs(V) * NL_HSIZE * 4);
 }
 
 // ---- column statistics, pass 1: per-workgroup sums of (x - shift) and (x - shift)^2, shift = the first row
@@ -413,93 +408,6 @@ static inline unsigned nl_grid(int64_t V, K kernel) {
     return (unsigned)(wgs < cap ? (wgs > 0 ? wgs : 1) : cap);
 }
 
-// stats (may be NULL): column statistics the PRODUCER of x already formed -- stat_rows rows of [2][NL_DP] floats, sums of
-// (x - x[0]) and (x - x[0])^2 over disjoint sets of rows that cover x (the anchor gather holds every 64 rows of its matrix
-// in LDS anyway: csrc/anchor_gather.hip) -- then the statistics pass over x (1.3 GB at configs[2]) is skipped.
-int launch_norm_linear_forward(int64_t V, int d, const float* x, int ldx, const float* G, const float* c, float eps, float* y,
-                               float* mean, float* var, float* inv, void* scratch, const float* stats, int stat_rows,
-                               hipStream_t st) {
-    if (d < 1 || d > NL_DP) return 1;
-    float* coef = (float*)scratch;
-    float* spart = (float*)((char*)scratch + align_up((size_t)NLC_END * 4));
-    if (stats && stat_rows > 0) {
-        nl_stats_finish_kernel<<<1, 1024, 0, st>>>(V, d, stat_rows, x, stats, G, c, eps, mean, var, inv, coef);
-    } else {
-    // slabs of 2048 rows until they are more than the chip holds at once (8 workgroups per CU), then one round of larger
-    // slabs: 2246 workgroups on 2048 places ran a second round at a tenth of the machine, and the single-workgroup finish
-    // kernel read 9 k partials at 18 M rows
-    const int resident = d <= 64 ? nl_resident_wgs(nl_stats_partial_kernel<64>, 256, 2048) : nl_resident_wgs(nl_stats_partial_kernel<128>, 256, 2048);
-    int64_t slab = NL_SLAB;
-    if ((V + slab - 1) / slab > resident) slab = ((V + resident - 1) / resident + 7) / 8 * 8;
-    const int nwg = (int)((V + slab - 1) / slab);          // <= nl_stat_wgs(V): the scratch holds it
-    if (d <= 64) nl_stats_partial_kernel<64><<<nwg, 256, 0, st>>>(V, d, (int)slab, x, ldx, spart);
-    else nl_stats_partial_kernel<128><<<nwg, 256, 0, st>>>(V, d, (int)slab, x, ldx, spart);
-    nl_stats_finish_kernel<<<1, 1024, 0, st>>>(V, d, nwg, x, spart, G, c, eps, mean, var, inv, coef);
-    }
-    const bool al = ldx % 4 == 0 && ((uintptr_t)x & 15) == 0;
-#define SCR_NL_FWD(QQ)                                                                                                              \
-    case QQ:                                                                                                                        \
-        if (al) nl_forward_kernel<QQ, true><<<nl_grid(V, nl_forward_kernel<QQ, true>), 256, 0, st>>>(V, d, x, ldx, coef, y);        \
-        else nl_forward_kernel<QQ, false><<<nl_grid(V, nl_forward_kernel<QQ, false>), 256, 0, st>>>(V, d, x, ldx, coef, y);         \
-        break;
-    switch ((d + 15) / 16) { SCR_NL_FWD(1) SCR_NL_FWD(2) SCR_NL_FWD(3) SCR_NL_FWD(4) SCR_NL_FWD(5) }
-#undef SCR_NL_FWD
-    return 0;
-}
-
-// coef_out (may be NULL): the coefficients of pass 3 -- Gi [32][NL_DP] | k0 [NL_DP] | k1 [NL_DP], contiguous -- copied out for a
-// consumer that forms the rows of dx itself (csrc/anchor_gather.hip, csrc/triplane.hip pass 3); with dx == NULL pass 3 is
-// not run here at all.
-int launch_norm_linear_backward(int64_t V, int d, const float* x, int ldx, const float* dy, int lddy, const float* G,
-                                const float* mean, const float* inv, float* dx, int lddx, float* dG, float* dc, void* scratch,
-                                float* coef_out, hipStream_t st) {
-    if (d < 1 || d > NL_DP) return 1;
-    if (lddy % 4 != 0 || ((uintptr_t)dy & 15) != 0) return 2;
-    float* coef = (float*)scratch;
-    float* bpart = (float*)((char*)scratch + align_up((size_t)NLC_END * 4) + align_up((size_t)nl_stat_wgs(V) * 2 * NL_DP * 4));
-    int nwg = nl_bwd_wgs(V);        // the scratch holds this many partials: an upper bound for the grid
-#define SCR_NL_RED(NN)                                                                              \
-    case NN:                                                                                        \
-        nwg = min(nwg, nl_resident_wgs(nl_bwd_reduce_kernel<NN>, 256, 768));                        \
-        nl_bwd_reduce_kernel<NN><<<nwg, 256, 0, st>>>(V, d, x, ldx, dy, lddy, bpart);               \
-        break;
-    switch ((d + 15) / 16) { SCR_NL_RED(1) SCR_NL_RED(2) SCR_NL_RED(3) SCR_NL_RED(4) SCR_NL_RED(5) }
-#undef SCR_NL_RED
-    nl_bwd_sum_kernel<<<(NL_HSIZE + 31) / 32, 256, 0, st>>>(nwg, bpart, coef);
-    nl_bwd_finish_kernel<<<1, 128, 0, st>>>(V, d, G, mean, inv, coef, dG, dc);
-    static_assert(NLC_K0 == NLC_GI + NL_OUT * NL_DP && NLC_K1 == NLC_K0 + NL_DP, "Gi | k0 | k1 are contiguous");
-    if (coef_out && hipMemcpyAsync(coef_out, coef + NLC_GI, (size_t)(NL_OUT + 2) * NL_DP * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return 3;
-    if (!dx) return 0;
-    const bool al = ldx % 4 == 0 && lddx % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dx & 15) == 0;
-#define SCR_NL_DX(NN)                                                                                                                          \
-    case NN:                                                                                                                                   \
-        if (al) nl_bwd_dx_kernel<NN, true><<<nl_grid(V, nl_bwd_dx_kernel<NN, true>), 256, 0, st>>>(V, d, x, ldx, dy, lddy, coef, dx, lddx);     \
-        else nl_bwd_dx_kernel<NN, false><<<nl_grid(V, nl_bwd_dx_kernel<NN, false>), 256, 0, st>>>(V, d, x, ldx, dy, lddy, coef, dx, lddx);      \
-        break;
-    switch ((d + 15) / 16) { SCR_NL_DX(1) SCR_NL_DX(2) SCR_NL_DX(3) SCR_NL_DX(4) SCR_NL_DX(5) }
-#undef SCR_NL_DX
-    return 0;
-}
-
-// Pass 3 on its own, from a coefficient block a previous launch_norm_linear_backward(coef_out) left (Gi | k0 | k1): for the
-// consumer of those coefficients that finds it cannot form the rows itself after all (layout outside its fused pass).
-int launch_norm_linear_dx(int64_t V, int d, const float* x, int ldx, const float* dy, int lddy, const float* coef3, float* dx,
-                          int lddx, hipStream_t st) {
-    if (d < 1 || d > NL_DP) return 1;
-    if (lddy % 4 != 0 || ((uintptr_t)dy & 15) != 0) return 2;
-    const float* coef = coef3 - NLC_GI;          // the kernel reads coef + NLC_GI / NLC_K0 / NLC_K1 only: contiguous, in this order
-    const bool al = ldx % 4 == 0 && lddx % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dx & 15) == 0;
-#define SCR_NL_DX(NN)                                                                                                                          \
-    case NN:                                                                                                                                   \
-        if (al) nl_bwd_dx_kernel<NN, true><<<nl_grid(V, nl_bwd_dx_kernel<NN, true>), 256, 0, st>>>(V, d, x, ldx, dy, lddy, coef, dx, lddx);     \
-        else nl_bwd_dx_kernel<NN, false><<<nl_grid(V, nl_bwd_dx_kernel<NN, false>), 256, 0, st>>>(V, d, x, ldx, dy, lddy, coef, dx, lddx);      \
-        break;
-    switch ((d + 15) / 16) { SCR_NL_DX(1) SCR_NL_DX(2) SCR_NL_DX(3) SCR_NL_DX(4) SCR_NL_DX(5) }
-#undef SCR_NL_DX
-    return 0;
-}
-
 // ------------------------------------------------------------------ folding the BatchNorm / Linear parameters
 // FeaturePlanes sums L <= 4 pairs Linear_i(BatchNorm_i(.)) over its active levels.  With batch statistics the pairs fold
 // into ONE weight matrix G [32, d] and one bias c [32] (scene_model._norm_linear):
@@ -612,52 +520,196 @@ static bool nl_set_perm(unsigned char (&at)[NL_DP], int d, const unsigned char* 
     return true;
 }
 
-int launch_nl_fold(int L, int d, const int* dd, const int* col, const unsigned char* col_at, const float* const* W,
-                   const float* const* b, const float* const* gamma, const float* const* beta, float* G, float* c,
-                   hipStream_t st) {
-    if (L < 1 || L > 4 || d < 1 || d > NL_DP) return 1;
-    NlFoldArgs a = {};
-    a.L = L; a.d = d;
-    if (!nl_set_perm(a.at, d, col_at)) return 1;
-    for (int i = 0; i < L; ++i) {
-        if (dd[i] < 1 || col[i] < 0 || col[i] + dd[i] > d) return 1;
-        a.dd[i] = dd[i]; a.col[i] = col[i]; a.W[i] = W[i]; a.b[i] = b[i]; a.gamma[i] = gamma[i]; a.beta[i] = beta[i];
-    }
-    nl_fold_kernel<<<(32 * d + 255) / 256, 256, 0, st>>>(a, G, c);
-    return 0;
-}
-
-int launch_nl_fold_backward(int L, int d, const int* dd, const int* col, const unsigned char* col_at, const float* const* W,
-                            const float* const* gamma, const float* const* beta, const float* dG, const float* dc,
-                            float* const* dW, float* const* db, float* const* dgamma, float* const* dbeta, hipStream_t st) {
-    if (L < 1 || L > 4 || d < 1 || d > NL_DP) return 1;
-    NlFoldArgs a = {};
-    a.L = L; a.d = d;
-    if (!nl_set_perm(a.at, d, col_at)) return 1;
-    for (int i = 0; i < L; ++i) {
-        if (dd[i] < 1 || col[i] < 0 || col[i] + dd[i] > d) return 1;
-        a.dd[i] = dd[i]; a.col[i] = col[i]; a.W[i] = W[i]; a.gamma[i] = gamma[i]; a.beta[i] = beta[i];
-        a.dW[i] = dW[i]; a.db[i] = db[i]; a.dgamma[i] = dgamma[i]; a.dbeta[i] = dbeta[i];
-    }
-    nl_fold_backward_kernel<<<dim3((32 * d + 255) / 256, L), 256, 0, st>>>(a, dG, dc);
-    return 0;
-}
-
-int launch_nl_running_stats(int L, int d, const int* dd, const int* col, const unsigned char* col_at, const float* momentum,
-                            float* const* run_mean, float* const* run_var, long long* const* batches, const float* mean,
-                            const float* var, int64_t n, hipStream_t st) {
-    if (L < 1 || L > 4 || d < 1 || d > NL_DP) return 1;
-    NlRunArgs a = {};
-    a.L = L;
-    if (!nl_set_perm(a.at, d, col_at)) return 1;
+// the pairs' shape: 1 <= L <= 4 pairs, 1 <= d <= NL_DP columns, every column block inside [0, d); fills the permutation
+static bool nl_pairs_ok(unsigned char (&at)[NL_DP], int L, int d, const int* dd, const int* col, const unsigned char* col_at) {
+    if (L < 1 || L > 4 || d < 1 || d > NL_DP) return false;
+    if (!nl_set_perm(at, d, col_at)) return false;
     for (int i = 0; i < L; ++i)
-        if (dd[i] < 1 || col[i] < 0 || col[i] + dd[i] > d) return 1;
-    for (int i = 0; i < L; ++i) {
-        a.dd[i] = dd[i]; a.col[i] = col[i]; a.momentum[i] = momentum[i];
-        a.run_mean[i] = run_mean[i]; a.run_var[i] = run_var[i]; a.batches[i] = batches ? batches[i] : nullptr;
-    }
-    nl_running_stats_kernel<<<1, 256, 0, st>>>(a, mean, var, (float)((double)n / (double)(n > 1 ? n - 1 : 1)));
-    return 0;
+        if (dd[i] < 1 || col[i] < 0 || col[i] + dd[i] > d) return false;
+    return true;
+}
+
+// pass 3 of the backward: dx from the coefficient block (reads coef + NLC_GI / NLC_K0 / NLC_K1 only)
+static void nl_launch_dx(int64_t V, int d, const float* x, int ldx, const float* dy, int lddy, const float* coef, float* dx, int lddx,
+                         hipStream_t st) {
+    const bool al = ldx % 4 == 0 && lddx % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dx & 15) == 0;
+#define SCR_NL_DX(NN)                                                                                                                          \
+    case NN:                                                                                                                                   \
+        if (al) nl_bwd_dx_kernel<NN, true><<<nl_grid(V, nl_bwd_dx_kernel<NN, true>), 256, 0, st>>>(V, d, x, ldx, dy, lddy, coef, dx, lddx);     \
+        else nl_bwd_dx_kernel<NN, false><<<nl_grid(V, nl_bwd_dx_kernel<NN, false>), 256, 0, st>>>(V, d, x, ldx, dy, lddy, coef, dx, lddx);      \
+        break;
+    switch ((d + 15) / 16) { SCR_NL_DX(1) SCR_NL_DX(2) SCR_NL_DX(3) SCR_NL_DX(4) SCR_NL_DX(5) }
+#undef SCR_NL_DX
 }
 
 }  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+// ---- the parameter side of the fold: G, c from the pairs' weights, their gradients back, running statistics
+int scr_norm_fold(int32_t L, int32_t d, const int32_t* widths_host, const int32_t* cols_host, const uint8_t* col_at_host,
+                  const void* const* lin_weight_host,
+                  const void* const* lin_bias_host, const void* const* bn_weight_host, const void* const* bn_bias_host, float* G,
+                  float* c, void* stream) {
+    SCR_MARK_FN;
+    if (!widths_host || !cols_host || !lin_weight_host || !lin_bias_host || !bn_weight_host || !bn_bias_host || !G || !c)
+        return fail("NULL argument");
+    NlFoldArgs a = {};
+    if (!nl_pairs_ok(a.at, L, d, widths_host, cols_host, col_at_host))
+        return fail("scr_norm_fold: 1 <= L <= 4 pairs, column blocks inside [0, d), d <= 80, col_at a permutation of 0 .. d-1");
+    a.L = L; a.d = d;
+    for (int i = 0; i < L; ++i) {
+        a.dd[i] = widths_host[i]; a.col[i] = cols_host[i];
+        a.W[i] = (const float*)lin_weight_host[i]; a.b[i] = (const float*)lin_bias_host[i];
+        a.gamma[i] = (const float*)bn_weight_host[i]; a.beta[i] = (const float*)bn_bias_host[i];
+    }
+    nl_fold_kernel<<<(32 * d + 255) / 256, 256, 0, (hipStream_t)stream>>>(a, G, c);
+    CHECK_LAUNCH("nl_fold_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+int scr_norm_fold_backward(int32_t L, int32_t d, const int32_t* widths_host, const int32_t* cols_host, const uint8_t* col_at_host,
+                           const void* const* lin_weight_host, const void* const* bn_weight_host, const void* const* bn_bias_host,
+                           const float* dG, const float* dc, void* const* d_lin_weight_host, void* const* d_lin_bias_host,
+                           void* const* d_bn_weight_host, void* const* d_bn_bias_host, void* stream) {
+    SCR_MARK_FN;
+    if (!widths_host || !cols_host || !lin_weight_host || !bn_weight_host || !bn_bias_host || !dG || !dc || !d_lin_weight_host ||
+        !d_lin_bias_host || !d_bn_weight_host || !d_bn_bias_host)
+        return fail("NULL argument");
+    NlFoldArgs a = {};
+    if (!nl_pairs_ok(a.at, L, d, widths_host, cols_host, col_at_host))
+        return fail("scr_norm_fold_backward: 1 <= L <= 4 pairs, column blocks inside [0, d), d <= 80");
+    a.L = L; a.d = d;
+    for (int i = 0; i < L; ++i) {
+        a.dd[i] = widths_host[i]; a.col[i] = cols_host[i];
+        a.W[i] = (const float*)lin_weight_host[i]; a.gamma[i] = (const float*)bn_weight_host[i]; a.beta[i] = (const float*)bn_bias_host[i];
+        a.dW[i] = (float*)d_lin_weight_host[i]; a.db[i] = (float*)d_lin_bias_host[i];
+        a.dgamma[i] = (float*)d_bn_weight_host[i]; a.dbeta[i] = (float*)d_bn_bias_host[i];
+    }
+    nl_fold_backward_kernel<<<dim3((32 * d + 255) / 256, L), 256, 0, (hipStream_t)stream>>>(a, dG, dc);
+    CHECK_LAUNCH("nl_fold_backward_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+int scr_norm_running_stats(int32_t L, int32_t d, const int32_t* widths_host, const int32_t* cols_host, const uint8_t* col_at_host,
+                           const float* momentum_host,
+                           void* const* running_mean_host, void* const* running_var_host, void* const* num_batches_host,
+                           const float* mean, const float* var, int64_t n, void* stream) {
+    SCR_MARK_FN;
+    if (!widths_host || !cols_host || !momentum_host || !running_mean_host || !running_var_host || !mean || !var)
+        return fail("NULL argument");
+    NlRunArgs a = {};
+    if (!nl_pairs_ok(a.at, L, d, widths_host, cols_host, col_at_host)) return fail("scr_norm_running_stats: 1 <= L <= 4");
+    a.L = L;
+    for (int i = 0; i < L; ++i) {
+        a.dd[i] = widths_host[i]; a.col[i] = cols_host[i]; a.momentum[i] = momentum_host[i];
+        a.run_mean[i] = (float*)running_mean_host[i]; a.run_var[i] = (float*)running_var_host[i];
+        a.batches[i] = num_batches_host ? (long long*)num_batches_host[i] : nullptr;
+    }
+    nl_running_stats_kernel<<<1, 256, 0, (hipStream_t)stream>>>(a, mean, var, (float)((double)n / (double)(n > 1 ? n - 1 : 1)));
+    CHECK_LAUNCH("nl_running_stats_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+// ---- BatchNorm1d (batch statistics) folded into Linear(d, 32)
+size_t scr_norm_linear_scratch_bytes(int64_t V) {
+    if (V < 1) V = 1;
+    return align_up((size_t)NLC_END * 4) + align_up((size_t)nl_stat_wgs(V) * 2 * NL_DP * 4) +
+           align_up((size_t)nl_bwd_wgs(V) * NL_HSIZE * 4);
+}
+
+// col_stats (may be NULL): column statistics the PRODUCER of x already formed -- col_stat_rows rows of [2][NL_DP] floats, sums
+// of (x - x[0]) and (x - x[0])^2 over disjoint sets of rows that cover x (the anchor gather holds every 64 rows of its matrix
+// in LDS anyway: csrc/anchor_gather.hip) -- then the statistics pass over x (1.3 GB at configs[2]) is skipped.
+int scr_norm_linear_forward(int64_t V, int32_t d, const float* x, int32_t ldx, const float* G, const float* c, float eps,
+                            float* y, float* mean, float* var, float* inv, void* scratch, const float* col_stats,
+                            int32_t col_stat_rows, void* stream) {
+    SCR_MARK_FN;
+    if (V < 1 || d < 1 || ldx < d) return fail("bad sizes");
+    if ((col_stats != nullptr) != (col_stat_rows > 0)) return fail("col_stats and col_stat_rows go together (NULL / 0: the statistics pass runs here)");
+    if (!x || !G || !c || !y || !mean || !var || !inv || !scratch) return fail("NULL argument");
+    if (d > NL_DP) return fail("d = %d input columns exceed the supported 80", d);
+    hipStream_t st = (hipStream_t)stream;
+    float* coef = (float*)scratch;
+    float* spart = (float*)((char*)scratch + align_up((size_t)NLC_END * 4));
+    { ProfScope ps_(SCR_PROF_NORM_LINEAR, st);
+      if (col_stats && col_stat_rows > 0) {
+          nl_stats_finish_kernel<<<1, 1024, 0, st>>>(V, d, col_stat_rows, x, col_stats, G, c, eps, mean, var, inv, coef);
+      } else {
+          // slabs of 2048 rows until they are more than the chip holds at once (8 workgroups per CU), then one round of larger
+          // slabs: 2246 workgroups on 2048 places ran a second round at a tenth of the machine, and the single-workgroup finish
+          // kernel read 9 k partials at 18 M rows
+          const int resident = d <= 64 ? nl_resident_wgs(nl_stats_partial_kernel<64>, 256, 2048) : nl_resident_wgs(nl_stats_partial_kernel<128>, 256, 2048);
+          int64_t slab = NL_SLAB;
+          if ((V + slab - 1) / slab > resident) slab = ((V + resident - 1) / resident + 7) / 8 * 8;
+          const int nwg = (int)((V + slab - 1) / slab);          // <= nl_stat_wgs(V): the scratch holds it
+          if (d <= 64) nl_stats_partial_kernel<64><<<nwg, 256, 0, st>>>(V, d, (int)slab, x, ldx, spart);
+          else nl_stats_partial_kernel<128><<<nwg, 256, 0, st>>>(V, d, (int)slab, x, ldx, spart);
+          nl_stats_finish_kernel<<<1, 1024, 0, st>>>(V, d, nwg, x, spart, G, c, eps, mean, var, inv, coef);
+      }
+      const bool al = ldx % 4 == 0 && ((uintptr_t)x & 15) == 0;
+#define SCR_NL_FWD(QQ)                                                                                                              \
+    case QQ:                                                                                                                        \
+        if (al) nl_forward_kernel<QQ, true><<<nl_grid(V, nl_forward_kernel<QQ, true>), 256, 0, st>>>(V, d, x, ldx, coef, y);        \
+        else nl_forward_kernel<QQ, false><<<nl_grid(V, nl_forward_kernel<QQ, false>), 256, 0, st>>>(V, d, x, ldx, coef, y);         \
+        break;
+      switch ((d + 15) / 16) { SCR_NL_FWD(1) SCR_NL_FWD(2) SCR_NL_FWD(3) SCR_NL_FWD(4) SCR_NL_FWD(5) }
+#undef SCR_NL_FWD
+    }
+    CHECK_LAUNCH("norm_linear_forward", 0, st);
+    return 0;
+}
+
+// coef_out (may be NULL): the coefficients of pass 3 -- Gi [32][NL_DP] | k0 [NL_DP] | k1 [NL_DP], contiguous -- copied out for a
+// consumer that forms the rows of dx itself (csrc/anchor_gather.hip, csrc/triplane.hip pass 3); with dx == NULL pass 3 is
+// not run here at all.
+int scr_norm_linear_backward(int64_t V, int32_t d, const float* x, int32_t ldx, const float* dy, int32_t lddy, const float* G,
+                             const float* mean, const float* inv, float* dx, int32_t lddx, float* dG, float* dc,
+                             void* scratch, float* coef_out, void* stream) {
+    SCR_MARK_FN;
+    if (V < 1 || d < 1 || ldx < d || lddy < 32 || (dx && lddx < d)) return fail("bad sizes");
+    if (!x || !dy || !G || !mean || !inv || !dG || !dc || !scratch) return fail("NULL argument");
+    if (d > NL_DP) return fail("d = %d input columns exceed the supported 80", d);
+    if (lddy % 4 != 0 || ((uintptr_t)dy & 15) != 0) return fail("dy must be 16-byte aligned with a row stride that is a multiple of 4 floats");
+    hipStream_t st = (hipStream_t)stream;
+    float* coef = (float*)scratch;
+    float* bpart = (float*)((char*)scratch + align_up((size_t)NLC_END * 4) + align_up((size_t)nl_stat_wgs(V) * 2 * NL_DP * 4));
+    int nwg = nl_bwd_wgs(V);        // the scratch holds this many partials: an upper bound for the grid
+    { ProfScope ps_(SCR_PROF_NORM_LINEAR_BACKWARD, st);
+#define SCR_NL_RED(NN)                                                                              \
+    case NN:                                                                                        \
+        nwg = min(nwg, nl_resident_wgs(nl_bwd_reduce_kernel<NN>, 256, 768));                        \
+        nl_bwd_reduce_kernel<NN><<<nwg, 256, 0, st>>>(V, d, x, ldx, dy, lddy, bpart);               \
+        break;
+      switch ((d + 15) / 16) { SCR_NL_RED(1) SCR_NL_RED(2) SCR_NL_RED(3) SCR_NL_RED(4) SCR_NL_RED(5) }
+#undef SCR_NL_RED
+      nl_bwd_sum_kernel<<<(NL_HSIZE + 31) / 32, 256, 0, st>>>(nwg, bpart, coef);
+      nl_bwd_finish_kernel<<<1, 128, 0, st>>>(V, d, G, mean, inv, coef, dG, dc);
+      static_assert(NLC_K0 == NLC_GI + NL_OUT * NL_DP && NLC_K1 == NLC_K0 + NL_DP, "Gi | k0 | k1 are contiguous");
+      if (coef_out && hipMemcpyAsync(coef_out, coef + NLC_GI, (size_t)(NL_OUT + 2) * NL_DP * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+          return fail("copy of the backward coefficients failed: %s", hipGetErrorString(hipGetLastError()));
+      if (dx) nl_launch_dx(V, d, x, ldx, dy, lddy, coef, dx, lddx, st);
+    }
+    CHECK_LAUNCH("norm_linear_backward", 0, st);
+    return 0;
+}
+
+// Pass 3 on its own, from a coefficient block a previous scr_norm_linear_backward(coef_out) left (Gi | k0 | k1): for the
+// consumer of those coefficients that finds it cannot form the rows itself after all (layout outside its fused pass).
+int scr_norm_linear_dx(int64_t V, int32_t d, const float* x, int32_t ldx, const float* dy, int32_t lddy, const float* coef,
+                       float* dx, int32_t lddx, void* stream) {
+    SCR_MARK_FN;
+    if (V < 1 || d < 1 || ldx < d || lddy < 32 || lddx < d) return fail("bad sizes");
+    if (!x || !dy || !coef || !dx) return fail("NULL argument");
+    if (d > NL_DP) return fail("d = %d input columns exceed the supported 80", d);
+    if (lddy % 4 != 0 || ((uintptr_t)dy & 15) != 0) return fail("dy must be 16-byte aligned with a row stride that is a multiple of 4 floats");
+    hipStream_t st = (hipStream_t)stream;
+    { ProfScope ps_(SCR_PROF_NORM_LINEAR_BACKWARD, st);
+      nl_launch_dx(V, d, x, ldx, dy, lddy, coef - NLC_GI, dx, lddx, st); }
+    CHECK_LAUNCH("norm_linear_dx", 0, st);
+    return 0;
+}
+
+}  // extern "C"

@@ -17,7 +17,6 @@
 // Arithmetic order is normative (-ffp-contract=off): e = p_j - p_i, d = (ex*ex + ey*ey) + ez*ez, ((b0 + b1) + b2) / 3.
 // The three smallest VALUES are unique whatever the tie-breaking, so the result is independent of the search order and
 // bit-identical to a brute force.  No atomics.
-#include "compact.h"
 #include "knn_grid.h"
 
 #include <math.h>
@@ -111,13 +110,7 @@ points_bounds_final_kernel(int64_t nwg, const float* __restrict__ partial, float
     }
 }
 
-size_t points_bounds_nwg(int64_t N) { return (size_t)((N + SI_BOUNDS_PER_WG - 1) / SI_BOUNDS_PER_WG); }
-
-void launch_points_bounds(int64_t N, const float* pts, float* partial, float* out, hipStream_t st) {
-    const size_t nwg = points_bounds_nwg(N);
-    points_bounds_kernel<<<(unsigned)nwg, SI_THREADS, 0, st>>>(N, pts, partial);
-    points_bounds_final_kernel<<<1, SI_THREADS, 0, st>>>((int64_t)nwg, partial, out);
-}
+static size_t points_bounds_nwg(int64_t N) { return (size_t)((N + SI_BOUNDS_PER_WG - 1) / SI_BOUNDS_PER_WG); }
 
 // ------------------------------------------------------------------ voxel keys
 __global__ void __launch_bounds__(SI_THREADS)
@@ -160,22 +153,6 @@ voxel_unique_write_kernel(int64_t n, KeepHead head, const uint32_t* __restrict__
     }
 }
 
-void launch_voxel_keys(int64_t N, const float* pts, float v, const int32_t* lo, int packed, int64_t* out, hipStream_t st) {
-    voxel_keys_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, st>>>(N, pts, v, lo[0], lo[1], lo[2],
-                                                                                          packed, out);
-}
-
-void launch_voxel_unique_count(int64_t n, const int64_t* keys, const CompactScratch& s, unsigned long long* mailbox,
-                               unsigned long long seq, hipStream_t st) {
-    launch_compact_count(n, KeepHead{keys}, s, mailbox, seq, st);
-}
-
-void launch_voxel_unique_write(int64_t n, const int64_t* keys, const uint32_t* wg_offset, float v, const int32_t* lo,
-                               float* out, hipStream_t st) {
-    voxel_unique_write_kernel<<<(uint32_t)compact_nwg(n), COMPACT_THREADS, 0, st>>>(n, KeepHead{keys}, wg_offset, v, lo[0],
-                                                                                    lo[1], lo[2], out);
-}
-
 // ------------------------------------------------------------------ fused 3-NN mean squared distance
 __global__ void __launch_bounds__(SI_THREADS)
 knn_cell_keys_kernel(int64_t N, KnnGrid gr, const float* __restrict__ pts, int64_t* __restrict__ keys) {
@@ -211,14 +188,90 @@ knn3_dist2_kernel(int64_t N, KnnGrid gr, const float* __restrict__ sorted_pts, c
     out[sorted_id[s]] = ((best.b0 + best.b1) + best.b2) / 3.0f;
 }
 
-void launch_knn_cell_keys(int64_t N, const float* grid8, const float* pts, int64_t* keys, hipStream_t st) {
-    knn_cell_keys_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, st>>>(N, knn_grid(grid8), pts, keys);
-}
-
-void launch_knn3_dist2(int64_t N, const float* grid8, const float* sorted_pts, const int64_t* sorted_id,
-                       const int32_t* cell_start, float* out, hipStream_t st) {
-    knn3_dist2_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, st>>>(N, knn_grid(grid8), sorted_pts,
-                                                                                         sorted_id, cell_start, out);
+static int check_voxel_args(const char* who, int64_t N, float voxel_size, const int32_t* lo_host) {
+    if (N <= 0 || N >= (1ll << 31)) return fail("%s: need 0 < N < 2^31", who);
+    if (!(voxel_size > 0.0f) || !(voxel_size <= 3.0e38f)) return fail("%s: voxel_size must be positive and finite", who);
+    if (!lo_host) return fail("%s: lo_host is NULL", who);
+    return 0;
 }
 
 }  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+size_t scr_voxel_unique_scratch_bytes(int64_t N) { return compact_scratch_bytes(N > 0 ? N : 1); }
+
+size_t scr_points_bounds_scratch_bytes(int64_t N) { return align_up(points_bounds_nwg(N > 0 ? N : 1) * 8 * sizeof(float)); }
+
+int scr_points_bounds(int64_t N, const float* points, void* scratch, float* out7, void* stream) {
+    SCR_MARK_FN;
+    if (N <= 0 || N >= (1ll << 31)) return fail("scr_points_bounds: need 0 < N < 2^31");
+    if (!points || !scratch || !out7) return fail("scr_points_bounds: NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t nwg = points_bounds_nwg(N);
+    points_bounds_kernel<<<(unsigned)nwg, SI_THREADS, 0, st>>>(N, points, (float*)scratch);
+    points_bounds_final_kernel<<<1, SI_THREADS, 0, st>>>((int64_t)nwg, (float*)scratch, out7);
+    CHECK_LAUNCH("points_bounds_kernel", 0, st);
+    return 0;
+}
+
+int scr_voxel_keys(int64_t N, const float* points, float voxel_size, const int32_t* lo_host, int32_t packed, int64_t* out,
+                   void* stream) {
+    SCR_MARK_FN;
+    if (check_voxel_args("scr_voxel_keys", N, voxel_size, lo_host)) return 1;
+    if (!points || !out) return fail("scr_voxel_keys: NULL argument");
+    voxel_keys_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, (hipStream_t)stream>>>(
+        N, points, voxel_size, lo_host[0], lo_host[1], lo_host[2], packed != 0, out);
+    CHECK_LAUNCH("voxel_keys_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+int scr_voxel_unique_plan(int64_t N, const int64_t* sorted_keys, void* scratch, int64_t* num_unique_host, void* stream) {
+    SCR_MARK_FN;
+    if (!num_unique_host) return fail("num_unique_host is NULL");
+    *num_unique_host = 0;
+    if (N <= 0 || N >= (1ll << 31)) return fail("scr_voxel_unique_plan: need 0 < N < 2^31");
+    if (!sorted_keys || !scratch) return fail("scr_voxel_unique_plan: NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    return compact_plan("compact_count_kernel<KeepHead>", N, scratch, num_unique_host, st,
+                        [&](const CompactScratch& s, unsigned long long* mb, unsigned long long seq) {
+                            launch_compact_count(N, KeepHead{sorted_keys}, s, mb, seq, st);
+                        });
+}
+
+int scr_voxel_unique_run(int64_t N, const int64_t* sorted_keys, const void* scratch, float voxel_size,
+                         const int32_t* lo_host, float* out_xyz, void* stream) {
+    SCR_MARK_FN;
+    if (check_voxel_args("scr_voxel_unique_run", N, voxel_size, lo_host)) return 1;
+    if (!sorted_keys || !scratch || !out_xyz) return fail("scr_voxel_unique_run: NULL argument");
+    voxel_unique_write_kernel<<<(uint32_t)compact_nwg(N), COMPACT_THREADS, 0, (hipStream_t)stream>>>(
+        N, KeepHead{sorted_keys}, (const uint32_t*)scratch, voxel_size, lo_host[0], lo_host[1], lo_host[2], out_xyz);
+    CHECK_LAUNCH("voxel_unique_write_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+int scr_knn_cell_keys(int64_t N, const float* grid_host, const float* points, int64_t* keys, void* stream) {
+    SCR_MARK_FN;
+    if (check_knn_grid("scr_knn_cell_keys", N, grid_host)) return 1;
+    if (!points || !keys) return fail("scr_knn_cell_keys: NULL argument");
+    knn_cell_keys_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, (hipStream_t)stream>>>(
+        N, knn_grid(grid_host), points, keys);
+    CHECK_LAUNCH("knn_cell_keys_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+int scr_knn3_dist2(int64_t N, const float* grid_host, const float* sorted_pts, const int64_t* sorted_id,
+                   const int32_t* cell_start, float* out, void* stream) {
+    SCR_MARK_FN;
+    if (check_knn_grid("scr_knn3_dist2", N, grid_host)) return 1;
+    if (N < 4) return fail("scr_knn3_dist2: fewer than 4 points");
+    if (!sorted_pts || !sorted_id || !cell_start || !out) return fail("scr_knn3_dist2: NULL argument");
+    knn3_dist2_kernel<<<(unsigned)((N + SI_THREADS - 1) / SI_THREADS), SI_THREADS, 0, (hipStream_t)stream>>>(
+        N, knn_grid(grid_host), sorted_pts, sorted_id, cell_start, out);
+    CHECK_LAUNCH("knn3_dist2_kernel", 0, (hipStream_t)stream);
+    return 0;
+}
+
+}  // extern "C"

@@ -12,6 +12,7 @@
 //   mu1 = G*x, mu2 = G*y, E11 = G*x^2, E22 = G*y^2, E12 = G*xy
 //   ssim = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2)),  s.. = E.. - mu mu
 //   dL/dx(p) = sum_q G(q-p) [ dmu1(q) + 2 x(p) dE11(q) + y(p) dE12(q) ]
+#include "capi.h"
 #include "wg.h"
 
 namespace scr {
@@ -164,30 +165,6 @@ static SsimWindow make_window() {
     return w;
 }
 
-size_t l1_ssim_scratch_bytes(int C, int H, int W, int with_grad) {
-    const size_t nb = (size_t)((W + SS_T - 1) / SS_T) * ((H + SS_T - 1) / SS_T) * C;
-    return align_up(nb * sizeof(float2)) + (with_grad ? align_up((size_t)3 * C * H * W * 4) : 0);
-}
-
-void launch_l1_ssim_forward(int C, int H, int W, const float* img1, const float* img2, void* scratch,
-                            int with_grad, float* out2, hipStream_t st) {
-    const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C);
-    const size_t nb = (size_t)grid.x * grid.y * grid.z;
-    float2* partial = (float2*)scratch;
-    float* dmaps = with_grad ? (float*)((char*)scratch + align_up(nb * sizeof(float2))) : nullptr;
-    l1_ssim_forward_kernel<<<grid, 256, 0, st>>>(H, W, img1, img2, make_window(), dmaps, partial);
-    l1_ssim_reduce_kernel<<<1, 1024, 0, st>>>((int)nb, partial, 1.0 / ((double)C * H * W), out2);
-}
-
-void launch_l1_ssim_backward(int C, int H, int W, const float* img1, const float* img2, const void* scratch,
-                             const float* g_l1, const float* g_ssim, float* dimg1, hipStream_t st) {
-    const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C);
-    const size_t nb = (size_t)grid.x * grid.y * grid.z;
-    const float* dmaps = (const float*)((const char*)scratch + align_up(nb * sizeof(float2)));
-    l1_ssim_backward_kernel<<<grid, 256, 0, st>>>(H, W, img1, img2, make_window(), dmaps, g_l1, g_ssim,
-                                                  (float)(1.0 / ((double)C * H * W)), dimg1);
-}
-
 // ------------------------------------------------------------------ scaling regulariser of the per-view loss
 // mean_p(s[p,0] s[p,1] s[p,2]) (train.py:192-196: scaling.prod(dim=1).mean()) and its gradient.  torch's prod backward
 // counts the zeros of its input first -- a compare, an int64 reduction at 60 GB/s and a host read -- before a division
@@ -248,26 +225,111 @@ pair_l1_backward_kernel(int64_t n, const float* __restrict__ g1, const float* __
     if (d1) d1[e] = -sg * w;
     if (d2) d2[e] = sg * w;
 }
-size_t pair_l1_scratch_bytes(int64_t n) { return align_up((size_t)((n + PL1_PER_WG - 1) / PL1_PER_WG + 1) * 8); }
-void launch_pair_l1_forward(int64_t n, const float* g1, const float* g2, const float* r1, const float* r2, void* scratch, float* out,
-                            hipStream_t st) {
-    const int nb = (int)((n + PL1_PER_WG - 1) / PL1_PER_WG);
-    pair_l1_partial_kernel<<<nb, 256, 0, st>>>(n, g1, g2, r1, r2, (double*)scratch);
-    scaling_reg_finish_kernel<<<1, 1024, 0, st>>>(nb, (const double*)scratch, 1.0 / (double)n, out);
-}
-void launch_pair_l1_backward(int64_t n, const float* g1, const float* g2, const float* r1, const float* r2, const float* g, float* d1,
-                             float* d2, hipStream_t st) {
-    pair_l1_backward_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, g1, g2, r1, r2, g, (float)(1.0 / (double)n), d1, d2);
-}
-
-size_t scaling_reg_scratch_bytes(int64_t P) { return align_up((size_t)((P + SREG_ROWS - 1) / SREG_ROWS + 1) * 8); }
-void launch_scaling_reg_forward(int64_t P, const float* s, void* scratch, float* out, hipStream_t st) {
-    const int nb = (int)((P + SREG_ROWS - 1) / SREG_ROWS);
-    scaling_reg_partial_kernel<<<nb, 256, 0, st>>>(P, s, (double*)scratch);
-    scaling_reg_finish_kernel<<<1, 1024, 0, st>>>(nb, (const double*)scratch, 1.0 / (double)P, out);
-}
-void launch_scaling_reg_backward(int64_t P, const float* s, const float* g, float* ds, hipStream_t st) {
-    scaling_reg_backward_kernel<<<(unsigned)((P + 255) / 256), 256, 0, st>>>(P, s, g, (float)(1.0 / (double)P), ds);
-}
 
 }  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+// ---- fused L1 + SSIM loss
+size_t scr_l1_ssim_scratch_bytes(int32_t C, int32_t H, int32_t W, int32_t with_grad) {
+    const size_t nb = (size_t)((W + SS_T - 1) / SS_T) * ((H + SS_T - 1) / SS_T) * C;
+    return align_up(nb * sizeof(float2)) + (with_grad ? align_up((size_t)3 * C * H * W * 4) : 0);
+}
+
+int scr_l1_ssim_forward(int32_t C, int32_t H, int32_t W, const float* img1, const float* img2, void* scratch,
+                        int32_t with_grad, float* out2, void* stream) {
+    SCR_MARK_FN;
+    if (C <= 0 || H <= 0 || W <= 0) return fail("bad image size");
+    if (!img1 || !img2 || !scratch || !out2) return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C);
+    const size_t nb = (size_t)grid.x * grid.y * grid.z;
+    float2* partial = (float2*)scratch;
+    float* dmaps = with_grad ? (float*)((char*)scratch + align_up(nb * sizeof(float2))) : nullptr;
+    { ProfScope ps_(SCR_PROF_L1_SSIM, st);
+      l1_ssim_forward_kernel<<<grid, 256, 0, st>>>(H, W, img1, img2, make_window(), dmaps, partial);
+      l1_ssim_reduce_kernel<<<1, 1024, 0, st>>>((int)nb, partial, 1.0 / ((double)C * H * W), out2); }
+    CHECK_LAUNCH("l1_ssim_forward_kernel", 0, st);
+    return 0;
+}
+
+int scr_l1_ssim_backward(int32_t C, int32_t H, int32_t W, const float* img1, const float* img2,
+                         const void* scratch, const float* g_l1, const float* g_ssim, float* dimg1,
+                         void* stream) {
+    SCR_MARK_FN;
+    if (C <= 0 || H <= 0 || W <= 0) return fail("bad image size");
+    if (!img1 || !img2 || !scratch || !g_l1 || !g_ssim || !dimg1) return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C);
+    const size_t nb = (size_t)grid.x * grid.y * grid.z;
+    const float* dmaps = (const float*)((const char*)scratch + align_up(nb * sizeof(float2)));
+    { ProfScope ps_(SCR_PROF_L1_SSIM_BACKWARD, st);
+      l1_ssim_backward_kernel<<<grid, 256, 0, st>>>(H, W, img1, img2, make_window(), dmaps, g_l1, g_ssim,
+                                                    (float)(1.0 / ((double)C * H * W)), dimg1); }
+    CHECK_LAUNCH("l1_ssim_backward_kernel", 0, st);
+    return 0;
+}
+
+// ---- scaling regulariser of the per-view loss
+size_t scr_scaling_reg_scratch_bytes(int64_t P) { return align_up((size_t)((P + SREG_ROWS - 1) / SREG_ROWS + 1) * 8); }
+
+int scr_scaling_reg_forward(int64_t P, const float* scaling, void* scratch, float* out, void* stream) {
+    SCR_MARK_FN;
+    if (P <= 0) return fail("P <= 0");
+    if (!scaling || !scratch || !out) return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = (int)((P + SREG_ROWS - 1) / SREG_ROWS);
+    { ProfScope ps_(SCR_PROF_L1_SSIM, st);
+      scaling_reg_partial_kernel<<<nb, 256, 0, st>>>(P, scaling, (double*)scratch);
+      scaling_reg_finish_kernel<<<1, 1024, 0, st>>>(nb, (const double*)scratch, 1.0 / (double)P, out); }
+    CHECK_LAUNCH("scaling_reg_partial_kernel", 0, st);
+    return 0;
+}
+
+int scr_scaling_reg_backward(int64_t P, const float* scaling, const float* g, float* dscaling, void* stream) {
+    SCR_MARK_FN;
+    if (P <= 0) return fail("P <= 0");
+    if (!scaling || !g || !dscaling) return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    { ProfScope ps_(SCR_PROF_L1_SSIM_BACKWARD, st);
+      scaling_reg_backward_kernel<<<(unsigned)((P + 255) / 256), 256, 0, st>>>(P, scaling, g, (float)(1.0 / (double)P), dscaling); }
+    CHECK_LAUNCH("scaling_reg_backward_kernel", 0, st);
+    return 0;
+}
+
+// ---- the L1 of the cross-view consistency term
+size_t scr_pair_l1_scratch_bytes(int64_t n) {
+    if (n < 1) n = 1;
+    return align_up((size_t)((n + PL1_PER_WG - 1) / PL1_PER_WG + 1) * 8);
+}
+
+int scr_pair_l1_forward(int64_t n, const float* gen1, const float* gen2, const float* real1, const float* real2, void* scratch,
+                        float* out, void* stream) {
+    SCR_MARK_FN;
+    if (n <= 0) return fail("n <= 0");
+    if (!gen1 || !gen2 || !real1 || !real2 || !scratch || !out) return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = (int)((n + PL1_PER_WG - 1) / PL1_PER_WG);
+    { ProfScope ps_(SCR_PROF_L1_SSIM, st);
+      pair_l1_partial_kernel<<<nb, 256, 0, st>>>(n, gen1, gen2, real1, real2, (double*)scratch);
+      scaling_reg_finish_kernel<<<1, 1024, 0, st>>>(nb, (const double*)scratch, 1.0 / (double)n, out); }
+    CHECK_LAUNCH("pair_l1_partial_kernel", 0, st);
+    return 0;
+}
+
+int scr_pair_l1_backward(int64_t n, const float* gen1, const float* gen2, const float* real1, const float* real2, const float* g,
+                         float* d_gen1, float* d_gen2, void* stream) {
+    SCR_MARK_FN;
+    if (n <= 0) return fail("n <= 0");
+    if (!gen1 || !gen2 || !real1 || !real2 || !g) return fail("NULL argument");
+    if (!d_gen1 && !d_gen2) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    { ProfScope ps_(SCR_PROF_L1_SSIM_BACKWARD, st);
+      pair_l1_backward_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, gen1, gen2, real1, real2, g, (float)(1.0 / (double)n), d_gen1, d_gen2); }
+    CHECK_LAUNCH("pair_l1_backward_kernel", 0, st);
+    return 0;
+}
+
+}  // extern "C"

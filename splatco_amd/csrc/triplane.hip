@@ -23,7 +23,7 @@
 // A crowded tile (a flat or contracted scene) is cut into segments, one workgroup each (tp_scan_proj, tp_split_finish_kernel).
 // Round 1 kept an index list per tile and gathered coordinates and gradients through it (0.43 ms per plane at
 // 4.6 M points, 5.2 ms per cfg2 step); records + one pass per grid + cell-centred sums: 3.2 ms per step.
-#include "common.h"
+#include "capi.h"
 #include <type_traits>
 
 namespace scr {
@@ -158,7 +158,7 @@ __device__ __forceinline__ void tp_flush_max(const TpProjSetT<N>& ps, const uint
 
 // A point's coordinate columns for the count kernel.  The per-grid path reads coords[i * cs + c] per projection: any
 // column pair of any row stride (plane_sample: cs = 2, columns 0 and 1).  The nine-projection sets sample columns 0..2
-// of rows with cs >= 3 (launch_triplane_backward_multi), and their count kernel keeps what tp_count9_kernel did: the row
+// of rows with cs >= 3 (scr_triplane_backward_multi), and their count kernel keeps what tp_count9_kernel did: the row
 // is loaded once and the columns are picked from registers (3 loads per point instead of 18).  NOT MEASURED against the
 // plain form: kept because it is what the benchmark's path ran before; drop the specialisation if the plain form times
 // the same.
@@ -1051,44 +1051,6 @@ plane_row_pairs_kernel(int A, int B, const float* __restrict__ plane, float* __r
     }
 }
 
-int launch_plane_row_pairs(int R, int A, int B, const float* plane, float* pairs, hipStream_t st) {
-    if (R < 1 || R > TP_MAX_R) return 1;
-    if (A < 2) return 0;
-    const dim3 grid((unsigned)((B + 255) / 256), (unsigned)(A - 1));
-#define SCR_TP_RP(RR) case RR: plane_row_pairs_kernel<RR><<<grid, 256, 0, st>>>(A, B, plane, pairs); break;
-    switch (R) {
-        SCR_TP_RP(1) SCR_TP_RP(2) SCR_TP_RP(3) SCR_TP_RP(4) SCR_TP_RP(5) SCR_TP_RP(6) SCR_TP_RP(7) SCR_TP_RP(8)
-        SCR_TP_RP(9) SCR_TP_RP(10) SCR_TP_RP(11) SCR_TP_RP(12) SCR_TP_RP(13) SCR_TP_RP(14) SCR_TP_RP(15) SCR_TP_RP(16)
-    }
-#undef SCR_TP_RP
-    return 0;
-}
-
-int launch_triplane_forward(int64_t V, const float* coords, int cs, const float* xy, const float* xz, const float* yz,
-                            int R, int X, int Y, int Z, int channel_last, float* out, int ld, int col_xy, int col_xz,
-                            int col_yz, hipStream_t st) {
-    if (R > TP_MAX_R) return 1;
-    if (V <= 0) return 0;
-    const unsigned nb = (unsigned)((V + 255) / 256);
-#define SCR_TP_FWD(RR)                                                                                          \
-    case RR:                                                                                                    \
-        if (channel_last == 2)                                                                                  \
-            triplane_forward_kernel<RR, 2><<<nb, 256, 0, st>>>(V, coords, cs, xy, xz, yz, X, Y, Z, out, ld, col_xy,      \
-                                                               col_xz, col_yz);                                  \
-        else if (channel_last)                                                                                  \
-            triplane_forward_kernel<RR, 1><<<nb, 256, 0, st>>>(V, coords, cs, xy, xz, yz, X, Y, Z, out, ld, col_xy,      \
-                                                               col_xz, col_yz);                                  \
-        else                                                                                                    \
-            triplane_forward_kernel<RR, 0><<<nb, 256, 0, st>>>(V, coords, cs, xy, xz, yz, X, Y, Z, out, ld, col_xy,      \
-                                                               col_xz, col_yz);                                  \
-        break;
-    switch (R) {
-        SCR_TP_FWD(1) SCR_TP_FWD(2) SCR_TP_FWD(3) SCR_TP_FWD(4) SCR_TP_FWD(5) SCR_TP_FWD(6) SCR_TP_FWD(7) SCR_TP_FWD(8) SCR_TP_FWD(9) SCR_TP_FWD(10) SCR_TP_FWD(11) SCR_TP_FWD(12) SCR_TP_FWD(13) SCR_TP_FWD(14) SCR_TP_FWD(15) SCR_TP_FWD(16)
-    }
-#undef SCR_TP_FWD
-    return 0;
-}
-
 static inline size_t tp_tiles(int A, int B) { return (size_t)((A + TP_TILE - 1) / TP_TILE) * ((B + TP_TILE - 1) / TP_TILE); }
 constexpr size_t TP_HEAD_ZEROED = 2, TP_HEAD_WORDS = 6;     // words per tile: count, gmax (zeroed every call) | start, cursor, seg, pfirst (+ 4), then the list of split tiles
 static inline size_t tp_proj_bytes(int64_t V, int A, int B, int channels) {
@@ -1098,12 +1060,6 @@ static inline size_t tp_proj_bytes(int64_t V, int A, int B, int channels) {
 // partial cell sums of split tiles: one block for all projections of a call (their pass-4 kernels run one after the other)
 static inline size_t tp_part_bytes(int64_t V, int channels) {
     return align_up(tp_max_split_segments(V) * 4 * (size_t)channels * TP_TILE * TP_TILE * sizeof(long long));
-}
-
-size_t triplane_scratch_bytes(int64_t V, int A, int B, int channels) { return tp_proj_bytes(V, A, B, channels) + tp_part_bytes(V, channels); }
-
-size_t triplane_backward_scratch_bytes(int64_t V, int X, int Y, int Z, int channels) {
-    return tp_proj_bytes(V, X, Y, channels) + tp_proj_bytes(V, X, Z, channels) + tp_proj_bytes(V, Y, Z, channels) + tp_part_bytes(V, channels);
 }
 
 static char* tp_carve(TpProj& pj, int64_t V, int channels, char* scratch) {
@@ -1128,6 +1084,7 @@ constexpr int TP_HIST_MAX_TILES = 16384;   // 64 KB of LDS histogram (+ 64 KB of
 // the most pass 3 asks for (hist + hmax).  Every scatter launch asks for this much, so the attribute is set at a kernel's
 // first launch on a device whatever the planes' size, and never again
 constexpr size_t TP_SCATTER_MAX_LDS = 2 * TP_HIST_MAX_TILES * 4;
+static inline bool tp_fits(int A, int B) { return tp_tiles(A, B) <= (size_t)TP_HIST_MAX_TILES; }
 
 // Fills projection pj (coordinate columns, plane size, gradient columns), carves its part of the scratch block and queues
 // what has to be zero before the passes run: its tile header (count, gmax) and its plane gradient(s) (gp1: NULL for none).
@@ -1186,28 +1143,27 @@ static void tp_backward_launch(int64_t V, const float* coords, int cs, const flo
 }
 
 // nproj projections (1, or the 3 of a grid) x `planes` (1 or 2) planes each; cols0/cols1: first gradient column of the
-// first / second plane of every projection; pairs[q] = (cx, cy) of projection q; sizes[q] = (A, B)
-static int tp_backward(int64_t V, const float* coords, int cs, int R, int planes, int nproj, const int (*pairs)[2],
+// first / second plane of every projection; pairs[q] = (cx, cy) of projection q; sizes[q] = (A, B).  The caller has checked
+// 1 <= R <= TP_MAX_R, planes 1 or 2 and tp_fits() of every projection.
+static void tp_backward(int64_t V, const float* coords, int cs, int R, int planes, int nproj, const int (*pairs)[2],
                        const int (*sizes)[2], const float* grad, int ld, const int* cols0, const int* cols1,
                        float* const* gp0, float* const* gp1, void* scratch, hipStream_t st) {
-    if (R > TP_MAX_R || R < 1 || planes < 1 || planes > 2) return 1;
     if (planes == 2 && R > 5) {          // 4 cells x 4 corners x 2R sums per thread would not fit the registers
         // one plane after the other; both passes use the same scratch (stream order serialises them)
-        const int rc = tp_backward(V, coords, cs, R, 1, nproj, pairs, sizes, grad, ld, cols0, cols0, gp0, gp0, scratch, st);
-        return rc ? rc : tp_backward(V, coords, cs, R, 1, nproj, pairs, sizes, grad, ld, cols1, cols1, gp1, gp1, scratch, st);
+        tp_backward(V, coords, cs, R, 1, nproj, pairs, sizes, grad, ld, cols0, cols0, gp0, gp0, scratch, st);
+        tp_backward(V, coords, cs, R, 1, nproj, pairs, sizes, grad, ld, cols1, cols1, gp1, gp1, scratch, st);
+        return;
     }
     TpProjSetT<3> ps;
     ps.n = nproj;
     char* sc = (char*)scratch;
     ZeroList zl;
     for (int q = 0; q < nproj; ++q)
-        if (tp_tiles(sizes[q][0], sizes[q][1]) > (size_t)TP_HIST_MAX_TILES) return 2;
-    for (int q = 0; q < nproj; ++q)
         sc = tp_setup_projection(ps.p[q], pairs[q][0], pairs[q][1], sizes[q][0], sizes[q][1], cols0[q], cols1[q], V, R, planes,
                                  gp0[q], planes == 2 ? gp1[q] : nullptr, sc, zl, st);
     launch_zero(zl, st);
     tp_close_set(ps, sc);
-    if (V <= 0) return 0;
+    if (V <= 0) return;
     auto run = [&](const TpProjSetT<3>& set, float* const* g0, float* const* g1) {
 #define SCR_TP_BWD(RR)                                                                                   \
     case RR:                                                                                             \
@@ -1219,7 +1175,7 @@ static int tp_backward(int64_t V, const float* coords, int cs, int R, int planes
     };
     if (tp_total_tiles(ps) <= TP_HIST_MAX_TILES) {
         run(ps, gp0, gp1);
-        return 0;
+        return;
     }
     for (int q = 0; q < nproj; ++q) {     // the three histograms do not fit one workgroup's LDS: one projection per pass
         TpProjSetT<3> one;
@@ -1227,112 +1183,7 @@ static int tp_backward(int64_t V, const float* coords, int cs, int R, int planes
         one.p[0] = one.p[1] = one.p[2] = ps.p[q];
         run(one, gp0 + q, gp1 + q);
     }
-    return 0;
 }
-
-// ---- all grids of a step at once (see tp_scatter9_kernel).  ngrids <= 3; grid g: R[g] channels per plane (the attention
-// grid arrives with its planes stacked), sizes X/Y/Z[g], first column col[g] of its 3 * R[g] gradient columns (xy, xz, yz
-// in this order); the columns of all grids are contiguous from col[0].  Returns 3 when the layout is not one the fused
-// pass handles (the caller falls back to one call per grid); nothing has been enqueued then.
-size_t triplane_multi_scratch_bytes(int64_t V, int ngrids, const int* R, const int* X, const int* Y, const int* Z) {
-    size_t b = 0;
-    int widest = 1;
-    for (int g = 0; g < ngrids; ++g) {
-        b += tp_proj_bytes(V, X[g], Y[g], R[g]) + tp_proj_bytes(V, X[g], Z[g], R[g]) + tp_proj_bytes(V, Y[g], Z[g], R[g]);
-        widest = R[g] > widest ? R[g] : widest;
-    }
-    return b + tp_part_bytes(V, widest);
-}
-
-// nl_coef (NULL: off): the gradient rows are formed from the BatchNorm-Linear's coefficients, its upstream gradient nl_dy
-// [V,32] and its input nl_x (the sampled matrix, same columns as grad) -- see tp_scatter9_kernel; grad may then be NULL.
-int launch_triplane_backward_multi(int64_t V, const float* coords, int cs, int ngrids, const int* R, const int* X, const int* Y,
-                                   const int* Z, const int* col, const float* grad, int ld, float* const* grad_planes,
-                                   void* scratch, const float* nl_coef, const float* nl_dy, int nl_lddy, const float* nl_x,
-                                   int nl_ldx, hipStream_t st) {
-    if (ngrids < 1 || ngrids > 3 || cs < 3) return 3;
-    if (col[0] % 4 != 0) return 3;
-    if (grad && (ld % 4 != 0 || ((uintptr_t)grad & 15) != 0)) return 3;
-    if (!grad && !nl_coef) return 3;
-    if (nl_coef && (nl_ldx % 4 != 0 || ((uintptr_t)nl_x & 15) != 0 || nl_lddy % 4 != 0 || ((uintptr_t)nl_dy & 15) != 0)) return 3;
-    for (int g = 0; g + 1 < ngrids; ++g)
-        if (col[g + 1] != col[g] + 3 * R[g]) return 3;
-    const int RA = R[0], RB = ngrids > 1 ? R[1] : 0, RC = ngrids > 2 ? R[2] : 0;
-    // the layouts of FeaturePlanes (r = channels per plane): attention grid stacked (2 r) [+ plain (r) [+ plain (r)]], or plain grids only
-    // (15: the attention grid's pair planes with the same-size plain grid's plane stacked on them, one record / gather per projection)
-    const bool known = ((RA == 10 || RA == 5) && (RB == 0 || RB == 5) && (RC == 0 || RC == 5)) || (RA == 15 && (RB == 0 || RB == 5) && RC == 0);
-    if (!known || (RC && !RB)) return 3;
-    size_t total = 0;
-    for (int g = 0; g < ngrids; ++g) total += tp_tiles(X[g], Y[g]) + tp_tiles(X[g], Z[g]) + tp_tiles(Y[g], Z[g]);
-    if (total > (size_t)TP_HIST_MAX_TILES) return 3;
-    TpProjSetT<9> ps;
-    ZeroList zl;
-    ps.n = 3 * ngrids;
-    const int pairs[3][2] = {{1, 0}, {2, 0}, {2, 1}};
-    char* sc = (char*)scratch;
-    for (int g = 0; g < ngrids; ++g) {
-        const int sizes[3][2] = {{X[g], Y[g]}, {X[g], Z[g]}, {Y[g], Z[g]}};
-        for (int q = 0; q < 3; ++q)
-            sc = tp_setup_projection(ps.p[3 * g + q], pairs[q][0], pairs[q][1], sizes[q][0], sizes[q][1], col[g] + q * R[g],
-                                     col[g] + q * R[g], V, R[g], 1, grad_planes[3 * g + q], nullptr, sc, zl, st);
-    }
-    launch_zero(zl, st);
-    tp_close_set(ps, sc);
-    if (V <= 0) return 0;
-    const unsigned nwg = (unsigned)((V + TP_PER_WG - 1) / TP_PER_WG);
-    const size_t hb = total * 4;
-    tp_count_kernel<<<nwg, TP_THREADS, hb, st>>>(V, coords, cs, ps);
-    tp_scan_kernel<<<ps.n, 1024, 0, st>>>(ps);
-#define SCR_TP_S9(a, b, c)                                               \
-    do {                                                                 \
-        if (nl_coef) {                                                   \
-            allow_dynamic_lds((const void*)tp_scatter9_kernel<a, b, c, true>, TP_SCATTER_MAX_LDS);  \
-            tp_scatter9_kernel<a, b, c, true><<<nwg, TP_THREADS, 2 * hb, st>>>(V, coords, cs, grad, ld, col[0], ps, nl_coef, nl_dy, nl_lddy, nl_x, nl_ldx); \
-        } else {                                                         \
-            allow_dynamic_lds((const void*)tp_scatter9_kernel<a, b, c, false>, TP_SCATTER_MAX_LDS);  \
-            tp_scatter9_kernel<a, b, c, false><<<nwg, TP_THREADS, 2 * hb, st>>>(V, coords, cs, grad, ld, col[0], ps, nullptr, nullptr, 0, nullptr, 0); \
-        }                                                                \
-    } while (0)
-    if (RA == 15) {
-        if (RB) SCR_TP_S9(15, 5, 0); else SCR_TP_S9(15, 0, 0);
-    } else if (RA == 10) {
-        if (RC) SCR_TP_S9(10, 5, 5); else if (RB) SCR_TP_S9(10, 5, 0); else SCR_TP_S9(10, 0, 0);
-    } else {
-        if (RC) SCR_TP_S9(5, 5, 5); else if (RB) SCR_TP_S9(5, 5, 0); else SCR_TP_S9(5, 0, 0);
-    }
-#undef SCR_TP_S9
-    for (int g = 0; g < ngrids; ++g)
-        for (int q = 0; q < 3; ++q) {
-            const TpProj& pj = ps.p[3 * g + q];
-            float* gp = grad_planes[3 * g + q];
-            if (R[g] == 15) tp_gather_launch<15, 1>(pj, V, gp, gp, st);
-            else if (R[g] == 10) tp_gather_launch<10, 1>(pj, V, gp, gp, st);
-            else tp_gather_launch<5, 1>(pj, V, gp, gp, st);
-        }
-    return 0;
-}
-
-int launch_plane_sample_backward(int64_t V, const float* coords, int cs, int cx, int cy, int R, int A, int B, int planes,
-                                 const float* grad_out0, const float* grad_out1, int ld, float* grad_plane0,
-                                 float* grad_plane1, void* scratch, hipStream_t st) {
-    const int pairs[1][2] = {{cx, cy}}, sizes[1][2] = {{A, B}};
-    // the second block as a column offset from the first (the two blocks lie in the same gradient matrix)
-    const int cols0[1] = {0}, cols1[1] = {planes == 2 ? (int)(grad_out1 - grad_out0) : 0};
-    float* gp0[1] = {grad_plane0};
-    float* gp1[1] = {planes == 2 ? grad_plane1 : grad_plane0};
-    return tp_backward(V, coords, cs, R, planes, 1, pairs, sizes, grad_out0, ld, cols0, cols1, gp0, gp1, scratch, st);
-}
-
-// the three projections of a grid (coordinate pairs of scene/grids.py:148-150) in one pass over the points
-int launch_triplane_backward(int64_t V, const float* coords, int cs, int R, int X, int Y, int Z, int planes,
-                             const float* grad_out, int ld, const int* cols /*[3 * planes]*/, float* const* grad_planes,
-                             void* scratch, hipStream_t st) {
-    const int pairs[3][2] = {{1, 0}, {2, 0}, {2, 1}}, sizes[3][2] = {{X, Y}, {X, Z}, {Y, Z}};
-    const int* cols1 = planes == 2 ? cols + 3 : cols;
-    float* const* gp1 = planes == 2 ? grad_planes + 3 : grad_planes;
-    return tp_backward(V, coords, cs, R, planes, 3, pairs, sizes, grad_out, ld, cols, cols1, grad_planes, gp1, scratch, st);
-}
-
 
 // ---- normalised sample coordinates: ind = (xyz - lo) / (hi - lo) * 2 - 1 (scene/grids.py:146), the framework's four
 // elementwise passes over [V, 3] as one; the same IEEE operations in the same order, so the same bits
@@ -1357,12 +1208,231 @@ __global__ void __launch_bounds__(256) box_coords_kernel(int64_t n3, const float
             out[e] = ((xyz[e] - lo[c]) / den[c]) * 2.0f - 1.0f;
         }
 }
-void launch_box_coords(int64_t V, const float* xyz, const float* lo, const float* hi, float* out, hipStream_t st) {
-    if (V <= 0) return;
+}  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+size_t scr_plane_sample_scratch_bytes(int64_t V, int32_t A, int32_t B, int32_t channels) {
+    return tp_proj_bytes(V, A, B, channels) + tp_part_bytes(V, channels);
+}
+
+int scr_plane_sample_backward(int64_t V, const float* coords, int32_t cstride, int32_t cx, int32_t cy, int32_t R,
+                              int32_t A, int32_t B, int32_t planes, const float* grad_out0, const float* grad_out1,
+                              int32_t ld, float* grad_plane0, float* grad_plane1, void* scratch, void* stream) {
+    SCR_MARK_FN;
+    if (V < 0 || R <= 0 || A <= 1 || B <= 1) return fail("bad sizes");
+    if (planes != 1 && planes != 2) return fail("planes must be 1 or 2");
+    if (cstride <= 0 || cx < 0 || cy < 0 || cx >= cstride || cy >= cstride || ld < R) return fail("bad strides");
+    if (!grad_plane0 || !scratch || (V > 0 && (!coords || !grad_out0))) return fail("NULL argument");
+    if (planes == 2 && (!grad_plane1 || (V > 0 && !grad_out1))) return fail("NULL argument (second plane)");
+    if (R > TP_MAX_R) return fail("R = %d channels per plane exceeds the supported 16", R);
+    if (!tp_fits(A, B)) return fail("plane %dx%d has too many 32x32 tiles for the LDS histogram", A, B);
+    hipStream_t st = (hipStream_t)stream;
+    const int pairs[1][2] = {{cx, cy}}, sizes[1][2] = {{A, B}};
+    // the second block as a column offset from the first (the two blocks lie in the same gradient matrix)
+    const int cols0[1] = {0}, cols1[1] = {planes == 2 ? (int)(grad_out1 - grad_out0) : 0};
+    float* gp0[1] = {grad_plane0};
+    float* gp1[1] = {planes == 2 ? grad_plane1 : grad_plane0};
+    { ProfScope ps_(SCR_PROF_PLANE_BACKWARD, st);
+      tp_backward(V, coords, cstride, R, planes, 1, pairs, sizes, grad_out0, ld, cols0, cols1, gp0, gp1, scratch, st); }
+    CHECK_LAUNCH("plane_sample_backward", 0, st);
+    return 0;
+}
+
+size_t scr_triplane_backward_scratch_bytes(int64_t V, int32_t X, int32_t Y, int32_t Z, int32_t channels) {
+    return tp_proj_bytes(V, X, Y, channels) + tp_proj_bytes(V, X, Z, channels) + tp_proj_bytes(V, Y, Z, channels) + tp_part_bytes(V, channels);
+}
+
+// the three projections of a grid (coordinate pairs of scene/grids.py:148-150) in one pass over the points
+int scr_triplane_backward(int64_t V, const float* coords, int32_t cstride, int32_t R, int32_t X, int32_t Y, int32_t Z,
+                          int32_t planes, const float* grad_out, int32_t ld, const int32_t* cols, float* const* grad_planes,
+                          void* scratch, void* stream) {
+    SCR_MARK_FN;
+    if (V < 0 || R <= 0 || X <= 1 || Y <= 1 || Z <= 1) return fail("bad sizes");
+    if (planes != 1 && planes != 2) return fail("planes must be 1 or 2");
+    if (cstride < 3 || ld < R * 3 * planes) return fail("bad strides");
+    if (!cols || !grad_planes || !scratch || (V > 0 && (!coords || !grad_out))) return fail("NULL argument");
+    for (int q = 0; q < 3 * planes; ++q) {
+        if (!grad_planes[q]) return fail("NULL plane gradient %d", q);
+        if (cols[q] < 0 || cols[q] + R > ld) return fail("column block %d outside the gradient rows", q);
+    }
+    if (R > TP_MAX_R) return fail("R = %d channels per plane exceeds the supported 16", R);
+    if (!tp_fits(X, Y) || !tp_fits(X, Z) || !tp_fits(Y, Z))
+        return fail("a plane of %dx%dx%d has too many 32x32 tiles for the LDS histogram", X, Y, Z);
+    hipStream_t st = (hipStream_t)stream;
+    const int pairs[3][2] = {{1, 0}, {2, 0}, {2, 1}}, sizes[3][2] = {{X, Y}, {X, Z}, {Y, Z}};
+    const int* cols1 = planes == 2 ? cols + 3 : cols;
+    float* const* gp1 = planes == 2 ? grad_planes + 3 : grad_planes;
+    { ProfScope ps_(SCR_PROF_PLANE_BACKWARD, st);
+      tp_backward(V, coords, cstride, R, planes, 3, pairs, sizes, grad_out, ld, cols, cols1, grad_planes, gp1, scratch, st); }
+    CHECK_LAUNCH("triplane_backward", 0, st);
+    return 0;
+}
+
+// ---- all grids of a step at once (see tp_scatter9_kernel).  ngrids <= 3; grid g: R[g] channels per plane (the attention
+// grid arrives with its planes stacked), sizes X/Y/Z[g], first column col[g] of its 3 * R[g] gradient columns (xy, xz, yz
+// in this order); the columns of all grids are contiguous from col[0].
+size_t scr_triplane_backward_multi_scratch_bytes(int64_t V, int32_t ngrids, const int32_t* R, const int32_t* X, const int32_t* Y,
+                                                 const int32_t* Z) {
+    if (!R || !X || !Y || !Z || ngrids < 1 || ngrids > 3) return 0;
+    size_t b = 0;
+    int widest = 1;
+    for (int g = 0; g < ngrids; ++g) {
+        b += tp_proj_bytes(V, X[g], Y[g], R[g]) + tp_proj_bytes(V, X[g], Z[g], R[g]) + tp_proj_bytes(V, Y[g], Z[g], R[g]);
+        widest = R[g] > widest ? R[g] : widest;
+    }
+    return b + tp_part_bytes(V, widest);
+}
+
+// Returns 3 when the layout is not one the fused pass handles (not an error: the caller falls back to one call per grid);
+// nothing has been enqueued then.
+// nl_coef (NULL: off): the gradient rows are formed from the BatchNorm-Linear's coefficients, its upstream gradient nl_dy
+// [V,32] and its input nl_x (the sampled matrix, same columns as grad) -- see tp_scatter9_kernel; grad may then be NULL.
+int scr_triplane_backward_multi(int64_t V, const float* coords, int32_t cstride, int32_t ngrids, const int32_t* R,
+                                const int32_t* X, const int32_t* Y, const int32_t* Z, const int32_t* col, const float* grad_out,
+                                int32_t ld, float* const* grad_planes, void* scratch, const float* nl_coef, const float* nl_dy,
+                                int32_t nl_lddy, const float* nl_x, int32_t nl_ldx, void* stream) {
+    SCR_MARK_FN;
+    if (V < 0 || ngrids < 1 || ngrids > 3) return fail("bad sizes");
+    if (!R || !X || !Y || !Z || !col || !grad_planes || !scratch || (V > 0 && (!coords || (!grad_out && !nl_coef)))) return fail("NULL argument");
+    if (nl_coef && (!nl_dy || !nl_x || nl_lddy < 32 || nl_ldx < col[ngrids - 1] + 3 * R[ngrids - 1])) return fail("fused dx: dy [V,32] and x (the sampled matrix) are needed");
+    for (int g = 0; g < ngrids; ++g) {
+        if (R[g] < 1 || X[g] < 2 || Y[g] < 2 || Z[g] < 2 || col[g] < 0 || col[g] + 3 * R[g] > (grad_out ? ld : nl_ldx)) return fail("bad grid %d", g);
+        for (int q = 0; q < 3; ++q)
+            if (!grad_planes[3 * g + q]) return fail("NULL plane gradient %d", 3 * g + q);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps_(SCR_PROF_PLANE_BACKWARD, st);
+        if (cstride < 3) return 3;
+        if (col[0] % 4 != 0) return 3;
+        if (grad_out && (ld % 4 != 0 || ((uintptr_t)grad_out & 15) != 0)) return 3;
+        if (!grad_out && !nl_coef) return 3;
+        if (nl_coef && (nl_ldx % 4 != 0 || ((uintptr_t)nl_x & 15) != 0 || nl_lddy % 4 != 0 || ((uintptr_t)nl_dy & 15) != 0)) return 3;
+        for (int g = 0; g + 1 < ngrids; ++g)
+            if (col[g + 1] != col[g] + 3 * R[g]) return 3;
+        const int RA = R[0], RB = ngrids > 1 ? R[1] : 0, RC = ngrids > 2 ? R[2] : 0;
+        // the layouts of FeaturePlanes (r = channels per plane): attention grid stacked (2 r) [+ plain (r) [+ plain (r)]], or plain grids only
+        // (15: the attention grid's pair planes with the same-size plain grid's plane stacked on them, one record / gather per projection)
+        const bool known = ((RA == 10 || RA == 5) && (RB == 0 || RB == 5) && (RC == 0 || RC == 5)) || (RA == 15 && (RB == 0 || RB == 5) && RC == 0);
+        if (!known || (RC && !RB)) return 3;
+        size_t total = 0;
+        for (int g = 0; g < ngrids; ++g) total += tp_tiles(X[g], Y[g]) + tp_tiles(X[g], Z[g]) + tp_tiles(Y[g], Z[g]);
+        if (total > (size_t)TP_HIST_MAX_TILES) return 3;
+        TpProjSetT<9> ps;
+        ZeroList zl;
+        ps.n = 3 * ngrids;
+        const int pairs[3][2] = {{1, 0}, {2, 0}, {2, 1}};
+        char* sc = (char*)scratch;
+        for (int g = 0; g < ngrids; ++g) {
+            const int sizes[3][2] = {{X[g], Y[g]}, {X[g], Z[g]}, {Y[g], Z[g]}};
+            for (int q = 0; q < 3; ++q)
+                sc = tp_setup_projection(ps.p[3 * g + q], pairs[q][0], pairs[q][1], sizes[q][0], sizes[q][1], col[g] + q * R[g],
+                                         col[g] + q * R[g], V, R[g], 1, grad_planes[3 * g + q], nullptr, sc, zl, st);
+        }
+        launch_zero(zl, st);
+        tp_close_set(ps, sc);
+        if (V > 0) {
+            const unsigned nwg = (unsigned)((V + TP_PER_WG - 1) / TP_PER_WG);
+            const size_t hb = total * 4;
+            tp_count_kernel<<<nwg, TP_THREADS, hb, st>>>(V, coords, cstride, ps);
+            tp_scan_kernel<<<ps.n, 1024, 0, st>>>(ps);
+#define SCR_TP_S9(a, b, c)                                               \
+    do {                                                                 \
+        if (nl_coef) {                                                   \
+            allow_dynamic_lds((const void*)tp_scatter9_kernel<a, b, c, true>, TP_SCATTER_MAX_LDS);  \
+            tp_scatter9_kernel<a, b, c, true><<<nwg, TP_THREADS, 2 * hb, st>>>(V, coords, cstride, grad_out, ld, col[0], ps, nl_coef, nl_dy, nl_lddy, nl_x, nl_ldx); \
+        } else {                                                         \
+            allow_dynamic_lds((const void*)tp_scatter9_kernel<a, b, c, false>, TP_SCATTER_MAX_LDS);  \
+            tp_scatter9_kernel<a, b, c, false><<<nwg, TP_THREADS, 2 * hb, st>>>(V, coords, cstride, grad_out, ld, col[0], ps, nullptr, nullptr, 0, nullptr, 0); \
+        }                                                                \
+    } while (0)
+            if (RA == 15) {
+                if (RB) SCR_TP_S9(15, 5, 0); else SCR_TP_S9(15, 0, 0);
+            } else if (RA == 10) {
+                if (RC) SCR_TP_S9(10, 5, 5); else if (RB) SCR_TP_S9(10, 5, 0); else SCR_TP_S9(10, 0, 0);
+            } else {
+                if (RC) SCR_TP_S9(5, 5, 5); else if (RB) SCR_TP_S9(5, 5, 0); else SCR_TP_S9(5, 0, 0);
+            }
+#undef SCR_TP_S9
+            for (int g = 0; g < ngrids; ++g)
+                for (int q = 0; q < 3; ++q) {
+                    const TpProj& pj = ps.p[3 * g + q];
+                    float* gp = grad_planes[3 * g + q];
+                    if (R[g] == 15) tp_gather_launch<15, 1>(pj, V, gp, gp, st);
+                    else if (R[g] == 10) tp_gather_launch<10, 1>(pj, V, gp, gp, st);
+                    else tp_gather_launch<5, 1>(pj, V, gp, gp, st);
+                }
+        }
+    }
+    CHECK_LAUNCH("triplane_backward_multi", 0, st);
+    return 0;
+}
+
+int scr_plane_row_pairs(int32_t R, int32_t A, int32_t B, const float* plane, float* pairs, void* stream) {
+    SCR_MARK_FN;
+    if (A < 2 || B < 2) return fail("bad sizes");
+    if (!plane || !pairs) return fail("NULL argument");
+    if (R < 1 || R > TP_MAX_R) return fail("R = %d channels per plane exceeds the supported 16", R);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((B + 255) / 256), (unsigned)(A - 1));
+#define SCR_TP_RP(RR) case RR: plane_row_pairs_kernel<RR><<<grid, 256, 0, st>>>(A, B, plane, pairs); break;
+    switch (R) {
+        SCR_TP_RP(1) SCR_TP_RP(2) SCR_TP_RP(3) SCR_TP_RP(4) SCR_TP_RP(5) SCR_TP_RP(6) SCR_TP_RP(7) SCR_TP_RP(8)
+        SCR_TP_RP(9) SCR_TP_RP(10) SCR_TP_RP(11) SCR_TP_RP(12) SCR_TP_RP(13) SCR_TP_RP(14) SCR_TP_RP(15) SCR_TP_RP(16)
+    }
+#undef SCR_TP_RP
+    CHECK_LAUNCH("plane_row_pairs_kernel", 0, st);
+    return 0;
+}
+
+int scr_triplane_forward(int64_t V, const float* coords, int32_t cstride, const float* xy, const float* xz,
+                         const float* yz, int32_t R, int32_t X, int32_t Y, int32_t Z, int32_t channel_last, float* out,
+                         int32_t ld, int32_t col_xy, int32_t col_xz, int32_t col_yz, void* stream) {
+    SCR_MARK_FN;
+    if (V < 0 || R <= 0 || X <= 1 || Y <= 1 || Z <= 1) return fail("bad sizes");
+    if (cstride < 3 || col_xy < 0 || col_xz < 0 || col_yz < 0 || col_xy + R > ld || col_xz + R > ld || col_yz + R > ld)
+        return fail("bad strides");
+    if (V > 0 && (!coords || !xy || !xz || !yz || !out)) return fail("NULL argument");
+    if (R > TP_MAX_R) return fail("R = %d channels per plane exceeds the supported 16", R);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned nb = (unsigned)((V + 255) / 256);
+#define SCR_TP_FWD(RR)                                                                                          \
+    case RR:                                                                                                    \
+        if (channel_last == 2)                                                                                  \
+            triplane_forward_kernel<RR, 2><<<nb, 256, 0, st>>>(V, coords, cstride, xy, xz, yz, X, Y, Z, out, ld, col_xy, \
+                                                               col_xz, col_yz);                                  \
+        else if (channel_last)                                                                                  \
+            triplane_forward_kernel<RR, 1><<<nb, 256, 0, st>>>(V, coords, cstride, xy, xz, yz, X, Y, Z, out, ld, col_xy, \
+                                                               col_xz, col_yz);                                  \
+        else                                                                                                    \
+            triplane_forward_kernel<RR, 0><<<nb, 256, 0, st>>>(V, coords, cstride, xy, xz, yz, X, Y, Z, out, ld, col_xy, \
+                                                               col_xz, col_yz);                                  \
+        break;
+    { ProfScope ps_(SCR_PROF_TRIPLANE_FORWARD, st);
+      if (V > 0) switch (R) {
+          SCR_TP_FWD(1) SCR_TP_FWD(2) SCR_TP_FWD(3) SCR_TP_FWD(4) SCR_TP_FWD(5) SCR_TP_FWD(6) SCR_TP_FWD(7) SCR_TP_FWD(8) SCR_TP_FWD(9) SCR_TP_FWD(10) SCR_TP_FWD(11) SCR_TP_FWD(12) SCR_TP_FWD(13) SCR_TP_FWD(14) SCR_TP_FWD(15) SCR_TP_FWD(16)
+      } }
+#undef SCR_TP_FWD
+    CHECK_LAUNCH("triplane_forward_kernel", 0, st);
+    return 0;
+}
+
+// ---- normalised tri-plane coordinates of contiguous xyz[V,3] in the box [lo, hi]
+int scr_box_coords(int64_t V, const float* xyz, const float* lo_host, const float* hi_host, float* out, void* stream) {
+    SCR_MARK_FN;
+    if (V < 0) return fail("V < 0");
+    if (V == 0) return 0;
+    if (!xyz || !lo_host || !hi_host || !out) return fail("NULL argument");
+    hipStream_t st = (hipStream_t)stream;
     const int64_t n3 = 3 * V, groups = n3 / 12;
     const int64_t want = (groups + 255) / 256;
     const unsigned grid = (unsigned)(want < 1 ? 1 : want < 16384 ? want : 16384);
-    box_coords_kernel<<<grid, 256, 0, st>>>(n3, xyz, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], out);
+    box_coords_kernel<<<grid, 256, 0, st>>>(n3, xyz, lo_host[0], lo_host[1], lo_host[2], hi_host[0], hi_host[1], hi_host[2], out);
+    CHECK_LAUNCH("box_coords_kernel", 0, st);
+    return 0;
 }
 
-}  // namespace scr
+}  // extern "C"

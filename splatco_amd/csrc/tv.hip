@@ -20,10 +20,11 @@
 // plane element is loaded once per strip plus the two halo rows (2 / TV_ROWS = 6 %, mostly L2 hits); the left / right
 // neighbours of a lane's columns come from the neighbouring lanes' cache lines (L1 hits).  Four rows of loads are in flight
 // per wave.  Consecutive units of the same XCD are neighbouring column tiles and strips, so the halos meet in that XCD's L2.
-#include "tv.h"
+#include "capi.h"
 
 namespace scr {
 
+constexpr int TV_MAX = 12;        // planes per launch (three projections of up to four grids)
 constexpr int TV_ROWS = 32;       // rows per strip
 constexpr int TV_BATCH = 4;       // rows whose loads are issued together
 
@@ -129,12 +130,29 @@ __global__ void __launch_bounds__(256) tv_add_grad_kernel(const TvArgs a) {
     else           tv_strip<1>(a.p[t] + plane, a.g[t] + plane, A, B, a0, a1, ct * 64 + lane, a.coef[t]);
 }
 
-int launch_tv_add_grad(int n, const scr_tv_plane* planes, hipStream_t st) {
-    for (int t0 = 0; t0 < n; t0 += TV_MAX) {
+}  // namespace scr
+
+using namespace scr;
+
+extern "C" {
+
+int scr_tv_add_grad(int32_t n_planes, const scr_tv_plane* planes, void* stream) {
+    SCR_MARK_FN;
+    if (n_planes < 0) return fail("scr_tv_add_grad: n_planes < 0");
+    if (n_planes == 0) return 0;
+    if (!planes) return fail("scr_tv_add_grad: planes is NULL");
+    for (int t = 0; t < n_planes; ++t) {
+        const scr_tv_plane& x = planes[t];
+        if (x.channels < 0 || x.rows < 0 || x.cols < 0) return fail("scr_tv_add_grad: negative plane size");
+        if ((int64_t)x.channels * x.rows * x.cols > 0 && (!x.plane || !x.grad)) return fail("scr_tv_add_grad: NULL plane / grad");
+        if (x.plane == x.grad && x.plane) return fail("scr_tv_add_grad: plane and grad must be distinct buffers");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    for (int t0 = 0; t0 < n_planes; t0 += TV_MAX) {
         TvArgs a;
         a.n = 0;
         uint64_t units = 0;
-        for (int t = t0; t < min(t0 + TV_MAX, n); ++t) {
+        for (int t = t0; t < min(t0 + TV_MAX, n_planes); ++t) {
             const scr_tv_plane& x = planes[t];
             if ((int64_t)x.channels * x.rows * x.cols == 0) continue;
             const int k = a.n++;
@@ -150,14 +168,15 @@ int launch_tv_add_grad(int n, const scr_tv_plane* planes, hipStream_t st) {
             a.strips[k] = (x.rows + TV_ROWS - 1) / TV_ROWS;
             a.ctiles[k] = (x.cols + 64 * per_lane - 1) / (64 * per_lane);
             units += (uint64_t)x.channels * a.strips[k] * a.ctiles[k];
-            if (units > 0x7fffffffull) return 1;
+            if (units > 0x7fffffffull) return fail("scr_tv_add_grad: more than 2^31 wave units in one launch");
         }
         if (!a.n) continue;
         a.first_unit[a.n] = (uint32_t)units;
         const uint64_t blocks = ((units + 3) / 4 + 7) / 8 * 8;
         tv_add_grad_kernel<<<(unsigned)blocks, 256, 0, st>>>(a);
     }
+    CHECK_LAUNCH("tv_add_grad_kernel", 0, st);
     return 0;
 }
 
-}  // namespace scr
+}  // extern "C"
