@@ -25,6 +25,16 @@
  *     one 64-byte pinned mailbox per calling host thread (created on first use), a per-device flag that
  *     the >64 KB dynamic-LDS attribute has been set, and the opt-in profiling event pool (scr_profile_*).
  *     One host thread per process/GPU.
+ *   - Fresh memory.  No scratch, saved-state or output buffer of any scr_* entry point needs initialising by the caller,
+ *     and no result depends on what such a buffer held before the call: every word the library reads or hands back it has
+ *     written itself in that call or in the earlier call of the same pass that produced the buffer (scr_*_plan before
+ *     scr_*_run, a forward before its backward; those buffers must reach the later call unchanged).  Outputs are written
+ *     in full: rows, pixels and plane nodes that nothing contributes to hold 0.  The exceptions are exactly the arguments
+ *     documented as accumulated into, whose contents are inputs: the plane gradients of scr_tv_add_grad, the four
+ *     accumulators of scr_statis_apply, the parameters and both moments of scr_adam_step / scr_adam_step_rows, and the four
+ *     gradient arrays of scr_anchor_gather_backward when accumulate != 0 (a further view of the step: a GradSink's second
+ *     view).  (The running statistics that scr_norm_running_stats updates are module state of the same kind, not a buffer
+ *     of this paragraph.)  tests/test_gpu_fresh_memory.py runs every operator family on buffers pre-filled with three byte patterns.
  *   - Return value: 0 = ok, non-zero = error; scr_last_error() returns a thread-local message.
  */
 #ifndef SPLATCO_RASTER_H
