@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define SCR_ABI_VERSION 36
+#define SCR_ABI_VERSION 37
 #define SCR_TILE 16 /* 16x16-pixel tiles: part of the result contract (tile rects, ranges, sort keys) */
 
 /* The 12 fields of GaussianRasterizationSettings, same order (gaussian_renderer/__init__.py:145-158).
@@ -640,6 +640,30 @@ int scr_voxel_keys(int64_t N, const float* points, float voxel_size, const int32
 int scr_voxel_unique_plan(int64_t N, const int64_t* sorted_keys, void* scratch, int64_t* num_unique_host, void* stream);
 int scr_voxel_unique_run(int64_t N, const int64_t* sorted_keys, const void* scratch, float voxel_size,
                          const int32_t* lo_host, float* out_xyz, void* stream);
+
+/* ---- Mip-Splatting's 3D smoothing filter (ABI 37; kernels: csrc/filter3d.hip, host half: splatco_amd/filter3d.py).  All
+ * float32, no contraction, the comparisons exactly these.
+ * scr_filter3d_distance: points[N,3]; cameras[C,16], one packed row per training camera: rows 0..2 of the 3x4 [R | t] of
+ * W2C = world_view_transform^T (r00 r01 r02 t0, r10 ..., r20 ...), tx = 1.3 tan(FoVx / 2), ty = 1.3 tan(FoVy / 2),
+ * focal = max(fx, fy), 0.  p = R x + t with px = ((r00 x + r01 y) + r02 z) + t0 (py, pz alike).  The camera observes the point
+ * when x, y, z are finite and pz > 0.2f and |px| <= tx pz and |py| <= ty pz (upstream's test: z > 0.2 and the pixel inside
+ * the image enlarged by 15 % per side, bounds inclusive).  m[N] = min over the observing cameras of pz / focal, +inf when no
+ * camera observes the point: the same bits for every order of the cameras.  Any C >= 1; N <= (2^31 - 1) * 256.
+ * scr_filter3d_apply: the V k candidates of scr_expand_run (V k < 2^31), out_index[V k] int32 = each candidate's position among
+ * the P Gaussians or -1 (every position exactly once, rising), row_filter[V] = the filter value f of each row's anchor,
+ * scaling[P,3], opacity[P].  With t_i = sqrt(s_i^2 + f^2) and r_i = s_i / t_i: scaling_out[j,i] = t_i and
+ * opacity_out[j] = o ((r_0 r_1) r_2) (the ratio form: the product of the squares underflows for small scales).  A row with
+ * f == 0 passes through: the inputs' bits.  Every output row is written exactly once; an index outside [0, P) is skipped.
+ * scr_filter3d_apply_backward: d_scaling[j,i] = g_scaling[j,i] r_i + ((g_opacity[j] o) prod_{l != i} r_l) (f / t_i)^2 / t_i,
+ * d_opacity[j] = g_opacity[j] ((r_0 r_1) r_2); no division by s_i.  g_scaling / g_opacity may be NULL (zero, not
+ * materialised); rows with f == 0 get the upstream gradients' bits.  f carries no gradient.
+ * N == 0 / P == 0: nothing is launched, status 0. */
+int scr_filter3d_distance(int64_t N, const float* points, int32_t C, const float* cameras, float* m, void* stream);
+int scr_filter3d_apply(int64_t V, int32_t k, int64_t P, const int32_t* out_index, const float* row_filter, const float* scaling,
+                       const float* opacity, float* scaling_out, float* opacity_out, void* stream);
+int scr_filter3d_apply_backward(int64_t V, int32_t k, int64_t P, const int32_t* out_index, const float* row_filter,
+                                const float* scaling, const float* opacity, const float* g_scaling, const float* g_opacity,
+                                float* d_scaling, float* d_opacity, void* stream);
 
 /* ---- measurement aid: a float4 grid-stride copy of `bytes` bytes (src -> dst, device pointers).  bench.py times it to
  * quote the HBM bandwidth a streaming kernel reaches on the box next to the 8 TB/s datasheet figure. */

@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("SPLATCO_RASTER_LIB", os.path.join(_HERE, "csrc", "lib
 PLAN_NONFINITE_COLOUR, PLAN_LARGE_RECTS, PLAN_ANTIALIASED = 1, 2, 4      # SCR_PLAN_*
 MODE_ANTIALIASED = 1                                # SCR_MODE_* (scr_forward_plan / scr_forward_plan_run)
 PROF_COUNT = 20
-ABI_VERSION = 36
+ABI_VERSION = 37
 FLIP_MAX_RADIUS = 16                                # SCR_FLIP_MAX_RADIUS
 
 (DBG_TILES_TOUCHED, DBG_POINT_OFFSETS, DBG_RANGES, DBG_POINT_LIST, DBG_N_CONTRIB, DBG_FINAL_T, DBG_SPLAT_RECORDS, DBG_QMASK,
@@ -135,6 +135,9 @@ SIGNATURES = [
     ("scr_voxel_keys", i32, i64, vp, f32, P(i32), i32, vp, vp),
     ("scr_voxel_unique_plan", i32, i64, vp, vp, P(i64), vp),
     ("scr_voxel_unique_run", i32, i64, vp, vp, f32, P(i32), vp, vp),
+    ("scr_filter3d_distance", i32, i64, vp, i32, vp, vp, vp),
+    ("scr_filter3d_apply", i32, i64, i32, i64, *[vp] * 7),
+    ("scr_filter3d_apply_backward", i32, i64, i32, i64, *[vp] * 9),
     ("scr_copy_probe", i32, vp, vp, sz, vp),
     ("scr_profile_enable", i32, i32),
     ("scr_profile_stride", i32, i32),

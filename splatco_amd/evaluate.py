@@ -30,20 +30,23 @@ def _eval_mode(pc):
         pc.train(was_training)
 
 
-def render_views(views, pc, pipe, bg_color, antialiased=None):
+def render_views(views, pc, pipe, bg_color, antialiased=None, filter_3d=None):
     """Render every view as render.py:47-53 does: under no_grad, prefilter_voxel then render, each view timed between
     two device synchronisations.  Returns (images: list of [3,H,W] device tensors, times: list of seconds, fps).
     fps = 1 / mean(times[5:]) as render.py:63-64 prints it (the first five views warm up); with 5 views or fewer there
     is no such tail, and the mean of all of them is taken instead of the reference's NaN.  antialiased: handed to render()
-    (None: pipe.antialiasing decides)."""
+    (None: pipe.antialiasing decides).  filter_3d: Mip-Splatting's 3D smoothing filter, handed to render() (a
+    filter3d.Filter3D or an [N] tensor; None: no filter)."""
+    extra = {} if antialiased is None else {"antialiased": antialiased}
+    if filter_3d is not None:
+        extra["filter_3d"] = filter_3d
     images, times = [], []
     with _eval_mode(pc), torch.no_grad():
         for view in views:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             vis = prefilter_voxel(view, pc, pipe, bg_color)
-            img = render(view, pc, pipe, bg_color, visible_mask=vis,
-                         **({} if antialiased is None else {"antialiased": antialiased}))["render"]
+            img = render(view, pc, pipe, bg_color, visible_mask=vis, **extra)["render"]
             torch.cuda.synchronize()
             times.append(time.perf_counter() - t0)
             images.append(img)
@@ -68,15 +71,16 @@ def score_views(images, gts, quantize=True, pixels_per_degree=metrics.DEFAULT_PP
 
 
 def evaluate_views(views, pc, pipe, bg_color, gts=None, names=None, quantize=True,
-                   pixels_per_degree=metrics.DEFAULT_PPD, antialiased=None):
+                   pixels_per_degree=metrics.DEFAULT_PPD, antialiased=None, filter_3d=None):
     """Render and score test views; the result is shaped like metrics.py's per-method entry:
       {"SSIM", "PSNR", "FLIPS", "NUM", "FPS", "per_view": {"SSIM": {name: v}, "PSNR": {...}, "FLIPS": {...}}}
     gts: ground-truth [3,H,W] images, by default view.original_image[0:3] (render.py:58); names: by default
     "00000.png", ... (render.py:59).  NUM is the anchor count (render.py:91-95), FPS render.py's.  Renders are clamped
     to [0,1] (and with `quantize` rounded to 8 bits) before scoring, as saving them as PNG does.  LPIPS is absent:
     no pretrained weights can be obtained for it here.  antialiased: the views are rendered in the rasterizer's antialiased
-    mode (render(); None: pipe.antialiasing decides)."""
-    images, times, fps = render_views(views, pc, pipe, bg_color, **({} if antialiased is None else {"antialiased": antialiased}))
+    mode (render(); None: pipe.antialiasing decides).  filter_3d: rendered with the 3D smoothing filter (render())."""
+    images, times, fps = render_views(views, pc, pipe, bg_color, **({} if antialiased is None else {"antialiased": antialiased}),
+                                      **({} if filter_3d is None else {"filter_3d": filter_3d}))
     if gts is None:
         gts = [v.original_image[0:3] for v in views]
     if len(gts) != len(images):

@@ -35,7 +35,8 @@ def _parts_capable():
     return GaussianLearner
 
 
-def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False, expand=None, fused_heads=True):
+def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_training=False, expand=None, fused_heads=True,
+                              filter_3d=None):
     """Anchors -> neural Gaussians (gaussian_renderer/__init__.py:18-116), same op order.
     The mask / compaction / post-processing block (:68-111) is the single HIP op of splatco_amd.expand
     (device tensors only, no CPU path).  expand: test hook -- a callable with expand_compact's signature
@@ -43,7 +44,14 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
     the MLP heads as rocBLAS GEMMs (the checker of csrc/mlp_heads.hip).
     The camera centre is a CONSTANT here: the anchors' view direction ob_view is formed from camera_center.detach(), in the
     fused heads kernel and in the torch chain alike.  A camera that requires grad (cameras.pose_delta_camera) gets its
-    gradient through the rasterizer operator only; for every other camera nothing changes."""
+    gradient through the rasterizer operator only; for every other camera nothing changes.
+    filter_3d: Mip-Splatting's 3D smoothing filter (splatco_amd.filter3d): a Filter3D or an [N] tensor of per-anchor filter
+    values.  The returned scaling and opacity are then the filtered ones (filter3d.apply_filter_3d on the rows of the visible
+    anchors), and with is_training the tuple carries an eighth entry, the unfiltered scaling the heads produced (what the
+    scaling regulariser acts on).  None (the default): nothing of it runs."""
+    if filter_3d is not None:
+        from . import filter3d as _f3
+        filter_values = _f3.anchor_values(filter_3d, pc)       # raises for a stale filter before anything is launched
     campos = viewpoint_camera.camera_center.detach()
     if visible_mask is None:
         visible_mask = torch.ones(pc.get_anchor.shape[0], dtype=torch.bool, device=pc.get_anchor.device)
@@ -137,6 +145,12 @@ def generate_neural_gaussians(viewpoint_camera, pc, visible_mask=None, is_traini
         from .expand import expand_compact as expand
     xyz, color, opacity, scaling, rot, mask = expand(neural_opacity, color, scale_rot, grid_offsets, grid_scaling,
                                                      anchor, k)
+    if filter_3d is not None:
+        # the filter rows follow the visible-anchor index; the candidates' rows come from the compaction index on the mask
+        raw_scaling = scaling
+        scaling, opacity = _f3.apply_filter_3d(scaling, opacity, filter_values.index_select(0, idx), mask, k)
+        if is_training:
+            return xyz, color, opacity, scaling, rot, neural_opacity, mask, raw_scaling
     if is_training:
         return xyz, color, opacity, scaling, rot, neural_opacity, mask
     return xyz, color, opacity, scaling, rot
@@ -188,19 +202,23 @@ def keep_grad(screenspace_points):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_mask=None, retain_grad=False, aux=False,
-           antialiased=None):
+           antialiased=None, filter_3d=None):
     """gaussian_renderer/__init__.py:118-188.  Background tensor must be on the GPU.  aux=True: the result also holds
     "depth" and "alpha", the rasterizer's [H, W] depth and accumulated-opacity maps (GaussianRasterizer.forward).
     A camera whose world_view_transform / full_proj_transform / camera_center require grad (cameras.pose_delta_camera)
     receives the gradient of the image and the maps through the rasterizer operator: projection, covariance projection and
     depth.  The camera's path through the MLP heads (the anchors' view direction) is not differentiated.
     antialiased: the rasterizer's opacity compensation (GaussianRasterizer.forward); None (the default) follows
-    pipe.antialiasing, upstream's pipeline parameter, where the pipe has one."""
+    pipe.antialiasing, upstream's pipeline parameter, where the pipe has one.
+    filter_3d: Mip-Splatting's 3D smoothing filter, a splatco_amd.filter3d.Filter3D or an [N] tensor of per-anchor values
+    (generate_neural_gaussians): the rasterizer gets the filtered scaling and opacity, while res["scaling"] stays the
+    unfiltered tensor -- the regulariser acts on what the heads learn."""
     if antialiased is None:
         antialiased = bool(getattr(pipe, "antialiasing", False))
     is_training = pc.get_color_mlp.training
     with _C_stage("generate_neural_gaussians"):
-        out = generate_neural_gaussians(viewpoint_camera, pc, visible_mask, is_training=is_training)
+        out = generate_neural_gaussians(viewpoint_camera, pc, visible_mask, is_training=is_training,
+                                        **({} if filter_3d is None else {"filter_3d": filter_3d}))
     xyz, color, opacity, scaling, rot = out[:5]
     # zero tensor that carries the screen-space mean gradient back to the caller (:133-138): a NON-LEAF that requires grad
     # (the reference's `zeros_like(..., requires_grad=True) + 0`), whose .grad is populated only with retain_grad (:134-138,
@@ -219,7 +237,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, visible_m
     if aux:
         res["depth"], res["alpha"] = maps
     if is_training:
-        res.update({"selection_mask": out[6], "neural_opacity": out[5], "scaling": scaling})
+        res.update({"selection_mask": out[6], "neural_opacity": out[5], "scaling": scaling if filter_3d is None else out[7]})
     return res
 
 

@@ -56,7 +56,7 @@ def sync_densification_stats(densifier, n_views, out, vis, device):
 
 def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, bucket=None,
                        consistency_weight=0.0, densifier=None, arena=None, iteration=None, tv_weight=0.0, sparse_adam=False,
-                       depth_targets=None, depth_masks=None, depth_weight=0.0, depth_options=None):
+                       filter_3d=None, depth_targets=None, depth_masks=None, depth_weight=0.0, depth_options=None):
     """views / gt_images: the identically ordered mv view list every rank holds; gt_images[i] is the
     [3,H,W] target of views[i] (host or device).  densifier: a splatco_amd.densify.AnchorDensifier; its
     accumulators receive the statistics of the LAST view of the list on every rank (sync_densification_stats).
@@ -80,6 +80,11 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
     mask; every view is rendered with aux=True and depth_weight * depth_loss(out["depth"], out["alpha"], target, mask,
     **depth_options) is added to that view's loss.  Both lists are sharded as gt_images.  With the default weight of 0 the
     step is the one without these arguments, bit for bit: render() is called without aux and nothing else runs.
+    filter_3d: a filter3d.Filter3D (Mip-Splatting's 3D smoothing filter).  On entry it is recomputed from the model's anchors
+    (filter_3d.update(pc)) when it is stale -- never updated, or adjust_anchor / prune_anchor / sort_anchors replaced the
+    anchors -- or when `iteration % filter_3d.every == 0`; every render() of the step then gets it.  The filter is a function
+    of the parameters and the cameras alone: every rank computes the same values and nothing is exchanged.  None (the
+    default): the step is the one without the argument.
     Returns (local loss sum, last render dict, bucket or arena buffer)."""
     from .adam import FusedAdam, ShardedFusedAdam
     if sparse_adam:
@@ -99,6 +104,13 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
         for name, lst in (("depth_targets", depth_targets), ("depth_masks", depth_masks)):
             if lst is not None and len(lst) != len(views):
                 raise ValueError(f"collaborative_step: {len(lst)} {name} for {len(views)} views")
+    render_options = {"aux": True} if use_depth else {}
+    if filter_3d is not None:
+        from .filter3d import Filter3D
+        if isinstance(filter_3d, Filter3D) and filter_3d.due(pc, iteration):
+            with stage("filter_3d"):
+                filter_3d.update(pc)
+        render_options["filter_3d"] = filter_3d
     params = arena.params if arena is not None else [p for p in pc.parameters() if p.requires_grad]
     if arena is not None:
         # the per-anchor gradients (99 % of the arena) are written in place by the gather's backward kernel; the sink is
@@ -133,7 +145,7 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
             if want_union or sparse_adam:
                 union = vis.clone() if union is None else union.logical_or_(vis)
             with stage("render"):
-                out = render(cam, pc, pipe, bg_color, visible_mask=vis, retain_grad=True, **({"aux": True} if use_depth else {}))
+                out = render(cam, pc, pipe, bg_color, visible_mask=vis, retain_grad=True, **render_options)
             with stage("loss"):
                 gt = gt.to(out["render"].device, non_blocking=True)
                 loss = view_loss(out["render"], gt, out["scaling"])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/capi_rejections.json: what every streamed entry point of the C-ABI (an scr_* function of
+"""Generate tests/golden/capi_rejections_abi37.json: what every streamed entry point of the C-ABI (an scr_* function of
 include/splatco_raster.h whose last parameter is `void* stream`) answers to a few synthetic argument vectors that it must
 turn down, or accept as empty input, BEFORE it launches anything.  tests/test_capi_rejections_host.py replays the table:
 an argument check that a later change loses, reorders or rewords shows up there, on a machine without a device.
@@ -12,6 +12,11 @@ aligned host buffer of 4096 bytes ("buf": host arrays, structs and tables of poi
 parameter the given value, every float 0.5, the stream NULL.  Kept: the cases that came back before a launch -- a
 non-zero status whose message neither begins with "launch of" nor contains "failed:" (both are HIP's verdict on an
 enqueue), or status 0 (empty input).  The other cases reached the runtime; they are printed, not recorded.
+
+The table only grows.  tests/golden/capi_rejections.json (BASE) is the table as it was first recorded, at ABI 36, and stays
+as it is; OUT holds BASE's rows, unchanged and in place, with the rows of the entry points added since (ABI 37:
+scr_filter3d_*) among them in header order.  main() refuses to write a table that loses or changes a row of BASE, and
+tests/test_filter3d_host.py checks the same of the committed file.
 """
 import ctypes as C
 import json
@@ -20,7 +25,8 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "tests", "golden", "capi_rejections.json")
+BASE = os.path.join(ROOT, "tests", "golden", "capi_rejections.json")
+OUT = os.path.join(ROOT, "tests", "golden", "capi_rejections_abi37.json")
 VECTORS = ("null_1", "null_-1", "null_0", "buf_1", "buf_-1", "buf_0")
 BUF_BYTES = 4096
 
@@ -72,6 +78,21 @@ def before_launch(rc, message):
     return rc == 0 or not (message.startswith("launch of") or "failed:" in message)
 
 
+def added_rows(base, table):
+    """The rows of `table` that are not rows of `base`; AssertionError unless `table` holds every row of `base`, unchanged
+    and in the same order (the table only grows)."""
+    it = iter(table)
+    extra = []
+    for row in base:
+        for got in it:
+            if got == row:
+                break
+            extra.append(got)
+        else:
+            raise AssertionError(f"the table lost or changed the recorded row {row}")
+    return extra + list(it)
+
+
 def main():
     sys.path.insert(0, ROOT)
     import torch
@@ -89,6 +110,9 @@ def main():
         print("dropped (reached the runtime):", row["name"], row["vector"], row["rc"], row["error"])
     missing = sorted(set(streamed_entry_points()) - {r["name"] for r in kept})
     assert not missing, f"no case of {missing} returns before a launch"
+    with open(BASE) as f:
+        new = added_rows(json.load(f), kept)
+    print(f"{len(new)} rows beyond {BASE}: {sorted({r['name'] for r in new})}")
     with open(OUT, "w") as f:
         f.write("[\n" + ",\n".join(json.dumps(r) for r in kept) + "\n]\n")
     print(f"{OUT}: {len(kept)} cases kept, {len(dropped)} dropped, {os.path.getsize(OUT)} bytes")
