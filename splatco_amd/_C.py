@@ -1,4 +1,5 @@
-"""ctypes binding of the C-ABI in include/splatco_raster.h (libsplatco_raster.so, gfx950).
+"""ctypes binding of the C-ABI in include/splatco_raster.h and of the family header include/splatco_bilagrid.h
+(libsplatco_raster.so, gfx950).
 
 This is the binding a maintainer of the reference would write in place of the pybind module
 `diff_gaussian_rasterization._C`.  There is NO fallback: if the HIP library
@@ -149,6 +150,18 @@ SIGNATURES = [
 ]
 SYMBOLS = [s[0] for s in SIGNATURES]
 
+# A family with a header of its own (include/splatco_bilagrid.h), in the same library: same layout as SIGNATURES, its own
+# version.  Launched through family_call(); tests/test_bilagrid_host.py checks every entry against that header.
+BILAGRID_ABI_VERSION = 1
+BILAGRID_SIGNATURES = [
+    ("scr_bilagrid_abi_version", i32),
+    ("scr_bilagrid_scratch_bytes", sz, i32, i32, i32, i32, i32),
+    ("scr_bilagrid_slice", i32, vp, i32, i32, i32, vp, i32, i32, vp, vp),
+    ("scr_bilagrid_slice_backward", i32, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, sz, vp),
+    ("scr_bilagrid_tv_add_grad", i32, vp, vp, i64, i32, i32, i32, f32, vp),
+]
+_FAMILY_NAMES = frozenset(s[0] for s in BILAGRID_SIGNATURES)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -157,13 +170,15 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C splatco_amd/csrc`). "
             "There is deliberately no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, restype, *argtypes in SIGNATURES:
+    for name, restype, *argtypes in SIGNATURES + BILAGRID_SIGNATURES:
         if not hasattr(lib, name):
             raise ImportError(f"{LIB_PATH} does not export {name}")
         f = getattr(lib, name)
         f.restype, f.argtypes = restype, argtypes
     if lib.scr_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {lib.scr_abi_version()}, expected {ABI_VERSION}")
+    if lib.scr_bilagrid_abi_version() != BILAGRID_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has bilateral-grid ABI version {lib.scr_bilagrid_abi_version()}, expected {BILAGRID_ABI_VERSION}")
     return lib
 
 
@@ -250,6 +265,18 @@ def call(name, *args, device=None, check=True):
     otherwise the first tensor argument's; it is current during the call, and the stream is the caller's current stream
     on it.  Every tensor argument must live on that device: ValueError otherwise, before anything is launched.  A non-zero
     status raises through check(); with check=False it is returned instead.  The function is looked up at call time."""
+    return _launch(name, args, device, check)
+
+
+def family_call(name, *args, device=None, check=True):
+    """call() for the streamed entry points of a family header (BILAGRID_SIGNATURES, include/splatco_bilagrid.h): any other
+    name is refused with ValueError before anything is looked up or launched; everything else is call()'s own code."""
+    if name not in _FAMILY_NAMES:
+        raise ValueError(f"family_call: {name} is not declared in include/splatco_bilagrid.h")
+    return _launch(name, args, device, check)
+
+
+def _launch(name, args, device, check):
     fn = getattr(lib, name)
     if device is not None:
         device = torch.device(device)

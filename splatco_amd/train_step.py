@@ -56,7 +56,8 @@ def sync_densification_stats(densifier, n_views, out, vis, device):
 
 def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, bucket=None,
                        consistency_weight=0.0, densifier=None, arena=None, iteration=None, tv_weight=0.0, sparse_adam=False,
-                       filter_3d=None, depth_targets=None, depth_masks=None, depth_weight=0.0, depth_options=None):
+                       filter_3d=None, bilateral_grid=None, bilagrid_tv_weight=10.0, depth_targets=None, depth_masks=None,
+                       depth_weight=0.0, depth_options=None):
     """views / gt_images: the identically ordered mv view list every rank holds; gt_images[i] is the
     [3,H,W] target of views[i] (host or device).  densifier: a splatco_amd.densify.AnchorDensifier; its
     accumulators receive the statistics of the LAST view of the list on every rank (sync_densification_stats).
@@ -85,8 +86,23 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
     anchors -- or when `iteration % filter_3d.every == 0`; every render() of the step then gets it.  The filter is a function
     of the parameters and the cameras alone: every rank computes the same values and nothing is exchanged.  None (the
     default): the step is the one without the argument.
+    bilateral_grid / bilagrid_tv_weight: a bilagrid.BilateralGrid (one learnable colour-correction grid per training view).
+    Every view's out["render"] goes through bilateral_grid(image, cam.uid) before view_loss; the depth and consistency terms
+    keep the uncorrected image.  bilateral_grid.grids.grad is cleared on entry like the model's gradients, and after the
+    backward pass bilagrid.tv_add_grad(grids, bilagrid_tv_weight) adds the grids' total-variation gradient once.  `optimizer`
+    steps the grids if it holds them in a group (adam.FusedAdam: {"params": [bilateral_grid.grids], "lr": 2e-3}).  The grids
+    are not part of a GradArena and their gradients are not exchanged, so more than one rank or an arena is refused.  None
+    (the default): the step is the one without the argument, bit for bit.
     Returns (local loss sum, last render dict, bucket or arena buffer)."""
     from .adam import FusedAdam, ShardedFusedAdam
+    if bilateral_grid is not None:
+        if world_info()[1] > 1:
+            raise NotImplementedError("collaborative_step: bilateral_grid on more than one rank is not built: the grids' gradients "
+                                      "would have to be summed over the ranks, and they are not among the exchanged parameters")
+        if arena is not None:
+            raise NotImplementedError("collaborative_step: bilateral_grid with a GradArena is not built: the grids are not in the "
+                                      "arena, so their gradients would be neither cleared nor summed with it")
+        bilateral_grid.grids.grad = None
     if sparse_adam:
         if isinstance(optimizer, ShardedFusedAdam):
             raise NotImplementedError("collaborative_step: sparse_adam with ShardedFusedAdam is not built: its flat per-rank slices "
@@ -148,7 +164,8 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
                 out = render(cam, pc, pipe, bg_color, visible_mask=vis, retain_grad=True, **render_options)
             with stage("loss"):
                 gt = gt.to(out["render"].device, non_blocking=True)
-                loss = view_loss(out["render"], gt, out["scaling"])
+                image = out["render"] if bilateral_grid is None else bilateral_grid(out["render"], cam.uid)
+                loss = view_loss(image, gt, out["scaling"])
                 if use_depth:
                     dev_k = out["render"].device
                     mask = None if local_masks is None or local_masks[k] is None else local_masks[k].to(dev_k, non_blocking=True)
@@ -183,6 +200,9 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
     if tv_weight and iteration is not None and tv_due(iteration):
         with stage("tv_loss"):
             pc.feat_planes.tv_loss(tv_weight)
+    if bilateral_grid is not None:
+        with stage("bilagrid_tv"):
+            bilateral_grid.tv_add_grad(bilagrid_tv_weight)
     if densifier is not None:
         with stage("training_statis"):
             sync_densification_stats(densifier, len(views), out, vis, device)
