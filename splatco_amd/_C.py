@@ -1,5 +1,5 @@
-"""ctypes binding of the C-ABI in include/splatco_raster.h and of the family header include/splatco_bilagrid.h
-(libsplatco_raster.so, gfx950).
+"""ctypes binding of the C-ABI in include/splatco_raster.h and of the family headers include/splatco_bilagrid.h and
+include/splatco_normals.h (libsplatco_raster.so, gfx950).
 
 This is the binding a maintainer of the reference would write in place of the pybind module
 `diff_gaussian_rasterization._C`.  There is NO fallback: if the HIP library
@@ -160,7 +160,19 @@ BILAGRID_SIGNATURES = [
     ("scr_bilagrid_slice_backward", i32, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, sz, vp),
     ("scr_bilagrid_tv_add_grad", i32, vp, vp, i64, i32, i32, i32, f32, vp),
 ]
-_FAMILY_NAMES = frozenset(s[0] for s in BILAGRID_SIGNATURES)
+
+# The depth-map normals and the normal-prior loss (include/splatco_normals.h); tests/test_normals_host.py checks every entry.
+NORMALS_ABI_VERSION = 1
+NORMALS_SIGNATURES = [
+    ("scr_normals_abi_version", i32),
+    ("scr_normals_map", i32, i32, i32, vp, vp, f64, f64, f64, f64, vp, f32, vp, vp),
+    ("scr_normals_map_backward", i32, i32, i32, vp, vp, f64, f64, f64, f64, vp, f32, vp, vp, vp, vp),
+    ("scr_normals_loss_scratch_bytes", sz, i32, i32),
+    ("scr_normals_loss_forward", i32, i32, i32, vp, vp, vp, vp, i32, f64, f64, f64, f64, f32, vp, vp, vp),
+    ("scr_normals_loss_backward", i32, i32, i32, vp, vp, vp, vp, i32, f64, f64, f64, f64, f32, vp, vp, vp, vp),
+]
+_FAMILY_HEADERS = {"include/splatco_bilagrid.h": BILAGRID_SIGNATURES, "include/splatco_normals.h": NORMALS_SIGNATURES}
+_FAMILY_NAMES = frozenset(s[0] for sigs in _FAMILY_HEADERS.values() for s in sigs)
 
 
 def _load():
@@ -170,7 +182,7 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C splatco_amd/csrc`). "
             "There is deliberately no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, restype, *argtypes in SIGNATURES + BILAGRID_SIGNATURES:
+    for name, restype, *argtypes in SIGNATURES + BILAGRID_SIGNATURES + NORMALS_SIGNATURES:
         if not hasattr(lib, name):
             raise ImportError(f"{LIB_PATH} does not export {name}")
         f = getattr(lib, name)
@@ -179,6 +191,8 @@ def _load():
         raise ImportError(f"{LIB_PATH} has ABI version {lib.scr_abi_version()}, expected {ABI_VERSION}")
     if lib.scr_bilagrid_abi_version() != BILAGRID_ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has bilateral-grid ABI version {lib.scr_bilagrid_abi_version()}, expected {BILAGRID_ABI_VERSION}")
+    if lib.scr_normals_abi_version() != NORMALS_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has normals ABI version {lib.scr_normals_abi_version()}, expected {NORMALS_ABI_VERSION}")
     return lib
 
 
@@ -269,10 +283,11 @@ def call(name, *args, device=None, check=True):
 
 
 def family_call(name, *args, device=None, check=True):
-    """call() for the streamed entry points of a family header (BILAGRID_SIGNATURES, include/splatco_bilagrid.h): any other
-    name is refused with ValueError before anything is looked up or launched; everything else is call()'s own code."""
+    """call() for the streamed entry points of the family headers (BILAGRID_SIGNATURES, include/splatco_bilagrid.h;
+    NORMALS_SIGNATURES, include/splatco_normals.h): any other name is refused with ValueError before anything is looked up or
+    launched; everything else is call()'s own code."""
     if name not in _FAMILY_NAMES:
-        raise ValueError(f"family_call: {name} is not declared in include/splatco_bilagrid.h")
+        raise ValueError(f"family_call: {name} is not declared in {' or '.join(_FAMILY_HEADERS)}")
     return _launch(name, args, device, check)
 
 

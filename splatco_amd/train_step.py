@@ -12,6 +12,7 @@ import torch.distributed as dist
 
 from .losses import depth_loss, view_loss
 from .multiview import GradArena, allreduce_gradients, collectives_on, consistency_loss, shard_views, world_info
+from .normals import normal_loss
 from .renderer import prefilter_voxel, render
 from .tv import tv_due
 from ._C import stage
@@ -56,8 +57,9 @@ def sync_densification_stats(densifier, n_views, out, vis, device):
 
 def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, bucket=None,
                        consistency_weight=0.0, densifier=None, arena=None, iteration=None, tv_weight=0.0, sparse_adam=False,
-                       filter_3d=None, bilateral_grid=None, bilagrid_tv_weight=10.0, depth_targets=None, depth_masks=None,
-                       depth_weight=0.0, depth_options=None):
+                       filter_3d=None, bilateral_grid=None, bilagrid_tv_weight=10.0, normal_targets=None, normal_masks=None,
+                       normal_weight=0.0, normal_options=None, depth_targets=None, depth_masks=None, depth_weight=0.0,
+                       depth_options=None):
     """views / gt_images: the identically ordered mv view list every rank holds; gt_images[i] is the
     [3,H,W] target of views[i] (host or device).  densifier: a splatco_amd.densify.AnchorDensifier; its
     accumulators receive the statistics of the LAST view of the list on every rank (sync_densification_stats).
@@ -81,6 +83,11 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
     mask; every view is rendered with aux=True and depth_weight * depth_loss(out["depth"], out["alpha"], target, mask,
     **depth_options) is added to that view's loss.  Both lists are sharded as gt_images.  With the default weight of 0 the
     step is the one without these arguments, bit for bit: render() is called without aux and nothing else runs.
+    normal_targets / normal_masks / normal_weight / normal_options: normal supervision (normals.normal_loss), with the same
+    rules.  With normal_weight > 0, normal_targets[i] is the [3,H,W] camera-frame normal prior of views[i] (host or device),
+    normal_masks[i] (optional list; an entry may be None) its mask; every view is rendered with aux=True and normal_weight *
+    normal_loss(out["depth"], out["alpha"], target, cam, mask, **normal_options) is added to that view's loss.  Both lists are
+    sharded as gt_images.  With the default weight of 0 the step is the one without these arguments, bit for bit.
     filter_3d: a filter3d.Filter3D (Mip-Splatting's 3D smoothing filter).  On entry it is recomputed from the model's anchors
     (filter_3d.update(pc)) when it is stale -- never updated, or adjust_anchor / prune_anchor / sort_anchors replaced the
     anchors -- or when `iteration % filter_3d.every == 0`; every render() of the step then gets it.  The filter is a function
@@ -120,7 +127,14 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
         for name, lst in (("depth_targets", depth_targets), ("depth_masks", depth_masks)):
             if lst is not None and len(lst) != len(views):
                 raise ValueError(f"collaborative_step: {len(lst)} {name} for {len(views)} views")
-    render_options = {"aux": True} if use_depth else {}
+    use_normals = normal_weight > 0
+    if use_normals:
+        if normal_targets is None:
+            raise ValueError("collaborative_step: normal_weight > 0 needs normal_targets")
+        for name, lst in (("normal_targets", normal_targets), ("normal_masks", normal_masks)):
+            if lst is not None and len(lst) != len(views):
+                raise ValueError(f"collaborative_step: {len(lst)} {name} for {len(views)} views")
+    render_options = {"aux": True} if use_depth or use_normals else {}
     if filter_3d is not None:
         from .filter3d import Filter3D
         if isinstance(filter_3d, Filter3D) and filter_3d.due(pc, iteration):
@@ -153,6 +167,8 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
     union = None
     local_targets = shard_views(depth_targets) if use_depth else None
     local_masks = shard_views(depth_masks) if use_depth and depth_masks is not None else None
+    local_normals = shard_views(normal_targets) if use_normals else None
+    local_normal_masks = shard_views(normal_masks) if use_normals and normal_masks is not None else None
     try:
         # (stage(): opt-in roctx ranges, _C.markers_enable / SPLATCO_MARKERS=1; nothing when off)
         for k, (cam, gt) in enumerate(zip(shard_views(views), shard_views(gt_images))):
@@ -171,6 +187,12 @@ def collaborative_step(pc, views, gt_images, pipe, bg_color, optimizer=None, buc
                     mask = None if local_masks is None or local_masks[k] is None else local_masks[k].to(dev_k, non_blocking=True)
                     loss = loss + depth_weight * depth_loss(out["depth"], out["alpha"], local_targets[k].to(dev_k, non_blocking=True),
                                                             mask, **(depth_options or {}))
+                if use_normals:
+                    dev_k = out["render"].device
+                    mask = (None if local_normal_masks is None or local_normal_masks[k] is None
+                            else local_normal_masks[k].to(dev_k, non_blocking=True))
+                    loss = loss + normal_weight * normal_loss(out["depth"], out["alpha"], local_normals[k].to(dev_k, non_blocking=True),
+                                                              cam, mask, **(normal_options or {}))
                 total = loss if total is None else total + loss
             if consistency_weight:
                 rendered.append((rank + k * world, out["render"], gt))
