@@ -1,5 +1,5 @@
-"""ctypes binding of the C-ABI in include/splatco_raster.h and of the family headers include/splatco_bilagrid.h and
-include/splatco_normals.h (libsplatco_raster.so, gfx950).
+"""ctypes binding of the C-ABI in include/splatco_raster.h and of the family headers include/splatco_bilagrid.h,
+include/splatco_normals.h and include/splatco_tsdf.h (libsplatco_raster.so, gfx950).
 
 This is the binding a maintainer of the reference would write in place of the pybind module
 `diff_gaussian_rasterization._C`.  There is NO fallback: if the HIP library
@@ -171,7 +171,28 @@ NORMALS_SIGNATURES = [
     ("scr_normals_loss_forward", i32, i32, i32, vp, vp, vp, vp, i32, f64, f64, f64, f64, f32, vp, vp, vp),
     ("scr_normals_loss_backward", i32, i32, i32, vp, vp, vp, vp, i32, f64, f64, f64, f64, f32, vp, vp, vp, vp),
 ]
-_FAMILY_HEADERS = {"include/splatco_bilagrid.h": BILAGRID_SIGNATURES, "include/splatco_normals.h": NORMALS_SIGNATURES}
+
+
+class TsdfView(C.Structure):
+    """struct scr_tsdf_view (include/splatco_tsdf.h): one view of scr_tsdf_integrate."""
+    _fields_ = [("depth", vp), ("alpha", vp), ("image", vp), ("mask", vp), ("H", i32), ("W", i32), ("mask_kind", i32),
+                ("min_alpha", f32), ("fx", f64), ("fy", f64), ("cx", f64), ("cy", f64), ("w2c", f64 * 12), ("near", f64)]
+
+
+# TSDF fusion and mesh extraction (include/splatco_tsdf.h); tests/test_tsdf_host.py checks every entry and the struct.
+TSDF_ABI_VERSION = 1
+TSDF_MAX_VIEWS = 16                                 # SCR_TSDF_MAX_VIEWS
+TSDF_SIGNATURES = [
+    ("scr_tsdf_abi_version", i32),
+    ("scr_tsdf_integrate", i32, i32, i32, i32, vp, f32, f64, f32, vp, vp, vp, i32, P(TsdfView), vp),
+    ("scr_tsdf_extract_scratch_bytes", sz, i32, i32, i32),
+    ("scr_tsdf_extract_vertices_plan", i32, i32, i32, i32, vp, vp, f32, vp, P(i64), vp),
+    ("scr_tsdf_extract_vertices_run", i32, i32, i32, i32, vp, f32, vp, vp, vp, f32, vp, i64, vp, vp, vp, vp),
+    ("scr_tsdf_extract_faces_plan", i32, i32, i32, i32, vp, vp, f32, vp, P(i64), vp),
+    ("scr_tsdf_extract_faces_run", i32, i32, i32, i32, vp, vp, f32, vp, i64, vp, i64, vp, vp),
+]
+_FAMILY_HEADERS = {"include/splatco_bilagrid.h": BILAGRID_SIGNATURES, "include/splatco_normals.h": NORMALS_SIGNATURES,
+                   "include/splatco_tsdf.h": TSDF_SIGNATURES}
 _FAMILY_NAMES = frozenset(s[0] for sigs in _FAMILY_HEADERS.values() for s in sigs)
 
 
@@ -182,7 +203,7 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C splatco_amd/csrc`). "
             "There is deliberately no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, restype, *argtypes in SIGNATURES + BILAGRID_SIGNATURES + NORMALS_SIGNATURES:
+    for name, restype, *argtypes in SIGNATURES + BILAGRID_SIGNATURES + NORMALS_SIGNATURES + TSDF_SIGNATURES:
         if not hasattr(lib, name):
             raise ImportError(f"{LIB_PATH} does not export {name}")
         f = getattr(lib, name)
@@ -193,6 +214,8 @@ def _load():
         raise ImportError(f"{LIB_PATH} has bilateral-grid ABI version {lib.scr_bilagrid_abi_version()}, expected {BILAGRID_ABI_VERSION}")
     if lib.scr_normals_abi_version() != NORMALS_ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has normals ABI version {lib.scr_normals_abi_version()}, expected {NORMALS_ABI_VERSION}")
+    if lib.scr_tsdf_abi_version() != TSDF_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has TSDF ABI version {lib.scr_tsdf_abi_version()}, expected {TSDF_ABI_VERSION}")
     return lib
 
 
@@ -284,8 +307,8 @@ def call(name, *args, device=None, check=True):
 
 def family_call(name, *args, device=None, check=True):
     """call() for the streamed entry points of the family headers (BILAGRID_SIGNATURES, include/splatco_bilagrid.h;
-    NORMALS_SIGNATURES, include/splatco_normals.h): any other name is refused with ValueError before anything is looked up or
-    launched; everything else is call()'s own code."""
+    NORMALS_SIGNATURES, include/splatco_normals.h; TSDF_SIGNATURES, include/splatco_tsdf.h): any other name is refused with
+    ValueError before anything is looked up or launched; everything else is call()'s own code."""
     if name not in _FAMILY_NAMES:
         raise ValueError(f"family_call: {name} is not declared in {' or '.join(_FAMILY_HEADERS)}")
     return _launch(name, args, device, check)

@@ -160,3 +160,82 @@ def load_scene(model, model_path, iteration, device=None):                      
     model.feat_planes.load_state_dict(ck[0], strict=False)
     model.contractor_state = {k: v for k, v in dict(ck[1]).items()} if len(ck) > 1 else {}
     return model
+
+
+def write_ply_mesh(path, vertices, faces, colors=None):
+    """A triangle mesh as binary little-endian PLY: vertices [Nv, 3] float (x y z), optionally colors [Nv, 3] in [0, 1] stored
+    as uchar red green blue (rounded, clamped), faces [Nf, 3] int as `property list uchar int vertex_indices`.  Tensors
+    (any device) and arrays are taken alike."""
+    host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    v = np.ascontiguousarray(host(vertices), dtype="<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(host(faces), dtype="<i4").reshape(-1, 3)
+    props = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}",
+              "property float x", "property float y", "property float z"]
+    if colors is not None:
+        c = np.asarray(host(colors), dtype=np.float64).reshape(-1, 3)
+        if c.shape[0] != v.shape[0]:
+            raise ValueError(f"write_ply_mesh: {c.shape[0]} colours for {v.shape[0]} vertices")
+        c = np.rint(np.clip(np.nan_to_num(c, nan=0.0), 0.0, 1.0) * 255.0).astype("u1")
+        props += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    header += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    vert = np.empty(v.shape[0], dtype=props)
+    vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        vert["red"], vert["green"], vert["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    face = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    face["n"], face["i"] = 3, f
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(vert.tobytes())
+        out.write(face.tobytes())
+
+
+def read_ply_mesh(path):
+    """-> (vertices [Nv, 3] float32, faces [Nf, 3] int32, colors [Nv, 3] float32 in [0, 1] (the stored byte / 255) or None),
+    numpy arrays, of a binary little-endian triangle PLY as write_ply_mesh writes it: a `vertex` element with x y z (and
+    possibly red green blue among other scalar properties), then a `face` element whose only property is a list of three
+    indices per face."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, elements = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: truncated PLY header")
+            tok = line.decode("ascii").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property":
+                if not elements:
+                    raise ValueError(f"{path}: a property before any element")
+                elements[-1][2].append(tok[1:])
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError(f"{path}: mesh PLY files are read in binary_little_endian only, not {fmt}")
+        if [e[0] for e in elements] != ["vertex", "face"]:
+            raise ValueError(f"{path}: expected the elements vertex, face; found {[e[0] for e in elements]}")
+        (_, nv, vprops), (_, nf, fprops) = elements
+        if any(p[0] == "list" for p in vprops):
+            raise ValueError(f"{path}: list properties on `vertex` are not supported")
+        vdt = np.dtype([(p[1], "<" + _PLY_TYPES[p[0]]) for p in vprops])
+        vert = np.frombuffer(f.read(nv * vdt.itemsize), dtype=vdt, count=nv)
+        if len(fprops) != 1 or fprops[0][0] != "list":
+            raise ValueError(f"{path}: the face element must hold one list property")
+        fdt = np.dtype([("n", "<" + _PLY_TYPES[fprops[0][1]]), ("i", "<" + _PLY_TYPES[fprops[0][2]], (3,))])
+        face = np.frombuffer(f.read(nf * fdt.itemsize), dtype=fdt, count=nf)
+        if nf and not (face["n"] == 3).all():
+            raise ValueError(f"{path}: only triangles are read")
+    vertices = np.stack((vert["x"], vert["y"], vert["z"]), axis=1).astype(np.float32) if nv else np.zeros((0, 3), np.float32)
+    colors = None
+    if all(n in vert.dtype.names for n in ("red", "green", "blue")):
+        colors = (np.stack((vert["red"], vert["green"], vert["blue"]), axis=1) / 255.0).astype(np.float32).reshape(-1, 3)
+    return vertices, face["i"].astype(np.int32).reshape(-1, 3), colors
