@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI in include/splatco_raster.h and of the family headers include/splatco_bilagrid.h,
-include/splatco_normals.h and include/splatco_tsdf.h (libsplatco_raster.so, gfx950).
+include/splatco_normals.h, include/splatco_tsdf.h and include/splatco_mesh.h (libsplatco_raster.so, gfx950).
 
 This is the binding a maintainer of the reference would write in place of the pybind module
 `diff_gaussian_rasterization._C`.  There is NO fallback: if the HIP library
@@ -191,8 +191,23 @@ TSDF_SIGNATURES = [
     ("scr_tsdf_extract_faces_plan", i32, i32, i32, i32, vp, vp, f32, vp, P(i64), vp),
     ("scr_tsdf_extract_faces_run", i32, i32, i32, i32, vp, vp, f32, vp, i64, vp, i64, vp, vp),
 ]
+
+# Mesh clean-up: components, size filter, vertex normals (include/splatco_mesh.h); tests/test_mesh_host.py checks every entry.
+MESH_ABI_VERSION = 1
+MESH_SIGNATURES = [
+    ("scr_mesh_abi_version", i32),
+    ("scr_mesh_scratch_bytes", sz, i64, i64),
+    ("scr_mesh_components", i32, i64, i64, vp, vp, vp, vp, vp, vp),
+    ("scr_mesh_roots_plan", i32, i64, vp, vp, vp, P(i64), vp),
+    ("scr_mesh_roots_run", i32, i64, vp, vp, vp, i64, vp, vp, vp),
+    ("scr_mesh_vertices_plan", i32, i64, vp, vp, i32, vp, P(i64), vp),
+    ("scr_mesh_vertices_run", i32, i64, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp),
+    ("scr_mesh_faces_plan", i32, i64, vp, vp, vp, i32, vp, P(i64), vp),
+    ("scr_mesh_faces_run", i32, i64, vp, vp, vp, i32, vp, i64, vp, vp, vp),
+    ("scr_mesh_vertex_normals", i32, i64, i64, vp, vp, vp, vp, vp),
+]
 _FAMILY_HEADERS = {"include/splatco_bilagrid.h": BILAGRID_SIGNATURES, "include/splatco_normals.h": NORMALS_SIGNATURES,
-                   "include/splatco_tsdf.h": TSDF_SIGNATURES}
+                   "include/splatco_tsdf.h": TSDF_SIGNATURES, "include/splatco_mesh.h": MESH_SIGNATURES}
 _FAMILY_NAMES = frozenset(s[0] for sigs in _FAMILY_HEADERS.values() for s in sigs)
 
 
@@ -203,7 +218,7 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C splatco_amd/csrc`). "
             "There is deliberately no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, restype, *argtypes in SIGNATURES + BILAGRID_SIGNATURES + NORMALS_SIGNATURES + TSDF_SIGNATURES:
+    for name, restype, *argtypes in SIGNATURES + BILAGRID_SIGNATURES + NORMALS_SIGNATURES + TSDF_SIGNATURES + MESH_SIGNATURES:
         if not hasattr(lib, name):
             raise ImportError(f"{LIB_PATH} does not export {name}")
         f = getattr(lib, name)
@@ -216,6 +231,8 @@ def _load():
         raise ImportError(f"{LIB_PATH} has normals ABI version {lib.scr_normals_abi_version()}, expected {NORMALS_ABI_VERSION}")
     if lib.scr_tsdf_abi_version() != TSDF_ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has TSDF ABI version {lib.scr_tsdf_abi_version()}, expected {TSDF_ABI_VERSION}")
+    if lib.scr_mesh_abi_version() != MESH_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has mesh ABI version {lib.scr_mesh_abi_version()}, expected {MESH_ABI_VERSION}")
     return lib
 
 
@@ -307,8 +324,9 @@ def call(name, *args, device=None, check=True):
 
 def family_call(name, *args, device=None, check=True):
     """call() for the streamed entry points of the family headers (BILAGRID_SIGNATURES, include/splatco_bilagrid.h;
-    NORMALS_SIGNATURES, include/splatco_normals.h; TSDF_SIGNATURES, include/splatco_tsdf.h): any other name is refused with
-    ValueError before anything is looked up or launched; everything else is call()'s own code."""
+    NORMALS_SIGNATURES, include/splatco_normals.h; TSDF_SIGNATURES, include/splatco_tsdf.h; MESH_SIGNATURES,
+    include/splatco_mesh.h): any other name is refused with ValueError before anything is looked up or launched; everything
+    else is call()'s own code."""
     if name not in _FAMILY_NAMES:
         raise ValueError(f"family_call: {name} is not declared in {' or '.join(_FAMILY_HEADERS)}")
     return _launch(name, args, device, check)

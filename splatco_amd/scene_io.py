@@ -162,16 +162,22 @@ def load_scene(model, model_path, iteration, device=None):                      
     return model
 
 
-def write_ply_mesh(path, vertices, faces, colors=None):
-    """A triangle mesh as binary little-endian PLY: vertices [Nv, 3] float (x y z), optionally colors [Nv, 3] in [0, 1] stored
-    as uchar red green blue (rounded, clamped), faces [Nf, 3] int as `property list uchar int vertex_indices`.  Tensors
-    (any device) and arrays are taken alike."""
+def write_ply_mesh(path, vertices, faces, colors=None, normals=None):
+    """A triangle mesh as binary little-endian PLY: vertices [Nv, 3] float (x y z), optionally normals [Nv, 3] float (nx ny nz,
+    right after x y z), optionally colors [Nv, 3] in [0, 1] stored as uchar red green blue (rounded, clamped), faces [Nf, 3]
+    int as `property list uchar int vertex_indices`.  Tensors (any device) and arrays are taken alike."""
     host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
     v = np.ascontiguousarray(host(vertices), dtype="<f4").reshape(-1, 3)
     f = np.ascontiguousarray(host(faces), dtype="<i4").reshape(-1, 3)
     props = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}",
               "property float x", "property float y", "property float z"]
+    if normals is not None:
+        n = np.ascontiguousarray(host(normals), dtype="<f4").reshape(-1, 3)
+        if n.shape[0] != v.shape[0]:
+            raise ValueError(f"write_ply_mesh: {n.shape[0]} normals for {v.shape[0]} vertices")
+        props += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
     if colors is not None:
         c = np.asarray(host(colors), dtype=np.float64).reshape(-1, 3)
         if c.shape[0] != v.shape[0]:
@@ -182,6 +188,8 @@ def write_ply_mesh(path, vertices, faces, colors=None):
     header += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     vert = np.empty(v.shape[0], dtype=props)
     vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        vert["nx"], vert["ny"], vert["nz"] = n[:, 0], n[:, 1], n[:, 2]
     if colors is not None:
         vert["red"], vert["green"], vert["blue"] = c[:, 0], c[:, 1], c[:, 2]
     face = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
@@ -193,11 +201,11 @@ def write_ply_mesh(path, vertices, faces, colors=None):
         out.write(face.tobytes())
 
 
-def read_ply_mesh(path):
+def read_ply_mesh(path, normals=False):
     """-> (vertices [Nv, 3] float32, faces [Nf, 3] int32, colors [Nv, 3] float32 in [0, 1] (the stored byte / 255) or None),
     numpy arrays, of a binary little-endian triangle PLY as write_ply_mesh writes it: a `vertex` element with x y z (and
     possibly red green blue among other scalar properties), then a `face` element whose only property is a list of three
-    indices per face."""
+    indices per face.  normals=True: a fourth array, the nx ny nz of the file [Nv, 3] float32, or None where it has none."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -238,4 +246,9 @@ def read_ply_mesh(path):
     colors = None
     if all(n in vert.dtype.names for n in ("red", "green", "blue")):
         colors = (np.stack((vert["red"], vert["green"], vert["blue"]), axis=1) / 255.0).astype(np.float32).reshape(-1, 3)
-    return vertices, face["i"].astype(np.int32).reshape(-1, 3), colors
+    if not normals:
+        return vertices, face["i"].astype(np.int32).reshape(-1, 3), colors
+    nrm = None
+    if all(n in vert.dtype.names for n in ("nx", "ny", "nz")):
+        nrm = np.stack((vert["nx"], vert["ny"], vert["nz"]), axis=1).astype(np.float32).reshape(-1, 3)
+    return vertices, face["i"].astype(np.int32).reshape(-1, 3), colors, nrm

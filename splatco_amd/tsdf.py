@@ -33,9 +33,10 @@ triangle, wound counter-clockwise seen from the free-space side.  The mesh is in
     vertices, faces, colors = vol.extract()
     scene_io.write_ply_mesh("mesh.ply", vertices, faces, colors)
 
-or extract_mesh(views, pc, pipe, bg, voxel_size) for all of it.  Not built: sparse or hashed volumes and unbounded scenes, mesh
-clean-up (largest components, decimation, smoothing), vertex normals, texture baking, a weight other than 1 per observation,
-bilinear depth lookup, gradients, multi-rank fusion.
+or extract_mesh(views, pc, pipe, bg, voxel_size) for all of it.  Component filtering and vertex normals of the extracted mesh
+are splatco_amd.mesh's (extract_mesh(..., keep_largest=50, min_faces=50) ends in its clean_mesh).  Not built: sparse or hashed
+volumes and unbounded scenes, decimation, smoothing, texture baking, a weight other than 1 per observation, bilinear depth
+lookup, gradients, multi-rank fusion.
 
 Every launch goes through _C.family_call.  There is no CPU path: a CPU tensor is a ValueError."""
 import ctypes
@@ -287,11 +288,13 @@ class TSDFVolume:
 
 
 def extract_mesh(views, pc, pipe, bg, voxel_size, bounds=None, trunc=None, min_alpha=0.5, antialiased=None, filter_3d=None,
-                 color=True):
+                 color=True, keep_largest=None, min_faces=None):
     """Render every view in evaluation mode (evaluate._eval_mode, no_grad, prefilter_voxel then render(aux=True), as
     evaluate.render_views does), fuse depth, alpha and (color=True) the image of each into one volume as it is rendered, and
     extract the mesh: (vertices [Nv, 3] float32, faces [Nf, 3] int32, colors [Nv, 3] float32 or None) on the device.
-    bounds: (lo, hi); None takes the bounding box of the anchors padded by trunc (default 4 voxel_size)."""
+    bounds: (lo, hi); None takes the bounding box of the anchors padded by trunc (default 4 voxel_size).  keep_largest /
+    min_faces: where either is given, the mesh goes through mesh.clean_mesh (2DGS's post_process_mesh uses 50) before it is
+    returned; with both None nothing of that module runs."""
     from . import knn_grid
     from .evaluate import _eval_mode
     from .renderer import prefilter_voxel, render
@@ -312,4 +315,7 @@ def extract_mesh(views, pc, pipe, bg, voxel_size, bounds=None, trunc=None, min_a
             out = render(view, pc, pipe, bg, visible_mask=vis, aux=True, **extra)
             vol._integrate("extract_mesh", [out["depth"]], [out["alpha"]], [view], [out["render"]] if color else None, None,
                            min_alpha, 0.05, 1)
-    return vol.extract()
+    if keep_largest is None and min_faces is None:
+        return vol.extract()
+    from .mesh import clean_mesh
+    return clean_mesh(*vol.extract(), keep_largest=keep_largest, min_faces=min_faces)[:3]
