@@ -1,5 +1,6 @@
 """ctypes binding of the C-ABI in include/splatco_raster.h and of the family headers include/splatco_bilagrid.h,
-include/splatco_normals.h, include/splatco_tsdf.h and include/splatco_mesh.h (libsplatco_raster.so, gfx950).
+include/splatco_normals.h, include/splatco_tsdf.h, include/splatco_mesh.h and include/splatco_surfeval.h
+(libsplatco_raster.so, gfx950).
 
 This is the binding a maintainer of the reference would write in place of the pybind module
 `diff_gaussian_rasterization._C`.  There is NO fallback: if the HIP library
@@ -206,8 +207,22 @@ MESH_SIGNATURES = [
     ("scr_mesh_faces_run", i32, i64, vp, vp, vp, i32, vp, i64, vp, vp, vp),
     ("scr_mesh_vertex_normals", i32, i64, i64, vp, vp, vp, vp, vp),
 ]
+
+# Mesh evaluation: surface sampling, cross-set nearest neighbour, score (include/splatco_surfeval.h);
+# tests/test_surfeval_host.py checks every entry.
+SURFEVAL_ABI_VERSION = 1
+SURFEVAL_MAX_THRESHOLDS = 8                         # SCR_SURFEVAL_MAX_THRESHOLDS
+SURFEVAL_SIGNATURES = [
+    ("scr_surfeval_abi_version", i32),
+    ("scr_surfeval_score_scratch_bytes", sz, i64),
+    ("scr_surfeval_face_counts", i32, i64, vp, vp, f64, C.c_uint32, vp, vp),
+    ("scr_surfeval_sample", i32, i64, i64, vp, vp, vp, C.c_uint32, vp, vp, vp),
+    ("scr_surfeval_nearest", i32, i64, i64, P(f32), vp, vp, vp, vp, vp, f32, vp, vp, vp),
+    ("scr_surfeval_score", i32, i64, vp, i32, P(f32), vp, vp, vp),
+]
 _FAMILY_HEADERS = {"include/splatco_bilagrid.h": BILAGRID_SIGNATURES, "include/splatco_normals.h": NORMALS_SIGNATURES,
-                   "include/splatco_tsdf.h": TSDF_SIGNATURES, "include/splatco_mesh.h": MESH_SIGNATURES}
+                   "include/splatco_tsdf.h": TSDF_SIGNATURES, "include/splatco_mesh.h": MESH_SIGNATURES,
+                   "include/splatco_surfeval.h": SURFEVAL_SIGNATURES}
 _FAMILY_NAMES = frozenset(s[0] for sigs in _FAMILY_HEADERS.values() for s in sigs)
 
 
@@ -218,7 +233,8 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C splatco_amd/csrc`). "
             "There is deliberately no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, restype, *argtypes in SIGNATURES + BILAGRID_SIGNATURES + NORMALS_SIGNATURES + TSDF_SIGNATURES + MESH_SIGNATURES:
+    for name, restype, *argtypes in (SIGNATURES + BILAGRID_SIGNATURES + NORMALS_SIGNATURES + TSDF_SIGNATURES + MESH_SIGNATURES
+                                     + SURFEVAL_SIGNATURES):
         if not hasattr(lib, name):
             raise ImportError(f"{LIB_PATH} does not export {name}")
         f = getattr(lib, name)
@@ -233,6 +249,8 @@ def _load():
         raise ImportError(f"{LIB_PATH} has TSDF ABI version {lib.scr_tsdf_abi_version()}, expected {TSDF_ABI_VERSION}")
     if lib.scr_mesh_abi_version() != MESH_ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has mesh ABI version {lib.scr_mesh_abi_version()}, expected {MESH_ABI_VERSION}")
+    if lib.scr_surfeval_abi_version() != SURFEVAL_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has mesh-evaluation ABI version {lib.scr_surfeval_abi_version()}, expected {SURFEVAL_ABI_VERSION}")
     return lib
 
 
@@ -325,7 +343,7 @@ def call(name, *args, device=None, check=True):
 def family_call(name, *args, device=None, check=True):
     """call() for the streamed entry points of the family headers (BILAGRID_SIGNATURES, include/splatco_bilagrid.h;
     NORMALS_SIGNATURES, include/splatco_normals.h; TSDF_SIGNATURES, include/splatco_tsdf.h; MESH_SIGNATURES,
-    include/splatco_mesh.h): any other name is refused with ValueError before anything is looked up or launched; everything
+    include/splatco_mesh.h; SURFEVAL_SIGNATURES, include/splatco_surfeval.h): any other name is refused with ValueError before anything is looked up or launched; everything
     else is call()'s own code."""
     if name not in _FAMILY_NAMES:
         raise ValueError(f"family_call: {name} is not declared in {' or '.join(_FAMILY_HEADERS)}")

@@ -55,6 +55,15 @@ def grid(lo, hi, N, h=None, per_cell=2.0):
     return h, n, slack
 
 
+def cell_order(pts, grid_host):
+    """The order that walks the device points [N,3] float32 by their CLAMPED cell key under ANOTHER set's grid descriptor
+    (`buckets(...)[0]`): int64 [N].  What a search from one set into another sorts its queries by (surface_eval.nearest)."""
+    from . import _C
+    keys = torch.empty(pts.shape[0], dtype=torch.long, device=pts.device)
+    _C.call("scr_knn_cell_keys", pts.shape[0], grid_host, pts, keys)
+    return torch.sort(keys).indices
+
+
 def buckets(pts):
     """The device points [N,3] float32 bucketed for scr_knn / scr_knn3_dist2: (grid_host, points in cell order, their
     original indices, cell_start)."""
