@@ -450,7 +450,13 @@ int scr_anchor_gather(int64_t V, const int64_t* visible_index, const float* anch
  * scr_norm_linear_backward leaves in coef_out), nl_dy [V,32] (row stride nl_lddy, 16-byte aligned) and nl_x = g_fea [V,71]
  * (row stride nl_ldx) the backward forms those rows itself, workgroup by workgroup, and ADDS them to whatever d_g_fea
  * carries (normally NULL then): 1.15 GB less written and read at configs[2], and the whole tail of a step's backward pass
- * -- dx and the gather -- runs per anchor RANGE, so that a range's exchange overlaps the next range's kernels. */
+ * -- dx and the gather -- runs per anchor RANGE, so that a range's exchange overlaps the next range's kernels.
+ * nl_x may have ANY row stride nl_ldx >= 71 (71 = packed rows, 72 = what scr_anchor_gather writes with g_fea_ld = 72, more
+ * = the columns of a wider matrix) at ANY 4-byte aligned address: a row that starts on a 16-byte boundary is read in
+ * 16-byte pieces, any other row float by float, row by row.  Only the 71 columns are read.  nl_dy and nl_coef must be
+ * 16-byte aligned and nl_lddy a multiple of 4 (the call is refused otherwise).
+ * grid_scaling (the forward's grid_scaling_out) may be NULL when d_grid_scaling, d_g_fea and nl_coef all are: nothing
+ * reaches the scaling columns then, and their gradient is 0. */
 int scr_anchor_gather_backward(int64_t N, int64_t V, const int64_t* inverse_index, const float* grid_scaling, const float* d_feat,
                                const float* d_anchor, const float* d_offsets, const float* d_grid_scaling,
                                const float* d_g_fea, int32_t g_fea_ld, float* g_anchor_feat, float* g_anchor,

@@ -85,7 +85,7 @@ static int64_t anchor_gather_stat_buffer_rows(int64_t V) {      // rows of the b
 __global__ void __launch_bounds__(2 * NL_DP) anchor_gather_stat_reduce_kernel(int64_t tiles, float* __restrict__ stats) {
     const float* in = stats + (size_t)AG_MAX_WGS * 2 * NL_DP;
     float a = 0.0f;
-    if (threadIdx.x % NL_DP < AG_LD)      // (the tiles write 72 of a row's 80 columns)
+    if (threadIdx.x % NL_DP < AG_LD)      // (columns 72.. of the tiles' rows are zeros)
         for (int64_t t = blockIdx.x; t < tiles; t += AG_MAX_WGS) a += in[(size_t)t * 2 * NL_DP + threadIdx.x];
     stats[(size_t)blockIdx.x * 2 * NL_DP + threadIdx.x] = a;
 }
@@ -188,12 +188,14 @@ anchor_gather_kernel(int64_t V, const int64_t* __restrict__ idx, const float* __
             *(float4*)&red[(1 * SRG + srg) * AG_LD + 4 * sq] = make_float4(ssq[0], ssq[1], ssq[2], ssq[3]);
         }
         __syncthreads();
-        if (threadIdx.x < 2 * AG_LD) {
-            const int which = threadIdx.x / AG_LD, c = threadIdx.x % AG_LD;
+        if (threadIdx.x < 2 * NL_DP) {      // the whole row [2][NL_DP]: columns 71.. are written as 0, not left as they were
+            const int which = threadIdx.x / NL_DP, c = threadIdx.x % NL_DP;
             float a = 0.0f;
+            if (c < AG_COLS) {
 #pragma unroll
-            for (int g = 0; g < SRG; ++g) a += red[(which * SRG + g) * AG_LD + c];      // fixed order
-            stats[((size_t)blockIdx.x * 2 + which) * NL_DP + c] = c < AG_COLS ? a : 0.0f;
+                for (int g = 0; g < SRG; ++g) a += red[(which * SRG + g) * AG_LD + c];      // fixed order
+            }
+            stats[((size_t)blockIdx.x * 2 + which) * NL_DP + c] = a;
         }
     }
 }
@@ -328,8 +330,9 @@ anchor_gather_backward_kernel(int64_t N, int64_t V, const int64_t* __restrict__ 
         auto issue_upstream = [&]() {
             if (fv + nv + 1 < V) ag_issue_all<false>(u, fv, nv, V, ldg, gf_now, d_feat, d_anchor, d_offsets, d_grid_scaling);
             else ag_issue_all<true>(u, fv, nv, V, ldg, gf_now, d_feat, d_anchor, d_offsets, d_grid_scaling);
-            gsc = (int)threadIdx.x < nv * 6 ? grid_scaling[fv * 6 + threadIdx.x] : 0.0f;      // exp(s) of the rows, for d exp
-            gsc2 = (int)threadIdx.x + AG_THREADS < nv * 6 ? grid_scaling[fv * 6 + threadIdx.x + AG_THREADS] : 0.0f;
+            // exp(s) of the rows, for d exp (NULL -- allowed when nothing reaches the scaling columns: they hold zeros then)
+            gsc = grid_scaling && (int)threadIdx.x < nv * 6 ? grid_scaling[fv * 6 + threadIdx.x] : 0.0f;
+            gsc2 = grid_scaling && (int)threadIdx.x + AG_THREADS < nv * 6 ? grid_scaling[fv * 6 + threadIdx.x + AG_THREADS] : 0.0f;
         };
         // DX: the upstream pieces are issued BEHIND the dx phase.  Issued in front of it (one memory round trip for both) the
         // two register sets need 158 registers, i.e. three workgroups per CU: 1.22 ms at configs[2] against 1.04 ms this way
@@ -343,6 +346,8 @@ anchor_gather_backward_kernel(int64_t N, int64_t V, const int64_t* __restrict__ 
                 const int64_t row = fv + (ok ? tr : 0);
                 const float* dr = nl.dy + (size_t)row * nl.lddy;
                 const float* xr = nl.x + (size_t)row * nl.ldx;
+                // x: any row stride >= 71 at any 4-byte alignment (the header); 16-byte loads where THIS row allows them
+                const bool xr16 = ((uintptr_t)xr & 15u) == 0;
                 agf4 dq[2], xv[5];
 #pragma unroll
                 for (int q = 0; q < 2; ++q) dq[q] = ok ? *(const agf4*)(dr + 16 * q + 4 * g4) : agf4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -351,11 +356,12 @@ anchor_gather_backward_kernel(int64_t N, int64_t V, const int64_t* __restrict__ 
                     const int k = 16 * nt + 4 * g4;
                     agf4 v = {0.0f, 0.0f, 0.0f, 0.0f};
                     if (ok) {
-                        if (k + 3 < AG_COLS && (nl.ldx & 3) == 0) v = *(const agf4*)(xr + k);
+                        if (k + 3 < AG_COLS && xr16) v = *(const agf4*)(xr + k);
                         else {
                             if (k < AG_COLS) v.x = xr[k];
                             if (k + 1 < AG_COLS) v.y = xr[k + 1];
                             if (k + 2 < AG_COLS) v.z = xr[k + 2];
+                            if (k + 3 < AG_COLS) v.w = xr[k + 3];
                         }
                     }
                     xv[nt] = v;

@@ -5,6 +5,7 @@ behind it, and the inputs the parity tests feed them.  TEST INFRASTRUCTURE ONLY;
   attention_f64   TriPlaneAttention + chunk + cat(plane, attended plane)                     -> checker of csrc/attention.hip
   expand_f64      torch_restatements.expand_torch_chain on double inputs                     -> checker of csrc/expand.hip
   ssim_f64        losses.l1_loss + losses.ssim in float64 (and the inputs of pair_l1 / scaling_reg) -> checker of csrc/ssim.hip
+  gather_f64      the four visible-anchor gathers, exp and cat; gather_dx_f64 the fused dx         -> checker of csrc/anchor_gather.hip
 
 The references are plain torch op chains, written from scene_model.py / torch_restatements.py, dtype- and device-agnostic:
 on float64 CPU tensors they are the reference, on float32 device tensors the "framework chain" whose own error against
@@ -636,3 +637,258 @@ def pair_inputs(n):
     z = slice(0, None, PAIR_ZERO_STRIDE)
     b0[z] = a0[z] - (r1[z] - r2[z])
     return a0, b0, r1, r2
+
+
+# ---------------------------------------------------------------------------------------------------------- anchor gather
+# csrc/anchor_gather.hip: the forward owns 64 rows of the OUTPUT per tile, 8 tiles and one statistics row per workgroup; the
+# backward owns 64 consecutive ANCHORS per block, whose visible ones own consecutive upstream rows fv .. fv + nv - 1.  Every
+# upstream chunk is loaded as 16-byte pieces from the aligned address below it (h = fv * width mod 4 floats in front), without
+# a guard while fv + nv + 1 < V and element by element otherwise.
+AG_ROWS, AG_TPW, AG_COLS, AG_LD, AG_DP = 64, 8, 71, 72, 80
+AG_PARTS = (("feat", 0, 32), ("anchor", 32, 3), ("offsets", 35, 30), ("scaling", 65, 6))       # name, first column, width
+AG_U = 2.0 ** -24
+GATHER_BWD_TOL, GATHER_DX_TOL = 4 * AG_U, 40 * AG_U
+GATHER_STAT_TOL = AG_ROWS * AG_TPW * AG_U                            # an fp32 sum of at most 512 terms per partial, any order
+GATHER_EXP_FLOOR = 2.0 ** -23
+GATHER_FWD_V = {"fwd511": 511, "fwd512": 512, "fwd513": 513, "fwd1025": 1025}
+GATHER_STAT_ROWS = {"fwd511": 1, "fwd512": 1, "fwd513": 2, "fwd1025": 3}
+GATHER_TAIL_FRONT = 3                                                # blocks in front of tail_edge's last 3 * 64 + 1 anchors
+GATHER_MIXED_SEED = 2                # the lowest for which the blocks' h takes every value (test_f64_refs_host.py asserts it)
+GATHER_CASES = ("one", "one_hidden", "b63", "b64", "b65", "b129", "only_last", "only_first", "hole", "tail_edge", "mixed",
+                *GATHER_FWD_V)
+GATHER_BWD_CASES = tuple(c for c in GATHER_CASES if c not in GATHER_FWD_V)
+GATHER_DX_CASES = ("b65", "hole", "tail_edge", "mixed")
+GATHER_SUB_CASES = ("mixed", "tail_edge")
+GATHER_UP = ("feat", "anchor", "offsets", "scaling", "g_fea")        # the five upstream gradients
+GATHER_FAULTS = ("no_xk1_col3", "first_v_plus_1", "no_exp")
+
+
+def gather_mask(case):
+    """bool [N]: the visible anchors of a case."""
+    full = {"one": 1, "b63": 63, "b64": 64, "b65": 65, "b129": 129}
+    if case in full:
+        return torch.ones(full[case], dtype=torch.bool)
+    if case == "one_hidden":
+        return torch.zeros(1, dtype=torch.bool)
+    g = torch.Generator().manual_seed(GATHER_CASES.index(case) + 7 + (GATHER_MIXED_SEED if case == "mixed" else 0))
+    if case in ("only_last", "only_first"):
+        m = torch.zeros(200, dtype=torch.bool)
+        m[199 if case == "only_last" else 0] = True
+        return m
+    if case == "hole":
+        m = torch.rand(256, generator=g) < 0.7
+        m[64:128] = False
+        return m
+    if case == "tail_edge":
+        f = GATHER_TAIL_FRONT * AG_ROWS
+        m = torch.zeros(f + 3 * AG_ROWS + 1, dtype=torch.bool)
+        m[:f] = torch.rand(f, generator=g) < 0.7
+        m[f + 17] = m[f + AG_ROWS + 63] = m[f + 3 * AG_ROWS] = True      # alone in their blocks; the third block is empty
+        return m
+    if case == "mixed":
+        return torch.rand(AG_ROWS * 9 + 7, generator=g) < 0.5
+    V = GATHER_FWD_V[case]
+    m = torch.zeros(V + V // 3, dtype=torch.bool)
+    m[torch.randperm(m.numel(), generator=g)[:V]] = True
+    return m
+
+
+def gather_blocks(inv, V, n0=0, n1=None):
+    """What the backward kernel derives per block of 64 anchors, from `inv` alone: dict(fv, nv, h {width: floats between
+    the 16-byte boundary below the chunk and the chunk}, path: "none" (nv = 0), "vector" (unguarded 16-byte loads) or
+    "tail" (element-wise, guarded))."""
+    n1 = inv.numel() if n1 is None else n1
+    out = []
+    for b0 in range(n0, n1, AG_ROWS):
+        rows = inv[b0:min(b0 + AG_ROWS, n1)]
+        vis = rows[rows >= 0]
+        nv = int(vis.numel())
+        fv = int(vis[0]) if nv else -1
+        assert not nv or torch.equal(vis, torch.arange(fv, fv + nv)), "the index list is not ascending"
+        out.append(dict(fv=fv, nv=nv, h={w: (fv * w) % 4 if nv else None for w in (3, 6, 30, 32, 71, 72)},
+                        path="none" if not nv else "vector" if fv + nv + 1 < V else "tail"))
+    return out
+
+
+def gather_stat_rows(V):
+    return max(1, -(-V // (AG_ROWS * AG_TPW)))
+
+
+def gather_inputs(case):
+    """fp32 CPU inputs of one gather case: dict(N, V, mask, idx [V], inv [N] (row of every anchor, -1 = invisible), params
+    (anchor_feat [N,32], anchor [N,3], offset [N,10,3], scaling [N,6]), up {name: upstream gradient; g_fea as [V,72] with
+    a pad column the kernel must ignore}, coef [34,80] = Gi [32] | k0 | k1 with columns 71.. zero, dy [V,32], old (four
+    buffers to accumulate into), blocks (gather_blocks)).  Scalings randn 0.3 - 3 and features randn 3 + 0.5 as in
+    test_fused_anchor_gather_matches_the_torch_ops; upstreams and coefficients O(1)."""
+    mask = gather_mask(case)
+    N, idx = mask.numel(), mask.nonzero().view(-1)
+    V = idx.numel()
+    inv = torch.full((N,), -1, dtype=torch.long)
+    inv[idx] = torch.arange(V)
+    g = torch.Generator().manual_seed(1000 + GATHER_CASES.index(case))
+    r = lambda *s: torch.randn(*s, generator=g)
+    params = (r(N, 32) * 3 + 0.5, r(N, 3) * 2, r(N, 10, 3), r(N, 6) * 0.3 - 3)
+    up = {"feat": r(V, 32), "anchor": r(V, 3), "offsets": r(V, 30), "scaling": r(V, 6), "g_fea": r(V, AG_LD)}
+    coef = torch.zeros(34, AG_DP)
+    coef[:, :AG_COLS] = r(34, AG_COLS)
+    coef[:32] *= 0.3
+    old = tuple(r(N, w) for _, _, w in AG_PARTS)
+    return dict(case=case, N=N, V=V, mask=mask, idx=idx, inv=inv, params=params, up=up, coef=coef, dy=r(V, 32), old=old,
+                blocks=gather_blocks(inv, V))
+
+
+def gather_f64(idx, anchor_feat, anchor, offset, scaling):
+    """The head of generate_neural_gaussians as the reference writes it: (feat [V,32], anchor [V,3], grid_offsets
+    [V,10,3], grid_scaling [V,6] = exp(scaling)[idx], g_fea [V,71])."""
+    feat, anc = anchor_feat.index_select(0, idx), anchor.index_select(0, idx)
+    off, gs = offset.index_select(0, idx), torch.exp(scaling).index_select(0, idx)
+    return feat, anc, off, gs, torch.cat((feat, anc, off.flatten(1), gs), dim=1)
+
+
+def gather_stats_f64(g_fea):
+    """Per column of the fp32 matrix g_fea [V, >= 71], in float64: (sum (x - x[0]), sum (x - x[0])^2, sum |x - x[0]|)."""
+    x = _f64(g_fea)[:, :AG_COLS]
+    t = x - x[0]
+    return t.sum(dim=0), (t * t).sum(dim=0), t.abs().sum(dim=0)
+
+
+def gather_stats_excess(stats, g_fea):
+    """stats [rows, 2, 80]: the partial sums of disjoint row sets.  -> (excess of the two sums over GATHER_STAT_TOL times
+    sum |x - x[0]| / sum (x - x[0])^2, 0 / 0 = 0; whether columns 71.. are exactly 0)."""
+    s = _f64(stats).sum(dim=0)
+    s1, s2, sa = gather_stats_f64(g_fea)
+    worst = 0.0
+    for got, ref, scale in ((s[0, :AG_COLS], s1, sa), (s[1, :AG_COLS], s2, s2)):
+        dlt = (got - ref).abs()
+        dlt = torch.where(torch.isnan(dlt), torch.full_like(dlt, float("inf")), dlt)
+        worst = max(worst, float(torch.where(dlt == 0, torch.zeros_like(dlt), dlt / (GATHER_STAT_TOL * scale)).max()))
+    return worst, bool((_f64(stats)[:, :, AG_COLS:] == 0).all())
+
+
+def gather_dx_f64(coef, dy, x):
+    """d g_fea [V,71] as the BatchNorm-Linear's backward ends: k0 + x k1 + dy Gi, coef = Gi [32][80] | k0 | k1."""
+    c = coef[:, :AG_COLS]
+    return c[32] + x[:, :AG_COLS] * c[33] + dy @ c[:32]
+
+
+def gather_run(idx, params, up, dx=None):
+    """Forward + backward of gather_f64 in the dtype / on the device of its arguments.  up: {name: gradient or None} of the
+    five outputs (offsets as [V,30], g_fea with 71 or 72 columns: the pad is dropped); dx: a further gradient of g_fea
+    [V,71].  -> (the five outputs, the gradients of the four parameters [N,32] / [N,3] / [N,10,3] / [N,6])."""
+    ps = [p.detach().clone().requires_grad_(True) for p in params]
+    outs = gather_f64(idx, *ps)
+    loss = outs[4].sum() * 0
+    for name, o, w in zip(GATHER_UP, outs, (32, 3, 30, 6, AG_COLS)):
+        u = up.get(name)
+        if u is not None:
+            loss = loss + (o.reshape(o.shape[0], w) * u[:, :w]).sum()
+    if dx is not None:
+        loss = loss + (outs[4] * dx).sum()
+    loss.backward()
+    return [o.detach() for o in outs], [p.grad for p in ps]
+
+
+def gather_terms(d, up, dx=None, old=None, n0=0, n1=None):
+    """Sum of the absolute values of every term that enters an element of the four gradients, d exp applied to the new
+    ones: ((|d part| + |d g_fea| + dx's terms) exp(s), + |old| where the call accumulates).  float64, [n1 - n0, width]
+    each; the bounds of the parity tests are multiples of 2^-24 of it.  dx: (coef, dy, x) -- 32 products, x k1 and k0."""
+    f = lambda t: t.detach().to("cpu", torch.float64)
+    V, N = d["V"], d["N"]
+    n1 = N if n1 is None else n1
+    A = torch.zeros(V, AG_COLS, dtype=torch.float64)
+    if up.get("g_fea") is not None:
+        A += f(up["g_fea"])[:, :AG_COLS].abs()
+    for name, c0, w in AG_PARTS:
+        if up.get(name) is not None:
+            A[:, c0:c0 + w] += f(up[name]).abs()
+    if dx is not None:
+        coef, dy, x = (f(t) for t in dx)
+        c = coef[:, :AG_COLS].abs()
+        A += c[32] + x[:, :AG_COLS].abs() * c[33] + dy.abs() @ c[:32]
+    A[:, 65:] *= torch.exp(f(d["params"][3]))[d["idx"]]
+    full = torch.zeros(N, AG_COLS, dtype=torch.float64)
+    full[d["idx"]] = A
+    outs = [full[n0:n1, c0:c0 + w].clone() for _, c0, w in AG_PARTS]
+    if old is not None:
+        outs = [o + f(b).reshape(N, -1)[n0:n1].abs() for o, b in zip(outs, old)]
+    return outs
+
+
+def gather_restated_f32(d, up, dx=None, old=None, fault=None):
+    """csrc/anchor_gather.hip's backward in plain fp32 torch on the CPU, in the kernel's order: the rows of dx (k0 + x k1,
+    then the 32 products) or of d g_fea, the four parts added, (with dx: d g_fea added last,) times exp(s) as the forward
+    left it, rows scattered to their anchors (zeros elsewhere), added to `old`.  -> the four gradients [N, width].
+    fault: one of GATHER_FAULTS, a deliberate error --
+      no_xk1_col3     the x k1 term is missing in columns 3, 7, .., 67 of dx
+      first_v_plus_1  every block takes its upstream rows from first_v + 1 (the last row from itself)
+      no_exp          d scaling without the factor exp(s)"""
+    assert fault is None or fault in GATHER_FAULTS, fault
+    V, N, idx = d["V"], d["N"], d["idx"]
+    rows = torch.arange(V)
+    if fault == "first_v_plus_1":
+        rows = (rows + 1).clamp(max=max(V - 1, 0))
+    g = lambda t: None if t is None else t.detach().float().cpu()[rows]
+    T = torch.zeros(V, AG_COLS)
+    gf = g(up.get("g_fea"))
+    if dx is not None:
+        coef, dy, x = dx[0].float()[:, :AG_COLS], g(dx[1]), g(dx[2])[:, :AG_COLS]
+        k1 = coef[33].clone()
+        xk1 = x * k1
+        if fault == "no_xk1_col3":
+            xk1[:, 3:68:4] = 0
+        T = (coef[32] + xk1) + dy @ coef[:32]
+    elif gf is not None:
+        T = T + gf[:, :AG_COLS]
+    for name, c0, w in AG_PARTS:
+        if up.get(name) is not None:
+            T[:, c0:c0 + w] += g(up[name])
+    if dx is not None and gf is not None:
+        T = T + gf[:, :AG_COLS]
+    if fault != "no_exp":
+        T[:, 65:] *= torch.exp(d["params"][3].float())[idx]
+    full = torch.zeros(N, AG_COLS)
+    full[idx] = T
+    outs = [full[:, c0:c0 + w].clone() for _, c0, w in AG_PARTS]
+    if old is not None:
+        outs = [b.float().reshape(N, -1) + o for o, b in zip(outs, old)]
+    return outs
+
+
+def gather_excess(got, ref, terms, tol):
+    """max over the four gradients of |got - ref| / (tol * terms), 0 / 0 = 0: at most 1 when every element is inside its
+    bound.  An element whose terms are all zero (an invisible anchor, an absent upstream) must be exact."""
+    worst = 0.0
+    for a, b, s in zip(got, ref, terms):
+        a, b = a.detach().to("cpu", torch.float64).reshape(s.shape), b.detach().to("cpu", torch.float64).reshape(s.shape)
+        dlt = (a - b).abs()
+        dlt = torch.where(torch.isnan(dlt), torch.full_like(dlt, float("inf")), dlt)
+        ratio = torch.where(dlt == 0, torch.zeros_like(dlt), dlt / (tol * s))
+        if ratio.numel():
+            worst = max(worst, float(ratio.max()))
+    return worst
+
+
+GATHER_WRAPPER_N = (130, 2051)
+
+
+def gather_wrapper_inputs(N):
+    """fp32 CPU inputs of the wrapper check: dict(idx (80 % of N anchors), params, G [32,71], c [32], w (weights of the
+    sum over y, feat, anchor, offsets, scaling))."""
+    g = torch.Generator().manual_seed(N + 17)
+    r = lambda *s: torch.randn(*s, generator=g)
+    params = (r(N, 32) * 3 + 0.5, r(N, 3) * 2, r(N, 10, 3), r(N, 6) * 0.3 - 3)
+    idx = (torch.rand(N, generator=g) < 0.8).nonzero().view(-1)
+    V = idx.numel()
+    return dict(idx=idx, params=params, G=r(32, 71) * 0.2, c=r(32), w=(r(V, 32), r(V, 32), r(V, 3), r(V, 10, 3), r(V, 6)))
+
+
+def gather_norm_linear_run(idx, params, G, c, w, eps=1e-5):
+    """gather_f64 -> BatchNorm1d in training mode (no affine part) folded into a Linear, y = xhat G^T + c -> the sum of
+    y, feat, anchor, offsets and scaling weighted by w, in the dtype / on the device of its arguments.
+    -> gradients of the four parameters, of G and of c."""
+    ps = [p.detach().clone().requires_grad_(True) for p in params]
+    G, c = G.detach().clone().requires_grad_(True), c.detach().clone().requires_grad_(True)
+    feat, anc, off, gs, x = gather_f64(idx, *ps)
+    y = ((x - x.mean(dim=0)) / torch.sqrt(x.var(dim=0, unbiased=False) + eps)) @ G.T + c
+    sum((o * u).sum() for o, u in zip((y, feat, anc, off, gs), w)).backward()
+    return [p.grad for p in ps] + [G.grad, c.grad]

@@ -375,3 +375,162 @@ def test_the_l1_order_emulator_is_a_mean_and_its_seeds_tell_the_orders_apart(sha
         assert shape[1] * shape[2] == 1 and all(o.view(np.uint32) == got.view(np.uint32) for o in others)
     else:
         assert all(o.view(np.uint32) != got.view(np.uint32) for o in others), [float(o) for o in others]
+
+
+# ---------------------------------------------------------------------------------------------------------- anchor gather
+def test_gather_reference_is_the_literal_chain_and_passes_gradcheck():
+    """gather_f64 / gather_run on float64 give what autograd gives of the reference's own lines (boolean-mask gathers,
+    get_scaling = exp(_scaling), the concatenation), and gather_f64 with gather_dx_f64 behind it passes gradcheck."""
+    d = R.gather_inputs("b65")
+    mask = torch.rand(65, generator=torch.Generator().manual_seed(3)) < 0.6
+    idx = mask.nonzero().view(-1)
+    V = idx.numel()
+    ps = [p.double().requires_grad_(True) for p in d["params"]]
+    up = {n: t[:V].double() for n, t in d["up"].items()}
+    feat, anchor, offs, gs = ps[0][mask], ps[1][mask], ps[2][mask], torch.exp(ps[3])[mask]
+    g_fea = torch.cat([feat, anchor, offs.view(V, -1), gs], dim=1)
+    outs = (feat, anchor, offs.view(V, -1), gs, g_fea)
+    sum((o * up[n][:, :o.shape[1]]).sum() for n, o in zip(R.GATHER_UP, outs)).backward()
+    got_o, got_g = R.gather_run(idx, [p.detach() for p in ps], up)
+    assert got_o[4].shape == (V, 71) and got_o[2].shape == (V, 10, 3)
+    for a, b in zip(got_o, (feat, anchor, offs, gs, g_fea)):
+        assert torch.equal(a, b.detach())
+    for a, p in zip(got_g, ps):
+        assert a.shape == p.shape and torch.allclose(a, p.grad, rtol=1e-14, atol=1e-14)
+    assert float(got_g[0][~mask].abs().max()) == 0 and float(got_g[3][mask].abs().min()) > 0
+    g = torch.Generator().manual_seed(4)
+    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)
+    idx = torch.tensor([0, 2, 3])
+    ps = [r(5, 32).requires_grad_(), r(5, 3).requires_grad_(), r(5, 10, 3).requires_grad_(), (r(5, 6) * 0.3 - 3).requires_grad_()]
+    coef, dy = r(34, 80), r(3, 32)
+
+    def fn(*p):
+        outs = R.gather_f64(idx, *p)
+        return (*outs, R.gather_dx_f64(coef, dy, outs[4]))
+    assert torch.autograd.gradcheck(fn, ps, eps=1e-6, atol=1e-6, rtol=1e-5)
+
+
+def test_gather_inputs_hold_what_the_case_is_about():
+    """From `inv` alone: what each block of 64 anchors of every case makes the backward kernel do."""
+    ds = {c: R.gather_inputs(c) for c in R.GATHER_CASES}
+    for c, d in ds.items():
+        assert d["inv"].shape == (d["N"],) and int((d["inv"] >= 0).sum()) == d["V"] and d["N"] <= 2100
+        assert torch.equal(d["inv"][d["idx"]], torch.arange(d["V"])) and float(d["coef"][:, 71:].abs().max()) == 0
+        assert d["blocks"] == R.gather_blocks(d["inv"], d["V"]) and len(d["blocks"]) == -(-d["N"] // 64)
+    facts = lambda c: [(b["fv"], b["nv"], b["path"]) for b in ds[c]["blocks"]]
+    assert facts("one") == [(0, 1, "tail")] and facts("one_hidden") == [(-1, 0, "none")] and ds["one_hidden"]["V"] == 0
+    assert facts("b63") == [(0, 63, "tail")] and facts("b64") == [(0, 64, "tail")]
+    assert facts("b65") == [(0, 64, "tail"), (64, 1, "tail")]
+    assert facts("b129") == [(0, 64, "vector"), (64, 64, "tail"), (128, 1, "tail")]
+    assert facts("only_last") == [(-1, 0, "none")] * 3 + [(0, 1, "tail")] and ds["only_last"]["idx"].tolist() == [199]
+    assert facts("only_first") == [(0, 1, "tail")] + [(-1, 0, "none")] * 3
+    hole = facts("hole")
+    assert hole[1] == (-1, 0, "none") and all(f[1] > 0 for f in hole[:1] + hole[2:]) and not ds["hole"]["mask"][64:128].any()
+    te, V = facts("tail_edge"), ds["tail_edge"]["V"]
+    assert ds["tail_edge"]["N"] == (R.GATHER_TAIL_FRONT + 3) * 64 + 1 and len(te) == R.GATHER_TAIL_FRONT + 4
+    assert all(f[2] == "vector" and f[0] + f[1] <= V - 3 for f in te[:R.GATHER_TAIL_FRONT])
+    assert te[-4:] == [(V - 3, 1, "vector"), (V - 2, 1, "tail"), (-1, 0, "none"), (V - 1, 1, "tail")]
+    assert [f[0] + f[1] for f in te if f[1]][-3:] == [V - 2, V - 1, V]
+    mixed = ds["mixed"]
+    assert mixed["N"] == 64 * 9 + 7 and 0.4 < mixed["V"] / mixed["N"] < 0.6
+    hs = lambda w: {b["h"][w] for b in mixed["blocks"] if b["nv"]}
+    assert hs(3) == hs(71) == {0, 1, 2, 3} and hs(6) == hs(30) == {0, 2} and hs(32) == hs(72) == {0}
+    assert {b["path"] for b in mixed["blocks"]} == {"vector", "tail"}
+    for c, V in R.GATHER_FWD_V.items():
+        assert ds[c]["V"] == V and R.gather_stat_rows(V) == R.GATHER_STAT_ROWS[c]
+    assert [R.gather_stat_rows(V) for V in (1, 511, 512, 513, 1025)] == [1, 1, 1, 2, 3]
+
+
+def _gather_variants(d):
+    """(name, upstreams, dx, old) the GPU tests run on a case: everything, without dx; accumulating; with dx, with and
+    without a gradient that did arrive for g_fea."""
+    up = d["up"]
+    x = R.gather_f64(d["idx"], *d["params"])[4]
+    dx = (d["coef"], d["dy"], x)
+    out = [("all", up, None, None), ("accumulate", up, None, d["old"])]
+    if d["case"] in R.GATHER_DX_CASES:
+        out += [("dx", {**up, "g_fea": None}, dx, None), ("dx + d g_fea", up, dx, None)]
+    return out
+
+
+def _gather_ref(d, up, dx, old):
+    f = lambda t: None if t is None else t.double()
+    dx64 = None if dx is None else R.gather_dx_f64(*(f(t) for t in dx))
+    _, ref = R.gather_run(d["idx"], [f(p) for p in d["params"]], {n: f(t) for n, t in up.items()}, dx64)
+    if old is not None:
+        ref = [r.reshape(d["N"], -1) + f(o) for r, o in zip(ref, old)]
+    return ref, R.gather_terms(d, up, dx, old)
+
+
+@pytest.mark.parametrize("case", R.GATHER_BWD_CASES)
+def test_correct_fp32_gather_arithmetic_meets_the_a_priori_bounds(case):
+    """The condition under which the gather tests of test_gpu_f64_parity may ask what they ask: the backward's
+    arithmetic in plain fp32 (f64_refs.gather_restated_f32) is inside 4 x 2^-24 / 40 x 2^-24 of the sum of its terms on
+    every element of every case, fp32 exp inside 2^-23, and fp32 column sums of 512 rows inside 512 x 2^-24."""
+    d = R.gather_inputs(case)
+    for name, up, dx, old in _gather_variants(d):
+        ref, terms = _gather_ref(d, up, dx, old)
+        tol = R.GATHER_DX_TOL if dx is not None else R.GATHER_BWD_TOL
+        e = R.gather_excess(R.gather_restated_f32(d, up, dx, old), ref, terms, tol)
+        print(f"gather {case:10s} {name:14s} worst |got - ref| / bound {e:.3f}")
+        assert e <= 1
+        assert old is not None or all(float(r.reshape(d["N"], -1)[~d["mask"]].abs().sum()) == 0 for r in ref)
+    outs = R.gather_f64(d["idx"], *d["params"])
+    if d["V"]:
+        e64 = torch.exp(d["params"][3].double())[d["idx"]]
+        assert float(((outs[3].double() - e64).abs() / e64).max()) <= R.GATHER_EXP_FLOOR
+        g = outs[4]
+        t = g - g[0]
+        parts = [torch.stack((c.sum(dim=0), (c * c).sum(dim=0))) for c in t.split(512)]
+        stats = torch.zeros(len(parts), 2, 80)
+        stats[:, :, :71] = torch.stack(parts)
+        e, zeros = R.gather_stats_excess(stats, g)
+        print(f"gather {case:10s} statistics     worst |got - ref| / bound {e:.3f}")
+        assert e <= 1 and zeros
+
+
+@pytest.mark.parametrize("case", R.GATHER_SUB_CASES)
+def test_the_old_value_of_an_accumulating_call_stands_outside_exp_s(case):
+    """Why gather_terms adds |old| BEHIND the factor exp(s): the kernel multiplies the new gradient by exp(s) = 0.05 and
+    then adds it to the old value, and that addition alone rounds to 2^-24 |old + new|.  With the bound written as
+    4 x 2^-24 (|d part| + |d g_fea| + |old|) exp(s), plain fp32 arithmetic is several times outside it on d scaling
+    (5.7 x on `mixed`, 6.8 x on `tail_edge`); the other three gradients have exp(s) = 1 and are the same either way."""
+    d = R.gather_inputs(case)
+    ref, terms = _gather_ref(d, d["up"], None, d["old"])
+    got = R.gather_restated_f32(d, d["up"], None, d["old"])
+    e_s = torch.zeros(d["N"], 6, dtype=torch.float64)
+    e_s[d["idx"]] = torch.exp(d["params"][3].double())[d["idx"]]
+    new = R.gather_terms(d, d["up"])[3]
+    inside = new + d["old"][3].double().abs() * e_s
+    vis = d["mask"]
+    e_in = R.gather_excess([got[3][vis]], [ref[3][vis]], [inside[vis]], R.GATHER_BWD_TOL)
+    e_out = R.gather_excess([got[3]], [ref[3]], [terms[3]], R.GATHER_BWD_TOL)
+    print(f"gather {case}: d scaling, accumulate: {e_in:.2f} x the bound with |old| exp(s), {e_out:.2f} x with |old|")
+    assert e_in > 3 and e_out <= 1
+
+
+# `one` and the two `only_` cases have one upstream row: a block that starts a row late reads that row again
+_GATHER_V2 = {c for c in R.GATHER_BWD_CASES if R.gather_mask(c).sum() >= 2}
+GATHER_FAULT_SEEN_BY = {
+    "no_xk1_col3": set(R.GATHER_DX_CASES),                               # the cases that run with dx
+    "first_v_plus_1": _GATHER_V2,
+    "no_exp": set(R.GATHER_BWD_CASES) - {"one_hidden"},                  # V = 0: nothing to scale
+}
+
+
+@pytest.mark.parametrize("fault", R.GATHER_FAULTS)
+def test_a_wrong_gather_restatement_misses_the_bounds_on_the_cases_chosen_for_it(fault):
+    """Each deliberate error of f64_refs.gather_restated_f32 leaves the a-priori bounds on exactly the cases named in
+    GATHER_FAULT_SEEN_BY."""
+    missed = set()
+    for case in R.GATHER_BWD_CASES:
+        d = R.gather_inputs(case)
+        for name, up, dx, old in _gather_variants(d):
+            ref, terms = _gather_ref(d, up, dx, old)
+            tol = R.GATHER_DX_TOL if dx is not None else R.GATHER_BWD_TOL
+            e = R.gather_excess(R.gather_restated_f32(d, up, dx, old, fault=fault), ref, terms, tol)
+            if e > 1:
+                missed.add(case)
+                print(f"{fault:15s} {case:10s} {name:14s} {e:.3g} x bound")
+    assert missed == GATHER_FAULT_SEEN_BY[fault], (sorted(missed - GATHER_FAULT_SEEN_BY[fault]),
+                                                   sorted(GATHER_FAULT_SEEN_BY[fault] - missed))

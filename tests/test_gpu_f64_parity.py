@@ -11,9 +11,12 @@ row with the row's scale floored at 1e-3 of the tensor's (f64_refs.err).  The ba
 being the same figure of the fp32 chain against the same float64 result in the same process: floor 2e-5, c = 1.5 (the
 constants of test_fused_norm_linear_matches_batchnorm_linear_chain).  Every figure is printed before anything is
 asserted (and appended to the file $SPLATCO_F64_PARITY_LOG names, if set); profiles/r08_f64_parity.txt is one such run,
-profiles/r13_loss_f64_parity.txt one of the image losses (l1_ssim, scaling_reg, pair_l1: the end of this file).
+profiles/r13_loss_f64_parity.txt one of the image losses (l1_ssim, scaling_reg, pair_l1), profiles/r22_gather_f64_parity.txt
+one of csrc/anchor_gather.hip at its C ABI (the end of this file) and of the heads and the expansion reading feat /
+offsets in place from the gather's [V,72] matrix (layout `gather` of their tests).
 """
 import copy
+import functools
 import os
 
 import pytest
@@ -75,9 +78,32 @@ def _same_bits(a, b):
 HEADS_FLOOR = {"anchor": 6.9e-5}
 
 
-@pytest.mark.parametrize("V", R.HEADS_V)
-def test_mlp_heads_against_float64(V):
-    """16-row tiles, 4 tiles per workgroup, backward grid capped at 256 workgroups, forward at 512: the row counts give
+def _in_gather_layout(t, col0):
+    """t [V, w] as columns col0 .. col0 + w - 1 of a [V,72] leaf whose other columns are NaN: what csrc/anchor_gather.hip
+    hands the readers of feat (col0 = 0) and offsets (col0 = 35, rows 140 bytes into 288: 4-byte aligned only).
+    -> (the leaf, the view)"""
+    g72 = torch.full((t.shape[0], 72), float("nan"), device=t.device)
+    g72[:, col0:col0 + t.shape[1]] = t
+    g72.requires_grad_()
+    return g72, g72[:, col0:col0 + t.shape[1]]
+
+
+def _gather_layout_grad(g72, col0, w):
+    """(the gradient of the view, whether every other column of the leaf's gradient is exactly 0)"""
+    rest = g72.grad.clone()
+    rest[:, col0:col0 + w] = 0
+    return g72.grad[:, col0:col0 + w], float(rest.abs().max()) == 0
+
+
+HEADS_GATHER_V = [1, 17, 65, 1025, 16385]                    # V = 1: the wrapper copies (a row stride means nothing there)
+
+
+@pytest.mark.parametrize("V,layout", [pytest.param(V, "packed", id=str(V)) for V in R.HEADS_V]
+                         + [pytest.param(V, "gather", id=f"gather-{V}") for V in HEADS_GATHER_V])
+def test_mlp_heads_against_float64(V, layout):
+    """layout `gather`: feat is columns 0..31 of a [V,72] matrix (row stride 72, as the anchor gather leaves it), every
+    other column NaN -- an over-read shows in the values; same references and bars.
+    16-row tiles, 4 tiles per workgroup, backward grid capped at 256 workgroups, forward at 512: the row counts give
     4, 60, 64, 68, 128 and 1024 weight-gradient partials (the unrolled loop of mlp_heads_reduce_kernel alone, its tail
     alone, both), a last tile of 1, 15 and 16 rows alone and behind full workgroups, the first backward grid-stride
     (16385) and the first forward one (32769).  geo_fea arrives as one [V,64] matrix or as its two halves, alternating.
@@ -85,7 +111,7 @@ def test_mlp_heads_against_float64(V):
     pre-activations of +-40, +-100 (saturated tanh / sigmoid) and +-1e-4 (where 1 - 2 / (1 + e^2z) cancels)."""
     from splatco_amd.mlp_heads import mlp_heads, supported
     d = R.heads_inputs(V)
-    rep = Report("heads", f"V={V}")
+    rep = Report("heads", f"V={V}" + (" gather" if layout == "gather" else ""))
     two_parts = R.HEADS_V.index(V) % 2 == 1
     f64 = lambda t: t.double()
     ref_o, ref_g = R.heads_run(f64(d["feat"]), f64(d["anchor"]), f64(d["campos"]), f64(d["geo"]), [f64(u) for u in d["up"]],
@@ -97,6 +123,9 @@ def test_mlp_heads_against_float64(V):
     runs = []
     for _ in range(2):
         f, a, ge = (t.clone().requires_grad_() for t in (feat, anchor, geo))
+        if layout == "gather":
+            g72, f = _in_gather_layout(feat, 0)
+            assert f.stride() == (72, 1) and f.shape == feat.shape
         for p in pc.parameters():
             p.grad = None
         assert supported(pc, f, ge)
@@ -106,6 +135,9 @@ def test_mlp_heads_against_float64(V):
             outs = mlp_heads(pc, f, a, campos, ge)
         sum((o * u).sum() for o, u in zip(outs, up)).backward()
         grads = {"feat": f.grad, "anchor": a.grad, "geo": ge.grad}
+        if layout == "gather":
+            grads["feat"], clean = _gather_layout_grad(g72, 0, 32)
+            rep.require(clean, "d g72: 0 elsewhere")
         grads.update({n: p.grad.clone() for n, p in pc.named_parameters() if n.startswith("mlp_")})
         runs.append(([o.detach() for o in outs], grads))
     (k_o, k_g), (k_o2, k_g2) = runs
@@ -204,9 +236,12 @@ EXPAND_GRADS = ("d neural_opacity", "d color", "d scale_rot", "d offsets", "d gr
 EXPAND_OUTS = ("xyz", "color", "opacity", "scaling", "rot")
 
 
-@pytest.mark.parametrize("name,V,k,select,edges", R.EXPAND_CASES, ids=[c[0] for c in R.EXPAND_CASES])
-def test_expand_compact_against_float64(name, V, k, select, edges):
-    """k = 1, 5, 10, 33 offsets per anchor; n = V k candidates on both sides of the first workgroup (1024) and of the
+@pytest.mark.parametrize("name,V,k,select,edges,layout", [pytest.param(*c, "packed", id=c[0]) for c in R.EXPAND_CASES]
+                         + [pytest.param(*c, "gather", id="gather-" + c[0]) for c in R.EXPAND_CASES if c[2] == 10])
+def test_expand_compact_against_float64(name, V, k, select, edges, layout):
+    """layout `gather` (the k = 10 cases): the offsets are columns 35..64 of a [V,72] matrix whose other columns are NaN,
+    rows 288 bytes apart and 140 bytes in; same references and bars.
+    k = 1, 5, 10, 33 offsets per anchor; n = V k candidates on both sides of the first workgroup (1024) and of the
     1024 and 2048 workgroups after which compact_scan_kernel carries its running total into the next chunk; everything
     kept, nothing kept, every other candidate kept.  The k cases carry the edge rows of f64_refs.expand_inputs: zero
     and 1e-20 quaternions (the clamped branch of the normalisation, forward and backward), scale_rot[:, :3] = +-90
@@ -215,7 +250,7 @@ def test_expand_compact_against_float64(name, V, k, select, edges):
     from splatco_amd.expand import expand_compact
     from splatco_amd.losses import scaling_reg
     d = R.expand_inputs(V, k, select, edges)
-    rep = Report("expand", name)
+    rep = Report("expand", name + (" gather" if layout == "gather" else ""))
     n = V * k
     want_mask = (d["args"][0] > 0).view(-1)
     want_idx = want_mask.nonzero().view(-1)
@@ -232,12 +267,21 @@ def test_expand_compact_against_float64(name, V, k, select, edges):
         runs = []
         for _ in range(2):
             ins = [t.clone().requires_grad_(True) for t in args]
+            if layout == "gather":
+                g72, off = _in_gather_layout(args[3].reshape(V, 30), 35)
+                ins[3] = off.unflatten(1, (10, 3))
+                assert (V == 1 or ins[3].stride() == (72, 3, 1)) and ins[3].data_ptr() % 16 == 12      # (one row: no stride)
             *outs, mask = expand_compact(*ins, k)
             loss = sum((o * u).sum() for o, u in zip(outs, upd))
             if reg and P:
                 loss = loss + reg * scaling_reg(outs[3])
             loss.backward()
-            runs.append(([o.detach() for o in outs], mask, mask._scr_out_index, [t.grad for t in ins]))
+            grads = [t.grad for t in ins]
+            if layout == "gather":
+                d_off, clean = _gather_layout_grad(g72, 35, 30)
+                grads[3] = d_off.reshape(V, 10, 3)
+                rep.require(clean, "d g72: 0 elsewhere" + tag)
+            runs.append(([o.detach() for o in outs], mask, mask._scr_out_index, grads))
         (k_o, k_m, k_i, k_g), (k_o2, k_m2, k_i2, k_g2) = runs
         if not reg:
             rep.require(torch.equal(ref_m, want_mask) and torch.equal(ch_m.cpu(), want_mask), "reference masks")
@@ -473,4 +517,223 @@ def test_pair_l1_at_workgroup_edges(n):
                 rep.require(torch.equal(got.sign(), want.sign()) and torch.allclose(got, want, rtol=2.0 ** -22, atol=0),
                             "gradient" + tag + (" (gen1)" if got is af else " (gen2)"))
         rep.require(bool(ok), "bit-reproducible" + tag)
+    rep.finish()
+
+
+# ---------------------------------------------------------------------------------------------------------- anchor gather
+# csrc/anchor_gather.hip at its own C ABI (include/splatco_raster.h: scr_anchor_gather, scr_anchor_gather_backward), on the
+# cases of f64_refs.GATHER_CASES: what each block of every case makes the kernel do is asserted from the index alone in
+# tests/test_f64_refs_host.py, which also shows that plain fp32 arithmetic meets every bound used here and three wrong
+# kernels do not.  profiles/r22_gather_f64_parity.txt is one run of this section.
+AG_WIDTHS = (32, 3, 30, 6)
+AG_ALL = frozenset(R.GATHER_UP)
+
+
+def _nan(*shape):
+    return torch.full(shape, float("nan"), device=DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def _gather_case(case):
+    """(the CPU inputs, their device copies with the fp32 framework chain's grid_scaling `gs` and g_fea `x`, the float64
+    forward): made once per case, shared by the tests below and never modified."""
+    d = R.gather_inputs(case)
+    g = lambda t: t.to(DEV)
+    dev = dict(idx=g(d["idx"]), inv=g(d["inv"]), params=[g(p) for p in d["params"]], up={n: g(t) for n, t in d["up"].items()},
+               coef=g(d["coef"]), dy=g(d["dy"]), old=[g(t) for t in d["old"]])
+    dev["up71"] = dev["up"]["g_fea"][:, :71].contiguous()
+    chain = R.gather_f64(dev["idx"], *dev["params"])
+    dev["gs"], dev["x"] = chain[3].contiguous(), chain[4].contiguous()
+    return d, dev, R.gather_f64(d["idx"], *(p.double() for p in d["params"]))
+
+
+@functools.lru_cache(maxsize=None)
+def _gather_bwd_ref(case, names, dx=False, old=False):
+    """(float64 gradients [N, width] x 4, the sums of |terms| their bounds are multiples of): once per set of operands."""
+    d, dev, _ = _gather_case(case)
+    f = lambda t: None if t is None else t.double()
+    up = {n: (d["up"][n] if n in names else None) for n in R.GATHER_UP}
+    dx3 = (d["coef"], d["dy"], dev["x"].cpu()) if dx else None
+    dx64 = R.gather_dx_f64(*(f(t) for t in dx3)) if dx else None
+    _, ref = R.gather_run(d["idx"], [f(p) for p in d["params"]], {n: f(t) for n, t in up.items()}, dx64)
+    ref = [r.reshape(d["N"], -1) for r in ref]
+    if old:
+        ref = [r + f(o) for r, o in zip(ref, d["old"])]
+    return ref, R.gather_terms(d, up, dx3, d["old"] if old else None)
+
+
+def _gather_backward(case, names, ldg, dxa=None, old=False, ranges=None, gs=True):
+    """scr_anchor_gather_backward into NaN-filled (old: copies of the case's old) buffers, one call per anchor range on
+    offset addresses as anchor_gather._AnchorGather.backward makes them.  names: the upstream gradients that are given."""
+    from splatco_amd import _C
+    d, dev, _ = _gather_case(case)
+    N, V = d["N"], d["V"]
+    outs = [o.clone() for o in dev["old"]] if old else [_nan(N, w) for w in AG_WIDTHS]
+    u = lambda n: _C.ptr(dev["up"][n]) if n in names else None
+    gf = _C.ptr(dev["up"]["g_fea"] if ldg == 72 else dev["up71"]) if "g_fea" in names else None
+    nl = dxa if dxa is not None else (None, None, 0, None, 0)
+    for n0, n1 in ranges or [(0, N)]:
+        _C.call("scr_anchor_gather_backward", n1 - n0, V, dev["inv"].data_ptr() + 8 * n0, _C.ptr(dev["gs"]) if gs else None,
+                u("feat"), u("anchor"), u("offsets"), u("scaling"), gf, ldg,
+                *(o.data_ptr() + 4 * w * n0 for o, w in zip(outs, AG_WIDTHS)), 1 if old else 0, *nl, device=DEV)
+    return outs
+
+
+def _gather_ranges(N):
+    """64-aligned ranges of [0, N): the first block, the full blocks behind it, the last (shorter) block."""
+    cuts = sorted({0, min(64, N), N // 64 * 64, N})
+    return [(a, b) for a, b in zip(cuts, cuts[1:]) if b > a]
+
+
+@pytest.mark.parametrize("ld,split", [(71, True), (72, True), (72, False)], ids=["ld71", "ld72", "ld72-inplace"])
+@pytest.mark.parametrize("case", R.GATHER_CASES)
+def test_anchor_gather_forward_against_float64(case, ld, split):
+    """scr_anchor_gather with packed (71) and padded (72) g_fea rows, with feat / offsets written or left to their readers
+    (NULL, 72 only), into NaN-filled buffers: the copied columns and the split outputs are the inputs' rows bit for bit, the
+    pad column is 0, exp(scaling) is within max(2^-23, 1.5 e_chain) of float64 (relative, per element; e_chain: fp32
+    torch.exp on the device), the per-workgroup column sums of (x - x[0]) and (x - x[0])^2 add up to the float64 sums over
+    the same fp32 matrix within 512 x 2^-24 of sum |x - x[0]| / sum (x - x[0])^2 (an fp32 sum of at most 512 terms per
+    partial, any order), their columns 71.. are 0, and everything the call owns is NaN-free.  V = 511, 512, 513, 1025: one
+    workgroup owns 8 x 64 rows and one statistics row."""
+    from splatco_amd import _C
+    d, dev, ref = _gather_case(case)
+    rep = Report("gather fw", f"{case} ld{ld}" + ("" if split else " in place"))
+    V = d["V"]
+    rows = _C.lib.scr_anchor_gather_stat_rows(V)
+    rep.require(rows == R.gather_stat_rows(V) == R.GATHER_STAT_ROWS.get(case, 1), f"{rows} stat rows")
+    runs = []
+    for _ in range(2):
+        g, anc, gs = _nan(V, ld), _nan(V, 3), _nan(V, 6)
+        feat, off = (_nan(V, 32), _nan(V, 30)) if split else (None, None)
+        st = _nan(_C.lib.scr_anchor_gather_stat_buffer_rows(V), 2, 80)
+        _C.call("scr_anchor_gather", V, _C.ptr(dev["idx"]), *dev["params"], _C.ptr(feat), anc, _C.ptr(off), gs, g, ld, st, device=DEV)
+        runs.append([t.cpu() for t in (g, anc, gs, st[:rows]) + ((feat, off) if split else ())])
+    g, anc, gs, st = runs[0][:4]
+    if V:
+        want = [p[d["idx"]].reshape(V, -1) for p in d["params"][:3]]
+        rep.require(torch.equal(g[:, :32], want[0]) and torch.equal(g[:, 32:35], want[1]) and torch.equal(g[:, 35:65], want[2]),
+                    "g_fea copies exact")
+        rep.require(torch.equal(anc, want[1]) and torch.equal(gs, g[:, 65:71]), "anchor, scaling exact")
+        if split:
+            rep.require(torch.equal(runs[0][4], want[0]) and torch.equal(runs[0][5], want[2]), "feat, offsets exact")
+        if ld == 72:
+            rep.require(bool((g[:, 71] == 0).all()), "pad column == 0")
+        rep.require(all(bool(torch.isfinite(t).all()) for t in runs[0]), "NaN-free")
+        rel = lambda t: float(((t.double() - ref[3]).abs() / ref[3]).max())
+        e, e_chain = rel(gs), rel(dev["gs"].cpu())
+        rep.lines.append(f"gather fw {rep.case:16s} exp: e_chain {e_chain:9.3e}")
+        rep.within("exp(scaling)", e, max(R.GATHER_EXP_FLOOR, 1.5 * e_chain))
+        excess, zeros = R.gather_stats_excess(st, g)
+        rep.within("column sums / bound", excess, 1.0)
+        rep.require(zeros, "stat columns 71.. == 0")
+        if V == 1:
+            rep.require(bool((st == 0).all()), "V = 1: sums exactly 0")
+    rep.require(all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(*runs)), "bit-reproducible")
+    rep.finish()
+
+
+def _gather_check(rep, tag, case, got, names, tol, dx=False, old=False):
+    d = _gather_case(case)[0]
+    ref, terms = _gather_bwd_ref(case, frozenset(names), dx, old)
+    rep.within(tag, R.gather_excess(got, ref, terms, tol), 1.0)
+    hidden = ~d["mask"]
+    want = d["old"] if old else [torch.zeros(d["N"], w) for w in AG_WIDTHS]
+    rep.require(all(torch.equal(a.cpu()[hidden], b[hidden]) for a, b in zip(got, want)),
+                tag + (": hidden == old" if old else ": hidden == 0"))
+
+
+@pytest.mark.parametrize("ldg", [71, 72], ids=["ld71", "ld72"])
+@pytest.mark.parametrize("case", R.GATHER_BWD_CASES)
+def test_anchor_gather_backward_against_float64(case, ldg):
+    """scr_anchor_gather_backward without dx, d g_fea packed (71) and padded (72, the pad column random: ignored).  Per
+    element |got - ref| <= 4 x 2^-24 x ((|d part| + |d g_fea|) exp(s) + |old|) -- at most three additions and one multiply;
+    the factor exp(s) is 1 outside d scaling, and |old| (accumulate only) is added behind the multiplication, so it does
+    not carry that factor (with |old| exp(s) in its place plain fp32 arithmetic itself stands at 5.7 x / 6.8 x the bound on
+    `mixed` / `tail_edge`: exp(s) = 0.05 and the last addition rounds to 2^-24 |old + new|; tests/test_f64_refs_host.py
+    has it at 0.43 of this one) -- against float64 autograd of the torch chain; invisible anchors exactly 0 (accumulate:
+    exactly the old value); a second run gives the same bits.  On `mixed` and `tail_edge` also: each upstream pointer NULL
+    on its own; all five and grid_scaling NULL (all zeros); accumulate = 1 over a random old buffer; the call split into
+    64-aligned ranges with a last range shorter than 64 and V larger than every range (the whole call's bits)."""
+    d = _gather_case(case)[0]
+    rep = Report("gather bw", f"{case} ld{ldg}")
+    got, got2 = _gather_backward(case, AG_ALL, ldg), _gather_backward(case, AG_ALL, ldg)
+    _gather_check(rep, "all upstreams", case, got, AG_ALL, R.GATHER_BWD_TOL)
+    rep.require(_same_bits(got, got2), "bit-reproducible")
+    if d["V"] == 0:                                            # upstream pointers NULL (nothing to point at), no grid_scaling
+        rep.require(all(float(t.abs().max()) == 0 for t in _gather_backward(case, (), ldg, gs=False)), "V = 0: all zeros")
+    if case in R.GATHER_SUB_CASES:
+        for n in R.GATHER_UP:
+            _gather_check(rep, "no d " + n, case, _gather_backward(case, AG_ALL - {n}, ldg), AG_ALL - {n}, R.GATHER_BWD_TOL)
+        rep.require(all(float(t.abs().max()) == 0 for t in _gather_backward(case, (), ldg, gs=False)), "no upstream: zeros")
+        _gather_check(rep, "accumulate", case, _gather_backward(case, AG_ALL, ldg, old=True), AG_ALL, R.GATHER_BWD_TOL, old=True)
+        ranges = _gather_ranges(d["N"])
+        assert len(ranges) == 3 and ranges[-1][1] - ranges[-1][0] < 64 and all(b - a < d["V"] for a, b in ranges[::2])
+        rep.require(_same_bits(_gather_backward(case, AG_ALL, ldg, ranges=ranges), got), "ranges: the call's bits")
+    rep.finish()
+
+
+@pytest.mark.parametrize("off", [0, 1], ids=["x0", "x1"])
+@pytest.mark.parametrize("ldx", [71, 72, 76], ids=["ldx71", "ldx72", "ldx76"])
+@pytest.mark.parametrize("case", R.GATHER_DX_CASES)
+def test_anchor_gather_backward_with_fused_dx_against_float64(case, ldx, off):
+    """scr_anchor_gather_backward forming d g_fea = k0 + x k1 + dy Gi itself (nl_coef given): x with packed rows (71), padded
+    rows (72) and a wider matrix (76), at a 16-byte aligned address and one float behind it (x0 / x1) -- the row pointers are
+    then 16-byte aligned on every row, every fourth row, or never; dy with row strides 32 and 36; d g_fea absent or given
+    (added on top).  The unused floats of x and dy are NaN.  Reference: float64 autograd of the torch chain fed d g_fea +
+    gather_dx_f64.  Per element |got - ref| <= 40 x 2^-24 x S exp(s), S the sum of the absolute values of all terms (32
+    products, x k1, k0, the other upstream parts): HEADS_TOL's rule for an fp32 MFMA dot product.  The call split into
+    64-aligned ranges gives the whole call's bits, a second run too."""
+    d, dev, _ = _gather_case(case)
+    rep = Report("gather dx", f"{case} ldx{ldx}+{off}")
+    V = d["V"]
+    xb = _nan(off + V * ldx + 3)
+    xb[off:off + V * ldx].view(V, ldx)[:, :71] = dev["x"]
+    assert xb.data_ptr() % 16 == 0
+    for with_gf in (False, True):
+        for lddy in (32, 36):
+            dyb = _nan(V, lddy)
+            dyb[:, :32] = dev["dy"]
+            dxa = (dev["coef"], dyb, lddy, xb.data_ptr() + 4 * off, ldx)
+            names, ldg = (AG_ALL if with_gf else AG_ALL - {"g_fea"}), (72 if lddy == 32 else 71)
+            tag = f"{'d g_fea ' if with_gf else ''}lddy {lddy}"
+            got = _gather_backward(case, names, ldg, dxa)
+            _gather_check(rep, tag, case, got, names, R.GATHER_DX_TOL, dx=True)
+            rep.require(_same_bits(_gather_backward(case, names, ldg, dxa), got), tag + ": bit-reproducible")
+            rep.require(_same_bits(_gather_backward(case, names, ldg, dxa, ranges=_gather_ranges(d["N"])), got),
+                        tag + ": ranges: the call's bits")
+    rep.finish()
+
+
+@pytest.mark.parametrize("N", R.GATHER_WRAPPER_N)
+def test_gather_wrappers_against_float64(N, monkeypatch):
+    """The product path: anchor_gather.gather_anchors -> scene_model._NormLinearFn with the deferred-dx box -> a weighted
+    sum of y and the four split outputs.  The gradients of the four parameters, of G and of c against float64 autograd of
+    the torch chain (f64_refs.gather_norm_linear_run), bar max(2e-5, 1.5 e_chain) with e_chain from the same chain in
+    fp32 on the device.  The backward call is watched: dx is formed inside the gather's kernel, no d g_fea arrives."""
+    from splatco_amd import _C
+    from splatco_amd import anchor_gather as ag
+    from splatco_amd import scene_model as sm
+    w = R.gather_wrapper_inputs(N)
+    rep = Report("gather wr", f"N={N}")
+    f, g = (lambda t: t.double()), (lambda t: t.to(DEV))
+    ref = R.gather_norm_linear_run(w["idx"], [f(p) for p in w["params"]], f(w["G"]), f(w["c"]), [f(u) for u in w["w"]])
+    chain = R.gather_norm_linear_run(g(w["idx"]), [g(p) for p in w["params"]], g(w["G"]), g(w["c"]), [g(u) for u in w["w"]])
+    calls, call = [], _C.call
+    monkeypatch.setattr(_C, "call", lambda name, *a, **k: (calls.append((name, a)), call(name, *a, **k))[1])
+    runs = []
+    for _ in range(2):
+        pc = sm.AnchorGaussianModel(plane_size=16, num_channels=15).to(DEV)
+        p_feat, p_anchor, p_offset, p_scaling = (g(p).clone() for p in w["params"])
+        pc.set_anchors(p_anchor, p_offset, p_feat, p_scaling)
+        G, c = g(w["G"]).clone().requires_grad_(), g(w["c"]).clone().requires_grad_()
+        feat, anc, off, gs, g_fea = ag.gather_anchors(pc, g(w["idx"]))
+        assert feat.stride() == (72, 1) and off.stride() == (72, 3, 1) and g_fea.stride() == (72, 1)
+        y, _, _ = sm._NormLinearFn.apply(g_fea, G, c, 1e-5, g_fea._scr_col_stats, g_fea._scr_deferred_dx)
+        sum((o * u).sum() for o, u in zip((y, feat, anc, off, gs), (g(u) for u in w["w"]))).backward()
+        runs.append([t.grad.clone() for t in (pc._anchor_feat, pc._anchor, pc._offset, pc._scaling, G, c)])
+    bw = [a for name, a in calls if name == "scr_anchor_gather_backward"]
+    rep.require(len(bw) == 2 and all(a[15] is not None and a[8] is None and a[19] == 72 for a in bw), "dx formed in the gather")
+    for name, a_, b_, c_ in zip(("d anchor_feat", "d anchor", "d offset", "d scaling", "d G", "d c"), runs[0], chain, ref):
+        rep.add(name, a_, b_, c_, rows=not name.endswith((" G", " c")))
+    rep.require(_same_bits(*runs), "bit-reproducible")
     rep.finish()
