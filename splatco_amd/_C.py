@@ -1,6 +1,6 @@
 """ctypes binding of the C-ABI in include/splatco_raster.h and of the family headers include/splatco_bilagrid.h,
-include/splatco_normals.h, include/splatco_tsdf.h, include/splatco_mesh.h and include/splatco_surfeval.h
-(libsplatco_raster.so, gfx950).
+include/splatco_normals.h, include/splatco_tsdf.h, include/splatco_tsdf_sparse.h, include/splatco_mesh.h and
+include/splatco_surfeval.h (libsplatco_raster.so, gfx950).
 
 This is the binding a maintainer of the reference would write in place of the pybind module
 `diff_gaussian_rasterization._C`.  There is NO fallback: if the HIP library
@@ -193,6 +193,29 @@ TSDF_SIGNATURES = [
     ("scr_tsdf_extract_faces_run", i32, i32, i32, i32, vp, vp, f32, vp, i64, vp, i64, vp, vp),
 ]
 
+class TsdfsView(C.Structure):
+    """struct scr_tsdfs_view (include/splatco_tsdf_sparse.h): the view and the rows of the camera-to-world matrix."""
+    _fields_ = [("view", TsdfView), ("c2w", f64 * 12)]
+
+
+# The block-sparse TSDF volume (include/splatco_tsdf_sparse.h); tests/test_tsdf_sparse_host.py checks every entry and the struct.
+TSDFS_ABI_VERSION = 1
+TSDFS_BLOCK = 8                                     # SCR_TSDFS_BLOCK
+TSDFS_SIGNATURES = [
+    ("scr_tsdfs_abi_version", i32),
+    ("scr_tsdfs_alloc_scratch_bytes", sz, i32, i32, i32),
+    ("scr_tsdfs_alloc_plan", i32, i32, i32, i32, vp, f32, f64, P(TsdfsView), vp, vp, P(i64), vp),
+    ("scr_tsdfs_alloc_run", i32, i32, i32, i32, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp),
+    ("scr_tsdfs_init_blocks", i32, i64, i64, vp, vp, vp, vp),
+    ("scr_tsdfs_integrate", i32, i32, i32, i32, vp, f32, f64, f32, i64, vp, vp, vp, vp, vp, P(TsdfsView), vp),
+    ("scr_tsdfs_neighbors", i32, i32, i32, i32, i64, vp, vp, vp),
+    ("scr_tsdfs_extract_scratch_bytes", sz, i64),
+    ("scr_tsdfs_extract_vertices_plan", i32, i32, i32, i32, i64, i64, i64, vp, vp, vp, vp, vp, f32, vp, P(i64), vp),
+    ("scr_tsdfs_extract_vertices_run", i32, i32, i32, i32, vp, f32, i64, i64, i64, vp, vp, vp, vp, vp, vp, f32, vp, i64, vp, vp, vp, vp),
+    ("scr_tsdfs_extract_faces_plan", i32, i32, i32, i32, i64, i64, i64, vp, vp, vp, vp, vp, f32, vp, P(i64), vp),
+    ("scr_tsdfs_extract_faces_run", i32, i32, i32, i32, i64, i64, i64, vp, vp, vp, vp, vp, f32, vp, i64, vp, i64, vp, vp),
+]
+
 # Mesh clean-up: components, size filter, vertex normals (include/splatco_mesh.h); tests/test_mesh_host.py checks every entry.
 MESH_ABI_VERSION = 1
 MESH_SIGNATURES = [
@@ -221,8 +244,8 @@ SURFEVAL_SIGNATURES = [
     ("scr_surfeval_score", i32, i64, vp, i32, P(f32), vp, vp, vp),
 ]
 _FAMILY_HEADERS = {"include/splatco_bilagrid.h": BILAGRID_SIGNATURES, "include/splatco_normals.h": NORMALS_SIGNATURES,
-                   "include/splatco_tsdf.h": TSDF_SIGNATURES, "include/splatco_mesh.h": MESH_SIGNATURES,
-                   "include/splatco_surfeval.h": SURFEVAL_SIGNATURES}
+                   "include/splatco_tsdf.h": TSDF_SIGNATURES, "include/splatco_tsdf_sparse.h": TSDFS_SIGNATURES,
+                   "include/splatco_mesh.h": MESH_SIGNATURES, "include/splatco_surfeval.h": SURFEVAL_SIGNATURES}
 _FAMILY_NAMES = frozenset(s[0] for sigs in _FAMILY_HEADERS.values() for s in sigs)
 
 
@@ -233,8 +256,8 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C splatco_amd/csrc`). "
             "There is deliberately no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, restype, *argtypes in (SIGNATURES + BILAGRID_SIGNATURES + NORMALS_SIGNATURES + TSDF_SIGNATURES + MESH_SIGNATURES
-                                     + SURFEVAL_SIGNATURES):
+    for name, restype, *argtypes in (SIGNATURES + BILAGRID_SIGNATURES + NORMALS_SIGNATURES + TSDF_SIGNATURES + TSDFS_SIGNATURES
+                                     + MESH_SIGNATURES + SURFEVAL_SIGNATURES):
         if not hasattr(lib, name):
             raise ImportError(f"{LIB_PATH} does not export {name}")
         f = getattr(lib, name)
@@ -247,6 +270,8 @@ def _load():
         raise ImportError(f"{LIB_PATH} has normals ABI version {lib.scr_normals_abi_version()}, expected {NORMALS_ABI_VERSION}")
     if lib.scr_tsdf_abi_version() != TSDF_ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has TSDF ABI version {lib.scr_tsdf_abi_version()}, expected {TSDF_ABI_VERSION}")
+    if lib.scr_tsdfs_abi_version() != TSDFS_ABI_VERSION:
+        raise ImportError(f"{LIB_PATH} has sparse-TSDF ABI version {lib.scr_tsdfs_abi_version()}, expected {TSDFS_ABI_VERSION}")
     if lib.scr_mesh_abi_version() != MESH_ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has mesh ABI version {lib.scr_mesh_abi_version()}, expected {MESH_ABI_VERSION}")
     if lib.scr_surfeval_abi_version() != SURFEVAL_ABI_VERSION:
@@ -342,8 +367,8 @@ def call(name, *args, device=None, check=True):
 
 def family_call(name, *args, device=None, check=True):
     """call() for the streamed entry points of the family headers (BILAGRID_SIGNATURES, include/splatco_bilagrid.h;
-    NORMALS_SIGNATURES, include/splatco_normals.h; TSDF_SIGNATURES, include/splatco_tsdf.h; MESH_SIGNATURES,
-    include/splatco_mesh.h; SURFEVAL_SIGNATURES, include/splatco_surfeval.h): any other name is refused with ValueError before anything is looked up or launched; everything
+    NORMALS_SIGNATURES, include/splatco_normals.h; TSDF_SIGNATURES, include/splatco_tsdf.h; TSDFS_SIGNATURES,
+    include/splatco_tsdf_sparse.h; MESH_SIGNATURES, include/splatco_mesh.h; SURFEVAL_SIGNATURES, include/splatco_surfeval.h): any other name is refused with ValueError before anything is looked up or launched; everything
     else is call()'s own code."""
     if name not in _FAMILY_NAMES:
         raise ValueError(f"family_call: {name} is not declared in {' or '.join(_FAMILY_HEADERS)}")

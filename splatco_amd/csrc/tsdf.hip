@@ -2,6 +2,8 @@
 //
 // The definition is include/splatco_tsdf.h's (tests/tsdf_ref.py restates it in numpy float64).  Everything between the float32
 // inputs and the float32 outputs is binary64 in the written order; the Makefile's -ffp-contract=off keeps it uncontracted.
+// The update of one node by one view (ts_node_update) and the lattice tables live in tsdf_node.h, which the block-sparse
+// family (tsdf_sparse.hip) shares: a node of a sparse block gets this kernel's own code.
 //
 // Integration.  One pass over the volume per batch of up to SCR_TSDF_MAX_VIEWS views.  The volume is walked as the LINEAR array
 // of its nx ny nz nodes: thread t owns the nodes 4 t .. 4 t + 3, x-adjacent except where a row ends inside the run, and carries
@@ -22,7 +24,7 @@
 // The predicates read the two (edge) or four (tetrahedron) tsdf values in load(); the eight weights of a cube are read in
 // keep(), and only for the few items that passed the sign test.
 #include "capi.h"
-#include "../../include/splatco_tsdf.h"
+#include "tsdf_node.h"
 
 namespace scr {
 
@@ -39,8 +41,6 @@ struct TsBatch {
     scr_tsdf_view v[SCR_TSDF_MAX_VIEWS];
 };
 static_assert(sizeof(TsBatch) + sizeof(TsVol) + 3 * sizeof(void*) <= 4096, "the batch must fit the kernel argument segment");
-
-__device__ __forceinline__ bool ts_finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }     // false for NaN
 
 __device__ __forceinline__ void ts_load4(const float* __restrict__ p, int64_t n0, int cnt, int vec, float (&v)[TS_RUN]) {
     if (vec) {
@@ -92,35 +92,7 @@ tsdf_integrate_kernel(TsVol g, TsBatch b, float* __restrict__ tsdf, float* __res
                 if (++j == g.ny) { j = 0; ++k; }
             }
             if (r >= cnt) continue;
-            const double x = g.lox + g.h * (double)ci, y = g.loy + g.h * (double)cj, z = g.loz + g.h * (double)ck;
-            const double xc = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
-            const double yc = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
-            const double zc = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
-            if (!(zc > V.near)) continue;
-            const double u = V.fx * xc / zc + V.cx, v = V.fy * yc / zc + V.cy;
-            const double fu = floor(u), fv = floor(v);
-            if (!(fu >= 0.0 && fu < (double)V.W && fv >= 0.0 && fv < (double)V.H)) continue;
-            const size_t pix = (size_t)(int)fv * V.W + (size_t)(int)fu;
-            const float D = V.depth[pix], A = V.alpha[pix];
-            bool ok = ts_finite(D) && ts_finite(A) && A >= V.min_alpha && D > 0.0f;
-            if (V.mask_kind == 1) ok = ok && ((const float*)V.mask)[pix] > 0.0f;
-            if (V.mask_kind == 2) ok = ok && ((const uint8_t*)V.mask)[pix] != 0;
-            if (!ok) continue;
-            const float zf = D / A;                                 // ONE binary32 division
-            const double sdf = (double)zf - zc;
-            if (sdf < -g.trunc) continue;
-            const double d = fmin(1.0, sdf / g.trunc);
-            const double Wt = (double)w[r], den = Wt + 1.0;
-            s[r] = (float)(((double)s[r] * Wt + d) / den);
-            if (COLOR && V.image) {
-                const float q0 = V.image[pix], q1 = V.image[HW + pix], q2 = V.image[2 * HW + pix];
-                if (ts_finite(q0) && ts_finite(q1) && ts_finite(q2)) {
-                    c0[r] = (float)(((double)c0[r] * Wt + (double)q0) / den);
-                    c1[r] = (float)(((double)c1[r] * Wt + (double)q1) / den);
-                    c2[r] = (float)(((double)c2[r] * Wt + (double)q2) / den);
-                }
-            }
-            w[r] = (float)fmin(den, g.max_weight);
+            ts_node_update<COLOR>(g, V, M, HW, ci, cj, ck, s[r], w[r], c0[r], c1[r], c2[r]);     // tsdf_node.h
         }
     }
     ts_store4(tsdf, n0, cnt, g.vec, s);
@@ -132,19 +104,7 @@ tsdf_integrate_kernel(TsVol g, TsBatch b, float* __restrict__ tsdf, float* __res
     }
 }
 
-// ------------------------------------------------------------------ extraction: lattice tables
-// a node offset inside a cube is a 3-bit code, bit 0 = +x, bit 1 = +y, bit 2 = +z
-__device__ __forceinline__ int ts_dir_code(int dir) { return ((0x59 >> dir) & 1) | (((0x6A >> dir) & 1) << 1) | (((0x74 >> dir) & 1) << 2); }
-// the lattice direction of an offset code 1..7: (1,0,0) (0,1,0) (1,1,0) (0,0,1) (1,0,1) (0,1,1) (1,1,1) -> 0 1 3 2 4 5 6
-__device__ __forceinline__ int ts_code_dir(int code) { return (int)((0xD62640u >> (3 * code)) & 7u); }
-// local node x = 0..3 of Kuhn tetrahedron q: corner, + e_pi1, + e_pi2, corner + (1, 1, 1); pi1 = q / 2, pi2 from a packed table
-__device__ __forceinline__ int ts_tet_code(int q, int x) {
-    const int a1 = q >> 1, a2 = (0x489 >> (2 * q)) & 3;
-    return x == 0 ? 0 : x == 1 ? (1 << a1) : x == 2 ? ((1 << a1) | (1 << a2)) : 7;
-}
-constexpr uint32_t TS_FLIP_EVEN = 0x4D24;               // inside masks whose triangles swap their last two vertices (even pi)
-constexpr uint32_t TS_ODD_PERM = 0x26;                  // q = 1, 2, 5: xzy, yxz, zyx
-
+// ------------------------------------------------------------------ extraction (the lattice tables are tsdf_node.h's)
 struct TsGrid {
     int nx, ny, nz;
     const float* __restrict__ tsdf;
@@ -283,28 +243,8 @@ tsdf_face_write_kernel(int64_t items, KeepSlot ks, const uint32_t* __restrict__ 
     for (int r = 0; r < COMPACT_ITEMS; ++r) {
         if (!c.keep[r] || (int64_t)c.pos[r] >= nf) continue;
         const TsSlot sl = ts_slot(ks.g, compact_item(r));
-        const uint32_t m = c.v[r].mask, out = ~m & 15u;
-        const int cnt = __builtin_popcount(m);
         int ex[3], ey[3];                               // the triangle's edges as pairs of local nodes
-        if (cnt == 2) {
-            const int a = __builtin_ctz(m), b = 31 - __builtin_clz(m), cc = __builtin_ctz(out), d = 31 - __builtin_clz(out);
-            ex[0] = a; ey[0] = cc;
-            if (sl.tri == 0) { ex[1] = a; ey[1] = d; ex[2] = b; ey[2] = d; }
-            else             { ex[1] = b; ey[1] = d; ex[2] = b; ey[2] = cc; }
-        } else {
-            const uint32_t one = cnt == 1 ? m : out;    // the single node, and the three others in ascending order
-            uint32_t rest = ~one & 15u;
-            const int a = __builtin_ctz(one);
-#pragma unroll
-            for (int e = 0; e < 3; ++e) {
-                ex[e] = a; ey[e] = __builtin_ctz(rest);
-                rest &= rest - 1;
-            }
-        }
-        if ((((TS_FLIP_EVEN >> m) ^ (TS_ODD_PERM >> sl.q)) & 1u) != 0) {
-            int t = ex[1]; ex[1] = ex[2]; ex[2] = t;
-            t = ey[1]; ey[1] = ey[2]; ey[2] = t;
-        }
+        ts_triangle_edges(c.v[r].mask, sl.q, sl.tri, ex, ey);
         const size_t o = 3 * (size_t)c.pos[r];
 #pragma unroll
         for (int e = 0; e < 3; ++e) {

@@ -34,9 +34,10 @@ triangle, wound counter-clockwise seen from the free-space side.  The mesh is in
     scene_io.write_ply_mesh("mesh.ply", vertices, faces, colors)
 
 or extract_mesh(views, pc, pipe, bg, voxel_size) for all of it.  Component filtering and vertex normals of the extracted mesh
-are splatco_amd.mesh's (extract_mesh(..., keep_largest=50, min_faces=50) ends in its clean_mesh).  Not built: sparse or hashed
-volumes and unbounded scenes, decimation, smoothing, texture baking, a weight other than 1 per observation, bilinear depth
-lookup, gradients, multi-rank fusion.
+are splatco_amd.mesh's (extract_mesh(..., keep_largest=50, min_faces=50) ends in its clean_mesh).  Scenes too large for a dense
+volume go to splatco_amd.tsdf_sparse (extract_mesh(..., sparse=True)), which stores 8 x 8 x 8-node blocks near the surface only.
+Not built: hashed volumes, decimation, smoothing, texture baking, a weight other than 1 per observation, bilinear depth lookup,
+gradients, multi-rank fusion.
 
 Every launch goes through _C.family_call.  There is no CPU path: a CPU tensor is a ValueError."""
 import ctypes
@@ -288,13 +289,15 @@ class TSDFVolume:
 
 
 def extract_mesh(views, pc, pipe, bg, voxel_size, bounds=None, trunc=None, min_alpha=0.5, antialiased=None, filter_3d=None,
-                 color=True, keep_largest=None, min_faces=None):
+                 color=True, sparse=False, keep_largest=None, min_faces=None):
     """Render every view in evaluation mode (evaluate._eval_mode, no_grad, prefilter_voxel then render(aux=True), as
     evaluate.render_views does), fuse depth, alpha and (color=True) the image of each into one volume as it is rendered, and
     extract the mesh: (vertices [Nv, 3] float32, faces [Nf, 3] int32, colors [Nv, 3] float32 or None) on the device.
     bounds: (lo, hi); None takes the bounding box of the anchors padded by trunc (default 4 voxel_size).  keep_largest /
     min_faces: where either is given, the mesh goes through mesh.clean_mesh (2DGS's post_process_mesh uses 50) before it is
-    returned; with both None nothing of that module runs."""
+    returned; with both None nothing of that module runs.  sparse=True fuses into a tsdf_sparse.SparseTSDFVolume over the same
+    bounds instead: every rendered view allocates its blocks and is integrated as it comes, so a block holds the views from
+    its first sighting on (that module's ORDER DEPENDENCE), and bounds beyond the dense volume's 2^31 nodes are accepted."""
     from . import knn_grid
     from .evaluate import _eval_mode
     from .renderer import prefilter_voxel, render
@@ -305,7 +308,11 @@ def extract_mesh(views, pc, pipe, bg, voxel_size, bounds=None, trunc=None, min_a
         lo, hi = np.asarray(lo, np.float64) - trunc, np.asarray(hi, np.float64) + trunc
     else:
         lo, hi = bounds
-    vol = TSDFVolume.from_bounds(lo, hi, h, trunc=trunc, color=color, device=pc.get_anchor.device)
+    if sparse:
+        from .tsdf_sparse import SparseTSDFVolume
+        vol = SparseTSDFVolume.from_bounds(lo, hi, h, trunc=trunc, color=color, device=pc.get_anchor.device)
+    else:
+        vol = TSDFVolume.from_bounds(lo, hi, h, trunc=trunc, color=color, device=pc.get_anchor.device)
     extra = {} if antialiased is None else {"antialiased": antialiased}
     if filter_3d is not None:
         extra["filter_3d"] = filter_3d
@@ -313,6 +320,9 @@ def extract_mesh(views, pc, pipe, bg, voxel_size, bounds=None, trunc=None, min_a
         for view in views:
             vis = prefilter_voxel(view, pc, pipe, bg)
             out = render(view, pc, pipe, bg, visible_mask=vis, aux=True, **extra)
+            if sparse:
+                vol.integrate(out["depth"], out["alpha"], view, image=out["render"] if color else None, min_alpha=min_alpha, near=0.05)
+                continue
             vol._integrate("extract_mesh", [out["depth"]], [out["alpha"]], [view], [out["render"]] if color else None, None,
                            min_alpha, 0.05, 1)
     if keep_largest is None and min_faces is None:
