@@ -469,9 +469,11 @@ int scr_anchor_gather_backward(int64_t N, int64_t V, const int64_t* inverse_inde
  *     y = xhat G^T + c,  xhat = (x - mean) * inv,  inv = 1 / sqrt(var + eps),  mean / var (biased) over the V rows.
  * forward writes y [V,32] and mean, var, inv [d] (the caller updates the running statistics from mean / var).
  * backward, given dy [V,32] (row stride lddy, 16-byte aligned), writes dG [32,d], dc [32] and, unless dx is NULL,
- * dx [V,d] (row stride lddx) including both BatchNorm reduction terms.  d <= 80; x rows may have any stride (16-byte
- * aligned rows take the wide-load path).  Sums over the rows are formed per workgroup and combined in a fixed order:
- * bit-reproducible.  Scratch from scr_norm_linear_scratch_bytes(V), the same block for forward and backward. */
+ * dx [V,d] (row stride lddx) including both BatchNorm reduction terms.  d <= 80; x rows may have any stride.
+ * With x 16-byte aligned and ldx a multiple of 4 the rows are read 16 bytes at a time.  Every row of x, the last one
+ * included, must then cover its columns [0, roundup4(d)); ldx >= d guarantees that.  No other float of x's matrix is read.
+ * Sums over the rows are formed per workgroup and combined in a fixed order: bit-reproducible.  Scratch from
+ * scr_norm_linear_scratch_bytes(V), the same block for forward and backward. */
 size_t scr_norm_linear_scratch_bytes(int64_t V);
 /* Normalised tri-plane sample coordinates of contiguous xyz[V,3] in the box [lo, hi] (host floats):
  * out = (xyz - lo) / (hi - lo) * 2 - 1 (scene/grids.py:146), the same IEEE operations in the same order as the four
@@ -503,13 +505,14 @@ int scr_norm_running_stats(int32_t L, int32_t d, const int32_t* widths_host, con
 int scr_norm_linear_forward(int64_t V, int32_t d, const float* x, int32_t ldx, const float* G, const float* c, float eps,
                             float* y, float* mean, float* var, float* inv, void* scratch, const float* col_stats,
                             int32_t col_stat_rows, void* stream);
+/* Pass 3 of the backward on its own, from a coefficient block scr_norm_linear_backward left in coef_out: for a consumer of
+ * the coefficients that cannot form the rows itself after all (a layout outside its fused pass).  coef: [32 + 2][80] floats,
+ * 16-byte aligned; its columns d.. are never carried into a stored column of dx. */
+int scr_norm_linear_dx(int64_t V, int32_t d, const float* x, int32_t ldx, const float* dy, int32_t lddy, const float* coef,
+                       float* dx, int32_t lddx, void* stream);
 /* coef_out (ABI 27; may be NULL): [32 + 2][80] floats that receive Gi = G * inv | k0 | k1, the coefficients of
  * dx[v][n] = k0[n] + x[v][n] k1[n] + sum_m dy[v][m] Gi[m][n], for a consumer that forms the rows of dx itself
  * (scr_anchor_gather_backward: nl_coef); with dx NULL the [V,d] matrix is then never written. */
-/* Pass 3 of the backward on its own, from a coefficient block scr_norm_linear_backward left in coef_out: for a consumer of
- * the coefficients that cannot form the rows itself after all (a layout outside its fused pass). */
-int scr_norm_linear_dx(int64_t V, int32_t d, const float* x, int32_t ldx, const float* dy, int32_t lddy, const float* coef,
-                       float* dx, int32_t lddx, void* stream);
 int scr_norm_linear_backward(int64_t V, int32_t d, const float* x, int32_t ldx, const float* dy, int32_t lddy, const float* G,
                              const float* mean, const float* inv, float* dx, int32_t lddx, float* dG, float* dc,
                              void* scratch, float* coef_out, void* stream);

@@ -10,7 +10,7 @@
 // x has millions of rows and d <= 80 columns: every op is a pass over [V,d] at HBM speed or it is wasted time.  torch
 // needs var_mean + addmm (forward) and sum + a slab-split bmm + addmm + addcmul (backward): 8 ms of the 33 ms
 // configs[2] step.  Here:
-//   forward : nl_stats (one pass: shifted sums per column, fp64 combination) -> nl_forward (one pass: f32 MFMA with
+//   forward : nl_stats (one pass: shifted sums per column in fp64, fp64 combination) -> nl_forward (one pass: f32 MFMA with
 //             the column-scaled weights held in registers)
 //   backward: nl_bwd_reduce (one pass over dy and x: dy^T x and the column sums of dy on the MFMA, per-workgroup
 //             partials summed in a fixed order) -> nl_bwd_finish (32 x d algebra: weight gradient and both BatchNorm
@@ -49,18 +49,25 @@ static inline int nl_bwd_wgs(int64_t V) {
     return (int)(blocks < 1024 ? (blocks > 0 ? blocks : 1) : 1024);
 }
 
-// ---- column statistics, pass 1: per-workgroup sums of (x - shift) and (x - shift)^2, shift = the first row
+// ---- column statistics, pass 1: per-workgroup sums of (x - shift) and (x - shift)^2, shift = the first row.  A lane forms
+// the difference and both sums in fp64 (exact products, 2^-53 per addition; the pass stays a stream of x at memory speed:
+// four fp64 operations per element where the fp32 form had four fp32 ones); the slab's two sums are rounded to fp32 ONCE,
+// into the same [2][NL_DP] floats per slab a caller's col_stats has.  With fp32 lanes a column whose first row lay a few
+// deviations from its mean carried 512 roundings of a running sum of size 512 |x0 - mean| into the mean: 1.6e-4 of a centred
+// column's scale at V = 20 000 where the framework's var_mean stands at 9e-7 (tests/test_gpu_renderer.py, per-column
+// figures).  That was rounding, not a fault: against the a-priori bound of 516 / 1026 fp32 terms per lane the fp32 form
+// stood at 0.73 at worst (tests/f64_refs.py: nl_n_s); it missed the framework's own accuracy, which the per-column test asks.
 template <int CW>   // lanes per row: 64 (d <= 64) or 128
 __global__ void __launch_bounds__(256)
 nl_stats_partial_kernel(int64_t V, int d, int slab, const float* __restrict__ x, int ldx, float* __restrict__ partial) {
     constexpr int RG = 256 / CW;
-    __shared__ float red[2][256];
+    __shared__ double red[2][256];
     const int c = threadIdx.x % CW, rg = threadIdx.x / CW;
     const int64_t r0 = (int64_t)blockIdx.x * slab;
     const int rows = (int)min((int64_t)slab, V - r0);
-    float s = 0.0f, q = 0.0f;
+    double s = 0.0, q = 0.0;
     if (c < d) {
-        const float shift = x[c];
+        const double shift = (double)x[c];
         const float* p = x + (size_t)r0 * ldx + c;
         int r = rg;
         for (; r + 7 * RG < rows; r += 8 * RG) {
@@ -69,29 +76,29 @@ nl_stats_partial_kernel(int64_t V, int d, int slab, const float* __restrict__ x,
             for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(r + u * RG) * ldx];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                const float t = v[u] - shift;
+                const double t = (double)v[u] - shift;
                 s += t;
-                q += t * t;
+                q = __builtin_fma(t, t, q);
             }
         }
         for (; r < rows; r += RG) {
-            const float t = p[(size_t)r * ldx] - shift;
+            const double t = (double)p[(size_t)r * ldx] - shift;
             s += t;
-            q += t * t;
+            q = __builtin_fma(t, t, q);
         }
     }
     red[0][threadIdx.x] = s;
     red[1][threadIdx.x] = q;
     __syncthreads();
     if (threadIdx.x < CW && threadIdx.x < d) {
-        float ss = 0.0f, qq = 0.0f;
+        double ss = 0.0, qq = 0.0;
 #pragma unroll
         for (int g = 0; g < RG; ++g) {
             ss += red[0][g * CW + threadIdx.x];
             qq += red[1][g * CW + threadIdx.x];
         }
-        partial[((size_t)blockIdx.x * 2 + 0) * NL_DP + threadIdx.x] = ss;
-        partial[((size_t)blockIdx.x * 2 + 1) * NL_DP + threadIdx.x] = qq;
+        partial[((size_t)blockIdx.x * 2 + 0) * NL_DP + threadIdx.x] = (float)ss;
+        partial[((size_t)blockIdx.x * 2 + 1) * NL_DP + threadIdx.x] = (float)qq;
     }
 }
 
@@ -157,14 +164,15 @@ nl_stats_finish_kernel(int64_t V, int d, int nwg, const float* __restrict__ x, c
 }
 
 // 16 bytes of a row (or four dwords when rows are not 16-byte aligned), zero beyond column d.  The aligned load is
-// UNCONDITIONAL -- the address is clamped into the row (the caller clamps the row into the matrix) and the components
-// beyond d are zeroed with selects: a load under `if (k + 3 < d)` makes the compiler close every load with its own
-// s_waitcnt vmcnt(0) at the join, i.e. the Q loads of a row are served one memory round trip after the other.
+// UNCONDITIONAL -- the address is clamped to the row's last 16-byte group that holds a column of x, (d - 1) & ~3 (the
+// caller clamps the row into the matrix), so a lane reads inside columns [0, roundup4(d)) of its own row whatever ld is,
+// and the components beyond d are zeroed with selects: a load under `if (k + 3 < d)` makes the compiler close every load
+// with its own s_waitcnt vmcnt(0) at the join, i.e. the Q loads of a row are served one memory round trip after the other.
 template <bool ALIGNED>
 __device__ __forceinline__ nlf4 nl_raw4(const float* __restrict__ row, int k, int d, int ld) {     // the loads alone
     nlf4 v;
     if (ALIGNED) {
-        v = *(const nlf4*)(row + min(k, ld - 4));      // k > ld - 4 means k >= ld >= d (both multiples of 4): all masked by nl_mask4
+        v = *(const nlf4*)(row + min(k, (d - 1) & ~3));      // k beyond it means k >= roundup4(d) >= d: all masked by nl_mask4
     } else {
         v.x = row[min(k, d - 1)];
         v.y = row[min(k + 1, d - 1)];
@@ -345,13 +353,13 @@ nl_bwd_finish_kernel(int64_t V, int d, const float* __restrict__ G, const float*
 template <int NT, bool ALIGNED>
 __global__ void __launch_bounds__(256)
 nl_bwd_dx_kernel(int64_t V, int d, const float* __restrict__ x, int ldx, const float* __restrict__ dy, int lddy,
-                 const float* __restrict__ coef, float* __restrict__ dx, int lddx) {
+                 const float* __restrict__ gk, float* __restrict__ dx, int lddx) {     // gk: Gi [32][NL_DP] | k0 [NL_DP] | k1 [NL_DP]
     const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
     float a[NT][8];     // A[m = feature 16 nt + r][k = dy column 16 q + 4 g + j], step s = 4 q + j
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-        for (int s = 0; s < 8; ++s) a[nt][s] = coef[NLC_GI + (16 * (s >> 2) + 4 * g + (s & 3)) * NL_DP + 16 * nt + r];
+        for (int s = 0; s < 8; ++s) a[nt][s] = gk[(16 * (s >> 2) + 4 * g + (s & 3)) * NL_DP + 16 * nt + r];
     const int64_t blocks = (V + 15) / 16, stride = (int64_t)gridDim.x * 4;
     for (int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); blk < blocks; blk += stride) {
         const int64_t row = blk * 16 + r;
@@ -367,7 +375,7 @@ nl_bwd_dx_kernel(int64_t V, int d, const float* __restrict__ x, int ldx, const f
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const int n0 = 16 * nt + 4 * g;
-            const nlf4 k0 = *(const nlf4*)(coef + NLC_K0 + n0), k1 = *(const nlf4*)(coef + NLC_K1 + n0);
+            const nlf4 k0 = *(const nlf4*)(gk + NL_OUT * NL_DP + n0), k1 = *(const nlf4*)(gk + (NL_OUT + 1) * NL_DP + n0);
             nlf4 acc = k0 + xv[nt] * k1;
 #pragma unroll
             for (int s = 0; s < 8; ++s) acc = nl_mfma(a[nt][s], dq[s >> 2][s & 3], acc);
@@ -529,14 +537,14 @@ static bool nl_pairs_ok(unsigned char (&at)[NL_DP], int L, int d, const int* dd,
     return true;
 }
 
-// pass 3 of the backward: dx from the coefficient block (reads coef + NLC_GI / NLC_K0 / NLC_K1 only)
-static void nl_launch_dx(int64_t V, int d, const float* x, int ldx, const float* dy, int lddy, const float* coef, float* dx, int lddx,
+// pass 3 of the backward: dx from gk = Gi | k0 | k1 (the scratch block's coef + NLC_GI, or a caller's copy of it)
+static void nl_launch_dx(int64_t V, int d, const float* x, int ldx, const float* dy, int lddy, const float* gk, float* dx, int lddx,
                          hipStream_t st) {
     const bool al = ldx % 4 == 0 && lddx % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dx & 15) == 0;
 #define SCR_NL_DX(NN)                                                                                                                          \
     case NN:                                                                                                                                   \
-        if (al) nl_bwd_dx_kernel<NN, true><<<nl_grid(V, nl_bwd_dx_kernel<NN, true>), 256, 0, st>>>(V, d, x, ldx, dy, lddy, coef, dx, lddx);     \
-        else nl_bwd_dx_kernel<NN, false><<<nl_grid(V, nl_bwd_dx_kernel<NN, false>), 256, 0, st>>>(V, d, x, ldx, dy, lddy, coef, dx, lddx);      \
+        if (al) nl_bwd_dx_kernel<NN, true><<<nl_grid(V, nl_bwd_dx_kernel<NN, true>), 256, 0, st>>>(V, d, x, ldx, dy, lddy, gk, dx, lddx);       \
+        else nl_bwd_dx_kernel<NN, false><<<nl_grid(V, nl_bwd_dx_kernel<NN, false>), 256, 0, st>>>(V, d, x, ldx, dy, lddy, gk, dx, lddx);        \
         break;
     switch ((d + 15) / 16) { SCR_NL_DX(1) SCR_NL_DX(2) SCR_NL_DX(3) SCR_NL_DX(4) SCR_NL_DX(5) }
 #undef SCR_NL_DX
@@ -690,7 +698,7 @@ int scr_norm_linear_backward(int64_t V, int32_t d, const float* x, int32_t ldx, 
       static_assert(NLC_K0 == NLC_GI + NL_OUT * NL_DP && NLC_K1 == NLC_K0 + NL_DP, "Gi | k0 | k1 are contiguous");
       if (coef_out && hipMemcpyAsync(coef_out, coef + NLC_GI, (size_t)(NL_OUT + 2) * NL_DP * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
           return fail("copy of the backward coefficients failed: %s", hipGetErrorString(hipGetLastError()));
-      if (dx) nl_launch_dx(V, d, x, ldx, dy, lddy, coef, dx, lddx, st);
+      if (dx) nl_launch_dx(V, d, x, ldx, dy, lddy, coef + NLC_GI, dx, lddx, st);
     }
     CHECK_LAUNCH("norm_linear_backward", 0, st);
     return 0;
@@ -705,9 +713,10 @@ int scr_norm_linear_dx(int64_t V, int32_t d, const float* x, int32_t ldx, const 
     if (!x || !dy || !coef || !dx) return fail("NULL argument");
     if (d > NL_DP) return fail("d = %d input columns exceed the supported 80", d);
     if (lddy % 4 != 0 || ((uintptr_t)dy & 15) != 0) return fail("dy must be 16-byte aligned with a row stride that is a multiple of 4 floats");
+    if (((uintptr_t)coef & 15) != 0) return fail("coef must be 16-byte aligned (k0 and k1 are read 16 bytes at a time)");
     hipStream_t st = (hipStream_t)stream;
     { ProfScope ps_(SCR_PROF_NORM_LINEAR_BACKWARD, st);
-      nl_launch_dx(V, d, x, ldx, dy, lddy, coef - NLC_GI, dx, lddx, st); }
+      nl_launch_dx(V, d, x, ldx, dy, lddy, coef, dx, lddx, st); }
     CHECK_LAUNCH("norm_linear_dx", 0, st);
     return 0;
 }

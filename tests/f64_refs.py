@@ -6,6 +6,8 @@ behind it, and the inputs the parity tests feed them.  TEST INFRASTRUCTURE ONLY;
   expand_f64      torch_restatements.expand_torch_chain on double inputs                     -> checker of csrc/expand.hip
   ssim_f64        losses.l1_loss + losses.ssim in float64 (and the inputs of pair_l1 / scaling_reg) -> checker of csrc/ssim.hip
   gather_f64      the four visible-anchor gathers, exp and cat; gather_dx_f64 the fused dx         -> checker of csrc/anchor_gather.hip
+  nl_*_f64        BatchNorm1d (batch statistics) folded into Linear(d, 32), launch by launch, and the parameter fold;
+                  nl_*_bounds the a-priori bound of every output element                          -> checker of csrc/normlinear.hip
 
 The references are plain torch op chains, written from scene_model.py / torch_restatements.py, dtype- and device-agnostic:
 on float64 CPU tensors they are the reference, on float32 device tensors the "framework chain" whose own error against
@@ -892,3 +894,440 @@ def gather_norm_linear_run(idx, params, G, c, w, eps=1e-5):
     y = ((x - x.mean(dim=0)) / torch.sqrt(x.var(dim=0, unbiased=False) + eps)) @ G.T + c
     sum((o * u).sum() for o, u in zip((y, feat, anc, off, gs), w)).backward()
     return [p.grad for p in ps] + [G.grad, c.grad]
+
+
+# ---------------------------------------------------------------------------------------------------------- norm-linear
+# csrc/normlinear.hip at its own C ABI: BatchNorm1d (batch statistics) folded into Linear(d, 32).  Every launch is checked
+# against float64 ON THAT LAUNCH'S OWN INPUTS (the forward GEMM takes the kernel's fp32 mean / inv as exact numbers, the dx
+# pass the coefficient block it was handed), so every bound below is rounding alone plus one stated conditioning term.
+# u = 2^-24; a bound is u times the number of fp32 operations on the longest chain into an element times the sum of the
+# absolute values of the terms.  The chain lengths, read from the kernels:
+NL_U = 2.0 ** -24
+NL_OUT, NL_DP, NL_SLAB = 32, 80, 2048            # output features; padded coefficient rows; rows per statistics workgroup
+NL_STAT_EXTRA = 3                                # an fp32 lane's x - shift, t * t and the rounding of its partial (nl_n_s's companion)
+NL_STAT_COMBINE = 2                              # the kernel's statistics: nl_stats_partial_kernel subtracts, squares and adds in fp64
+                                                 # and rounds a slab's two sums to fp32 once (1) + slack (1); a caller's col_stats are
+                                                 # roundings of exact sums in the same way; nl_stats_finish_kernel adds them in fp64
+NL_INV_ROUNDINGS = 2                             # 1 / sqrtf(vf + eps): the sum's rounding is halved by the root; the root and the division
+                                                 # are correctly rounded (half an ulp each, at most u of the result)
+NL_Y_EXTRA = 4                                   # G * inv, Gs * mean, c - acc, the accumulator's start: nl_stats_finish_kernel + nl_forward_kernel
+NL_FINISH_TERMS = NL_OUT + 2                     # nl_bwd_finish_kernel: u and w are 32-term sums of two-factor products
+NL_DX_TERMS = NL_OUT + 4                         # nl_bwd_dx_kernel: k0 + x k1 (2 roundings), 32 MFMA products, slack 2
+NL_BWD_CAP, NL_BWD_LOW = 1024, 256               # nl_bwd_wgs: at most 1024 workgroups of 64 rows; never fewer resident than one per CU
+NL_FWD_GRID_ROWS = 8 * 256 * 64                  # the most rows one round of nl_forward / nl_bwd_dx holds (8 workgroups x 256 CUs x 64)
+
+
+def nl_cw(d):
+    """Lanes per row of nl_stats_partial_kernel."""
+    return 64 if d <= 64 else 128
+
+
+def nl_n_s(d):
+    """Terms a lane of nl_stats_partial_kernel adds one after the other (slab / RG rows) plus the RG groups it folds: the
+    chain an fp32 lane would carry into a partial (nl_restated_f32 sums in fp32; the kernel's lanes in fp64, NL_STAT_COMBINE)."""
+    rg = 256 // nl_cw(d)
+    return NL_SLAB // rg + rg
+
+
+def nl_slabs(V):
+    return -(-V // NL_SLAB)
+
+
+def nl_partials(V):
+    """Workgroups (= partials) of nl_bwd_reduce_kernel when the chip holds them all: min(ceil(V / 64), 1024)."""
+    return max(1, min(-(-V // 64), NL_BWD_CAP))
+
+
+def nl_n_h(V):
+    """Worst chain into an element of Hraw / sdy: (rows a wave walks) / 4 MFMA steps, 4 waves, partials / 8 per lane of
+    nl_bwd_sum_kernel, its 8 groups (the 8 also covers the three roundings of (Hraw - sdy mean) inv in the finish kernel).
+    The grid is min(nl_partials, what the chip holds): both ends are taken."""
+    worst = 0
+    for g in {nl_partials(V), min(nl_partials(V), NL_BWD_LOW)}:
+        rows = -(-(-(-V // 16)) // (4 * g)) * 16
+        worst = max(worst, rows // 4 + 4 + -(-g // 8) + 8)
+    return worst
+
+
+def nl_loop_forms(n, first, step):
+    """{'unrolled', 'tail'}: the forms lane-group 0 of a `for (; i + first < n; i += step) ...; for (; i < n; ...)` pair runs."""
+    forms, i = set(), 0
+    while i + first < n:
+        forms.add("unrolled")
+        i += step
+    if i < n:
+        forms.add("tail")
+    return forms
+
+
+def nl_case_facts(V, d, ldx, off=0, lddx=None, dx_off=0, stat_rows=0):
+    """What a call makes the kernels do, from its shapes alone: dict(Q (= NT), CW, aligned (forward), aligned_dx, slabs,
+    partials, finish (loop forms of nl_stats_finish_kernel), slab_tail (loop forms the row groups of nl_stats_partial_kernel run on the
+    last slab, together), strides (rounds of the forward / dx grid-stride loop)).  off / dx_off: floats between a 16-byte boundary and x / dx."""
+    rg = 256 // nl_cw(d)
+    al = ldx % 4 == 0 and off % 4 == 0
+    nwg = stat_rows or nl_slabs(V)
+    last = (V - 1) % NL_SLAB + 1                 # rows of the last slab; row group g of rg owns rows g, g + rg, ...
+    return dict(Q=-(-d // 16), CW=nl_cw(d), aligned=al,
+                aligned_dx=None if lddx is None else al and lddx % 4 == 0 and dx_off % 4 == 0,
+                slabs=nl_slabs(V), partials=nl_partials(V), finish=nl_loop_forms(nwg, 56, 64),
+                slab_tail=set().union(*(nl_loop_forms(max(0, -(-(last - g) // rg)), 7, 8) for g in range(rg))),
+                strides=-(-V // NL_FWD_GRID_ROWS))
+
+
+NL_LAYOUTS = ("packed", "padded", "block", "off1", "odd")
+
+
+def _up4(n):
+    return (n + 3) // 4 * 4
+
+
+def nl_layout(t, layout, fill=float("nan")):
+    """t [V,w] inside a `fill`-filled allocation on t's device -> (the flat leaf, the view, its row stride, floats from the
+    leaf's 16-byte aligned start to the view).  packed: ld = w; padded: ld = roundup4(w); block: columns 4 .. 4 + w - 1 of a
+    [V, roundup4(w) + 8] matrix (aligned, NaN on both sides); off1: columns 1 .. w of a [V, roundup4(w + 1)] matrix (stride a
+    multiple of 4, rows 4-byte aligned only); odd: ld = w + 1 if that is odd, else w + 3 (never w itself; odd for an even
+    w, and for w = 1 mod 4 a multiple of 4 with three pad columns)."""
+    V, w = t.shape
+    ld, off = {"packed": (w, 0), "padded": (_up4(w), 0), "block": (_up4(w) + 8, 4), "off1": (_up4(w + 1), 1),
+               "odd": (w + 1 if (w + 1) % 2 else w + 3, 0)}[layout]
+    leaf = torch.full((V * ld + 4,), fill, dtype=t.dtype, device=t.device)
+    view = leaf[off:off + (V - 1) * ld + w].as_strided((V, w), (ld, 1))
+    view.copy_(t)
+    return leaf, view, ld, off
+
+
+def nl_inputs(V, d, seed=0):
+    """fp32 CPU inputs of one case: x [V,d] (the first d // 2 columns -5 +- 0.3, the log-scalings; the rest N(0,1)), G [32,d]
+    (0.2 randn), c [32], dy [V,32] -- what test_fused_norm_linear_matches_batchnorm_linear_chain draws."""
+    g = torch.Generator().manual_seed(V * 131 + d + 7919 * seed)
+    r = lambda *s: torch.randn(*s, generator=g)
+    x = r(V, d)
+    x[:, : d // 2] = x[:, : d // 2] * 0.3 - 5.0
+    return dict(V=V, d=d, x=x, G=r(NL_OUT, d) * 0.2, c=r(NL_OUT), dy=r(V, NL_OUT))
+
+
+def nl_coef_block(d, seed, pad=float("nan")):
+    """A free-standing coefficient block [34,80] = Gi [32] | k0 | k1, drawn (Gi 0.3 randn, k0 / k1 randn), columns d.. = pad."""
+    g = torch.Generator().manual_seed(50_000 + 97 * d + seed)
+    coef = torch.full((NL_OUT + 2, NL_DP), pad)
+    coef[:, :d] = torch.randn(NL_OUT + 2, d, generator=g)
+    coef[:NL_OUT, :d] *= 0.3
+    return coef
+
+
+NL_REGIME_COLUMNS = ("normal", "minus5", "constant", "1e4", "outlier_first", "alternating", "last_row_only", "row2048_only")
+NL_REGIME_V = 4099
+
+
+def nl_regime_matrix():
+    """[4099,8] fp32, one column per statistics regime (NL_REGIME_COLUMNS)."""
+    V = NL_REGIME_V
+    g = torch.Generator().manual_seed(4099)
+    r = lambda: torch.randn(V, generator=g)
+    x = torch.zeros(V, 8)
+    x[:, 0] = r()
+    x[:, 1] = r() * 0.3 - 5.0
+    x[:, 2] = 3.25
+    x[:, 3] = r() * 1e-2 + 1e4
+    x[:, 4] = r()
+    x[0, 4] = 1e3                                                      # the shift is a thousand deviations from the mean
+    x[:, 5] = 1.0 - 2.0 * (torch.arange(V) % 2)
+    x[V - 1, 6] = 1.0
+    x[NL_SLAB, 7] = 1.0
+    return x
+
+
+def nl_col_stats(x, rows, seed=0):
+    """[rows,2,80] fp32: roundings of the float64 sums of (x - x[0]) and (x - x[0])^2 over a seeded random partition of the
+    rows of x into `rows` non-empty disjoint sets; columns d.. are 0."""
+    V, d = x.shape
+    assert 1 <= rows <= V
+    g = torch.Generator().manual_seed(rows * 1009 + V + seed)
+    owner = torch.cat([torch.arange(rows), torch.randint(0, rows, (V - rows,), generator=g)])[torch.randperm(V, generator=g)]
+    t = _f64(x) - _f64(x)[0]
+    st = torch.zeros(rows, 2, NL_DP, dtype=torch.float64)
+    st[:, 0, :d].index_add_(0, owner, t)
+    st[:, 1, :d].index_add_(0, owner, t * t)
+    return st.float()
+
+
+# ---- references (dtype-agnostic op chains)
+def nl_stats_f64(x):
+    """(mean, biased variance) per column."""
+    m = x.mean(dim=0)
+    return m, ((x - m) ** 2).mean(dim=0)
+
+
+def nl_forward_f64(x, G, c, mean, inv):
+    return ((x - mean) * inv) @ G.T + c
+
+
+def nl_backward_f64(x, dy, G, mean, inv):
+    """(dG, dc, Gi, k0, k1) by the algebra in csrc/normlinear.hip's header: dG = (dy^T x - sdy mean^T) inv, dc = sdy,
+    u = G^T sdy, w = sum_m G dG, k1 = -inv^2 w / V, k0 = -inv u / V - mean k1, Gi = G inv."""
+    V = x.shape[0]
+    sdy = dy.sum(dim=0)
+    dG = (dy.T @ x - sdy[:, None] * mean) * inv
+    u, w = G.T @ sdy, (G * dG).sum(dim=0)
+    k1 = -(inv * inv) * w / V
+    return dG, sdy, G * inv, -inv * u / V - mean * k1, k1
+
+
+def nl_dx_f64(x, dy, Gi, k0, k1):
+    return k0 + x * k1 + dy @ Gi
+
+
+def nl_fold_f64(W, b, gamma, beta, widths, cols, d, col_at=None):
+    """(G [32,d], c [32]) of sum_i Linear_i(BatchNorm_i(.)) as scene_model._norm_linear's non-device branch folds them:
+    G_ref[:, cols_i + j] += W_i[:, j] gamma_i[j], c = sum_i (W_i beta_i + b_i); col_at: G[:, col_at[j]] = G_ref[:, j]."""
+    G = torch.zeros(NL_OUT, d, dtype=W[0].dtype)
+    for Wi, gi, c0, w in zip(W, gamma, cols, widths):
+        G[:, c0:c0 + w] = G[:, c0:c0 + w] + Wi * gi
+    c = sum(Wi @ bi + b_ for Wi, bi, b_ in zip(W, beta, b))
+    if col_at is not None:
+        G = torch.zeros_like(G).index_copy(1, torch.as_tensor(list(col_at), dtype=torch.long), G)
+    return G, c
+
+
+def nl_fold_backward_f64(dG, dc, W, gamma, beta, widths, cols, col_at=None, apply_at=True):
+    """[(dW_i, db_i, dgamma_i, dbeta_i)]: dW_i = dG_ref[:, block i] gamma_i + dc beta_i^T, db_i = dc, dgamma_i = sum_r
+    dG_ref W_i, dbeta_i = W_i^T dc, with dG_ref[:, j] = dG[:, col_at[j]].  apply_at=False: the planted fault (dG read as it lies)."""
+    if col_at is not None and apply_at:
+        dG = dG.index_select(1, torch.as_tensor(list(col_at), dtype=torch.long))
+    out = []
+    for Wi, gi, bi, c0, w in zip(W, gamma, beta, cols, widths):
+        blk = dG[:, c0:c0 + w]
+        out.append((blk * gi + dc[:, None] * bi, dc.clone(), (blk * Wi).sum(dim=0), Wi.T @ dc))
+    return out
+
+
+def nl_running_f64(run_mean, run_var, momentum, mean, var, n, widths, cols, col_at=None, unbiased=True):
+    """[(running_mean_i, running_var_i)] after nn.BatchNorm1d's update: (1 - m) old + m new, the variance times n / (n - 1)
+    (n = 1: times 1).  unbiased=False: the planted fault n / n."""
+    if col_at is not None:
+        at = torch.as_tensor(list(col_at), dtype=torch.long)
+        mean, var = mean.index_select(0, at), var.index_select(0, at)
+    f = n / max(n - 1, 1) if unbiased else 1.0
+    return [(rm * (1 - m) + m * mean[c0:c0 + w], rv * (1 - m) + m * (var[c0:c0 + w] * f))
+            for rm, rv, m, c0, w in zip(run_mean, run_var, momentum, cols, widths)]
+
+
+# ---- a-priori bounds, per element, float64, from the inputs alone
+def nl_excess(got, ref, bound):
+    """max |got - ref| / bound over the elements, 0 / 0 = 0, NaN = inf: at most 1 when every element is inside its bound."""
+    got, ref, bound = _f64(got), _f64(ref), _f64(bound)
+    assert got.shape == ref.shape == bound.shape, (got.shape, ref.shape, bound.shape)
+    if got.numel() == 0:
+        return 0.0
+    dlt = (got - ref).abs()
+    dlt = torch.where(torch.isnan(dlt), torch.full_like(dlt, float("inf")), dlt)
+    return float(torch.where(dlt == 0, torch.zeros_like(dlt), dlt / bound).max())
+
+
+def nl_stats_bounds(x, eps, n_s):
+    """{'mean' | 'var' | 'inv': (float64 reference, bound)} of the shifted one-pass statistics of the fp32 matrix x, shift
+    x0 = x[0], n_s fp32 terms per partial sum (NL_STAT_COMBINE for the kernel on either path: its lanes sum in fp64; nl_n_s(d)
+    for sums formed in fp32, f64_refs.nl_restated_f32):
+      shifted mean m = mean - x0:  bm = (n_s + 3) u mean_v |x - x0|;   mean = fl(x0 + m):  bm + u |mean|
+      var = E t^2 - m^2:           (n_s + 3) u (var + m^2) + 2 |m| bm + bm^2 + u var
+    var + m^2 = E t^2 is the CONDITIONING of a shifted one-pass variance: the rounding of the raw second moment stays when
+    m^2 is taken off, so a shift |m| / sigma deviations from the mean costs (|m| / sigma)^2 in relative accuracy.
+    (2 |m| bm, not 2 |m| times the whole mean bound: the variance is formed from m before x0 is added and rounded.)
+      inv = 1 / sqrt(var + eps):   the interval [var - b, var + b] mapped through it, plus 2 u inv (the addition of eps -- half of its
+                                   error passes the root --, the correctly rounded root and division)"""
+    x = _f64(x)
+    eps = float(torch.tensor(eps, dtype=torch.float32))
+    mean, var = nl_stats_f64(x)
+    t = x - x[0]
+    m = mean - x[0]
+    k = (n_s + NL_STAT_EXTRA) * NL_U
+    bm = k * t.abs().mean(dim=0)
+    bv = k * (var + m * m) + 2 * m.abs() * bm + bm * bm + NL_U * var
+    inv = 1.0 / torch.sqrt(var + eps)
+    hi, lo = 1.0 / torch.sqrt((var - bv).clamp_min(0) + eps), 1.0 / torch.sqrt(var + bv + eps)
+    return {"mean": (mean, bm + NL_U * mean.abs()), "var": (var, bv),
+            "inv": (inv, torch.maximum(hi - inv, inv - lo) + NL_INV_ROUNDINGS * NL_U * hi)}
+
+
+def nl_y_bound(x, G, c, mean, inv):
+    """(d + 4) u (sum_n |G_mn inv_n| (|x_vn| + |mean_n|) + |c_m|)  [V,32]; d products each in the bias and in the GEMM."""
+    x, G, c, mean, inv = (_f64(t) for t in (x, G, c, mean, inv))
+    Ga = (G * inv).abs()
+    return (x.shape[1] + NL_Y_EXTRA) * NL_U * (x.abs() @ Ga.T + Ga @ mean.abs() + c.abs())
+
+
+def nl_backward_bounds(x, dy, G, mean, inv):
+    """{'dG' | 'dc' | 'Gi' | 'k0' | 'k1': (reference, bound)}: dc and the raw moment with N_H = nl_n_h(V) terms,
+      dc: N_H u sum_v |dy_vm|;   dG: inv_n N_H u (sum_v |dy_vm x_vn| + |mean_n| sum_v |dy_vm|)
+    (the raw moment dy^T x is centred only afterwards: sum_v |dy x| stands where a centred sum would have sum_v |dy (x - mean)|
+    -- the conditioning term of this pass), and the finish kernel's 32-term sums over them:
+      u: sum_m |G| b_dc + 34 u sum_m |G sdy|;  w: sum_m |G| b_dG + 34 u sum_m |G dG|
+      k1: inv^2 b_w / V + 4 u |k1|;  k0: inv b_u / V + |mean| b_k1 + 4 u (|inv u / V| + |mean k1|);  Gi: u |Gi|"""
+    x, dy, G, mean, inv = (_f64(t) for t in (x, dy, G, mean, inv))
+    V = x.shape[0]
+    dG, dc, Gi, k0, k1 = nl_backward_f64(x, dy, G, mean, inv)
+    nh = nl_n_h(V) * NL_U
+    sa = dy.abs().sum(dim=0)
+    b_dc = nh * sa
+    b_dG = inv * nh * (dy.abs().T @ x.abs() + sa[:, None] * mean.abs())
+    ft = NL_FINISH_TERMS * NL_U
+    b_u = G.abs().T @ b_dc + ft * (G.abs().T @ dc.abs())
+    b_w = (G.abs() * b_dG).sum(dim=0) + ft * (G * dG).abs().sum(dim=0)
+    b_k1 = inv * inv * b_w / V + 4 * NL_U * k1.abs()
+    b_k0 = inv * b_u / V + mean.abs() * b_k1 + 4 * NL_U * ((inv * (G.T @ dc) / V).abs() + (mean * k1).abs())
+    return {"dG": (dG, b_dG), "dc": (dc, b_dc), "Gi": (Gi, NL_U * Gi.abs()), "k0": (k0, b_k0), "k1": (k1, b_k1)}
+
+
+def nl_dx_bound(x, dy, Gi, k0, k1):
+    """36 u (|k0| + |x k1| + sum_m |dy_vm Gi_mn|)  [V,d]."""
+    x, dy, Gi, k0, k1 = (_f64(t) for t in (x, dy, Gi, k0, k1))
+    return NL_DX_TERMS * NL_U * (k0.abs() + x.abs() * k1.abs() + dy.abs() @ Gi.abs())
+
+
+def nl_forward_figures(x, G, c, eps, y, mean, var, inv, n_s):
+    """[(name, |got - ref| / bound)] of one forward launch's four outputs (fp32 tensors on any device)."""
+    sb = nl_stats_bounds(x, eps, n_s)
+    out = [(n, nl_excess(t, *sb[n])) for n, t in (("mean", mean), ("var", var), ("inv", inv))]
+    y64 = nl_forward_f64(_f64(x), _f64(G), _f64(c), _f64(mean), _f64(inv))
+    return out + [("y", nl_excess(y, y64, nl_y_bound(x, G, c, mean, inv)))]
+
+
+def nl_backward_figures(x, dy, G, mean, inv, dG, dc, coef):
+    """[(name, excess)] of dG, dc and, with a coefficient block [34,80], of Gi / k0 / k1."""
+    bb = nl_backward_bounds(x, dy, G, mean, inv)
+    d = x.shape[1]
+    out = [("dG", nl_excess(dG, *bb["dG"])), ("dc", nl_excess(dc, *bb["dc"]))]
+    if coef is not None:
+        out += [("Gi", nl_excess(coef[:NL_OUT, :d], *bb["Gi"])), ("k0", nl_excess(coef[NL_OUT, :d], *bb["k0"])),
+                ("k1", nl_excess(coef[NL_OUT + 1, :d], *bb["k1"]))]
+    return out
+
+
+def nl_dx_figures(x, dy, coef, dx, rows=()):
+    """[('dx', excess over all elements)] + [('dx row r', excess of that row)]: the block's values taken as exact."""
+    d = x.shape[1]
+    Gi, k0, k1 = coef[:NL_OUT, :d], coef[NL_OUT, :d], coef[NL_OUT + 1, :d]
+    ref, b = nl_dx_f64(_f64(x), _f64(dy), _f64(Gi), _f64(k0), _f64(k1)), nl_dx_bound(x, dy, Gi, k0, k1)
+    return [("dx", nl_excess(dx, ref, b))] + [(f"dx row {r}", nl_excess(dx[r], ref[r], b[r])) for r in rows]
+
+
+NL_FAULTS = ("stats_drop_last_row", "pad_column_read", "k1_without_inv2", "dG_without_sdy_mean", "fold_bwd_ignores_at",
+             "unbias_n_over_n")
+
+
+def nl_restated_f32(x, G, c, dy, eps, fault=None, pad=None, col_stats=None, lanes="fp32"):
+    """csrc/normlinear.hip's three launches in plain fp32 torch on the CPU, the same formulas in torch's own summation
+    order: shifted sums per 2048-row slab combined in float64 (or the caller's col_stats), Gs = G inv and the folded bias
+    c - Gs mean, the raw moment dy^T x centred afterwards, the finish algebra, dx = (k0 + x k1) + dy Gi.
+    lanes: "fp32" -- the slab sums formed in fp32 (bound: nl_n_s(d) terms); "fp64" -- as nl_stats_partial_kernel forms them:
+    difference, square and sums in float64, a slab's two sums rounded to fp32 once (bound: NL_STAT_COMBINE).
+    -> dict(mean, var, inv, y, dG, dc, coef [34,80] (pads 0), dx).  pad: [V] fp32, the column behind x's last one in memory
+    (only the fault reads it).  fault: one of NL_FAULTS[:4], a deliberate error --
+      stats_drop_last_row   the statistics sums stop one row early (still divided by V)
+      pad_column_read       the forward contraction runs over d + 1 columns: x's pad times the weight of column 0
+      k1_without_inv2       k1 = -w / V
+      dG_without_sdy_mean   dG = Hraw inv"""
+    assert fault is None or fault in NL_FAULTS[:4], fault
+    x, G, c, dy = (t.detach().float().cpu() for t in (x, G, c, dy))
+    V, d = x.shape
+    if col_stats is None:
+        assert lanes in ("fp32", "fp64"), lanes
+        t = x - x[0] if lanes == "fp32" else x.double() - x[0].double()
+        if fault == "stats_drop_last_row":
+            t = t[:V - 1]
+        parts = [torch.stack((s.sum(dim=0), (s * s).sum(dim=0))) for s in t.split(NL_SLAB)]
+        st = torch.stack(parts).float().double().sum(dim=0) if parts else torch.zeros(2, d, dtype=torch.float64)
+    else:
+        st = col_stats.double().sum(dim=0)[:, :d]
+    m = st[0] / V
+    v = (st[1] / V - m * m).clamp_min(0)
+    mean, var = (x[0].double() + m).float(), v.float()
+    inv = 1.0 / torch.sqrt(var + torch.tensor(eps, dtype=torch.float32))
+    Gs = G * inv
+    cb = c - (Gs * mean).sum(dim=1)
+    y = x @ Gs.T + cb
+    if fault == "pad_column_read":
+        y = y + pad.float()[:, None] * Gs[:, 0]
+    sdy = dy.sum(dim=0)
+    h = dy.T @ x
+    dG = (h if fault == "dG_without_sdy_mean" else h - sdy[:, None] * mean) * inv
+    u, w = (G * sdy[:, None]).sum(dim=0), (G * dG).sum(dim=0)
+    k1 = -w / V if fault == "k1_without_inv2" else -(inv * inv) * w / V
+    k0 = -inv * u / V - mean * k1
+    coef = torch.zeros(NL_OUT + 2, NL_DP)
+    coef[:NL_OUT, :d], coef[NL_OUT, :d], coef[NL_OUT + 1, :d] = Gs, k0, k1
+    return dict(mean=mean, var=var, inv=inv, y=y, dG=dG, dc=sdy, coef=coef, dx=(k0 + x * k1) + dy @ Gs)
+
+
+# ---- the parameter fold
+# (name, d, widths, cols, col_at kind): L = 1; 4 pairs on the whole input; 4 blocks side by side; 3 blocks under a column map
+NL_FOLD_CASES = (("L1_w80", 80, (80,), (0,), None), ("L4_shared71", 71, (71,) * 4, (0,) * 4, None),
+                 ("L4_blocks", 60, (1, 30, 15, 14), (0, 1, 31, 46), None),
+                 ("L3_planes", 60, (30, 15, 15), (0, 30, 45), "planes"), ("L3_random", 60, (30, 15, 15), (0, 30, 45), "random"))
+
+
+def nl_fold_col_at(kind, d=60, r=5):
+    """None, the interleaving FeaturePlanes._sample_all gives two same-size grids sampled as one (r channels: grid 0's plane q
+    at 3 r q .., grid 1's behind it) followed by the identity, or a seeded random permutation."""
+    if kind is None:
+        return None
+    if kind == "random":
+        return [int(v) for v in torch.randperm(d, generator=torch.Generator().manual_seed(d))]
+    at = [(j // (2 * r)) * 3 * r + j % (2 * r) for j in range(6 * r)] + [q * 3 * r + 2 * r + k for q in range(3) for k in range(r)]
+    return at + list(range(len(at), d))
+
+
+def nl_fold_inputs(name):
+    """fp32 CPU inputs of one fold case: dict(d, widths, cols, col_at, W, b, gamma, beta, dG, dc, run_mean, run_var,
+    momentum, mean, var)."""
+    _, d, widths, cols, kind = NL_FOLD_CASES[[c[0] for c in NL_FOLD_CASES].index(name)]
+    g = torch.Generator().manual_seed(len(name) * 1000 + d)
+    r = lambda *s: torch.randn(*s, generator=g)
+    return dict(d=d, widths=widths, cols=cols, col_at=nl_fold_col_at(kind, d),
+                W=[r(NL_OUT, w) * 0.3 for w in widths], b=[r(NL_OUT) for _ in widths], gamma=[1 + 0.2 * r(w) for w in widths],
+                beta=[0.3 * r(w) for w in widths], dG=r(NL_OUT, d), dc=r(NL_OUT), run_mean=[r(w) for w in widths],
+                run_var=[r(w).abs() + 0.5 for w in widths], momentum=[0.1, 0.25, 0.5, 1.0][:len(widths)], mean=r(d),
+                var=r(d).abs() + 0.1)
+
+
+def nl_fold_bounds(p):
+    """(G, c) bounds: (L + 2) u sum_i |W gamma| per element of G (placed by col_at); (sum_i d_i + L) u (sum |W beta| + |b|)."""
+    W, ga, be, b = ([_f64(t).abs() for t in p[k]] for k in ("W", "gamma", "beta", "b"))
+    L = len(W)
+    bG, bc = nl_fold_f64(W, b, ga, be, p["widths"], p["cols"], p["d"], p["col_at"])
+    return (L + 2) * NL_U * bG, (sum(p["widths"]) + L) * NL_U * bc
+
+
+def nl_fold_backward_bounds(p):
+    """[(b dW, b db = 0, b dgamma, b dbeta)] per pair: 3 u (|dG gamma| + |dc beta|); 34-term column sums."""
+    a = lambda k: [_f64(t).abs() for t in p[k]]
+    terms = nl_fold_backward_f64(_f64(p["dG"]).abs(), _f64(p["dc"]).abs(), a("W"), a("gamma"), a("beta"), p["widths"], p["cols"],
+                                 p["col_at"])
+    ft = NL_FINISH_TERMS * NL_U
+    return [(3 * NL_U * t[0], 0 * t[1], ft * t[2], ft * t[3]) for t in terms]
+
+
+def nl_running_bounds(p, n):
+    """6 u ((1 - m) |old| + m |new|) per element: 1 - m, two products, the sum, the unbias factor and its rounding."""
+    a = lambda k: [_f64(t).abs() for t in p[k]]
+    terms = nl_running_f64(a("run_mean"), a("run_var"), p["momentum"], _f64(p["mean"]).abs(), _f64(p["var"]).abs(), n,
+                           p["widths"], p["cols"], p["col_at"])
+    return [(6 * NL_U * t[0], 6 * NL_U * t[1]) for t in terms]
+
+
+# ---- the cases of tests/test_gpu_f64_parity.py (shapes alone; tests/test_f64_refs_host.py asserts what each reaches)
+NL_ROW_DL = ((60, 60), (71, 72))
+NL_ROW_V = (1, 2, 15, 16, 17, 63, 64, 65, 129, 448, 512, 513, 1025)
+NL_COL_V, NL_COL_D = 193, (1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 71, 79, 80)
+NL_GRAD_D, NL_GRAD_LDDY, NL_GRAD_X = (17, 60, 71), (32, 36, 64), ("padded", "off1")
+NL_STRIDE_CASES = ((70_001, 60, 60), (140_001, 60, 60), (140_001, 71, 72))
+NL_SLAB_DL = ((7, 7), (71, 72))
+NL_SLAB_V = (2047, 2048, 2049, 2048 + 15, 2048 + 16, 2048 + 17, 2048 + 31, 2048 + 32, 2048 + 33, 8 * 2048 + 1)
+NL_SLAB_CASES = tuple((V, d, ld) for d, ld in NL_SLAB_DL for V in NL_SLAB_V) + ((64 * 2048 + 1, 7, 7),)
+NL_COLSTAT_V, NL_COLSTAT_ROWS = 4099, (1, 7, 8, 9, 56, 57, 58, 64, 65, 121, 2048)
+NL_EPS = (1e-5, 1e-3)
+
+
+def nl_lddx(d):
+    return (d, _up4(d), _up4(d) + 4)

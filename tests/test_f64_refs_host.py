@@ -534,3 +534,246 @@ def test_a_wrong_gather_restatement_misses_the_bounds_on_the_cases_chosen_for_it
                 print(f"{fault:15s} {case:10s} {name:14s} {e:.3g} x bound")
     assert missed == GATHER_FAULT_SEEN_BY[fault], (sorted(missed - GATHER_FAULT_SEEN_BY[fault]),
                                                    sorted(GATHER_FAULT_SEEN_BY[fault] - missed))
+
+
+# ---------------------------------------------------------------------------------------------------------- norm-linear
+def _bn_linear_chain(xs, bns, linears):
+    return sum(lin(bn(x)) for x, bn, lin in zip(xs, bns, linears))
+
+
+def test_norm_linear_references_are_the_module_chain_and_pass_gradcheck():
+    """At float64 statistics nl_forward_f64 / nl_backward_f64 / nl_dx_f64 are BatchNorm1d(affine=False, training) -> Linear
+    and its autograd to 1e-12; nl_fold_f64 (+ the forward on the column-mapped input) is the chain of modules FeaturePlanes
+    sums, with and without col_at; the backward algebra passes gradcheck."""
+    torch.manual_seed(3)
+    V, d, eps = 257, 23, 1e-5
+    inp = R.nl_inputs(V, d)
+    x, G, c, dy = (inp[k].double() for k in ("x", "G", "c", "dy"))
+    bn, lin = torch.nn.BatchNorm1d(d, eps=eps, affine=False).double().train(), torch.nn.Linear(d, 32).double()
+    with torch.no_grad():
+        lin.weight.copy_(G)
+        lin.bias.copy_(c)
+    xa = x.clone().requires_grad_()
+    ya = lin(bn(xa))
+    (ya * dy).sum().backward()
+    mean, var = R.nl_stats_f64(x)
+    inv = 1.0 / torch.sqrt(var + eps)
+    dG, dc, Gi, k0, k1 = R.nl_backward_f64(x, dy, G, mean, inv)
+    rel = lambda a, b: float((a - b).abs().max() / b.abs().max())
+    figures = {"y": rel(R.nl_forward_f64(x, G, c, mean, inv), ya.detach()), "dx": rel(R.nl_dx_f64(x, dy, Gi, k0, k1), xa.grad),
+               "dG": rel(dG, lin.weight.grad), "dc": rel(dc, lin.bias.grad)}
+    print(figures)
+    assert max(figures.values()) <= 1e-12
+
+    class Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x_, G_, c_):
+            m, v = R.nl_stats_f64(x_)
+            iv = 1.0 / torch.sqrt(v + eps)
+            ctx.save_for_backward(x_, G_, m, iv)
+            return R.nl_forward_f64(x_, G_, c_, m, iv)
+
+        @staticmethod
+        def backward(ctx, dy_):
+            x_, G_, m, iv = ctx.saved_tensors
+            dG_, dc_, Gi_, k0_, k1_ = R.nl_backward_f64(x_, dy_, G_, m, iv)
+            return R.nl_dx_f64(x_, dy_, Gi_, k0_, k1_), dG_, dc_
+    small = [t.clone().requires_grad_() for t in (x[:9, :5], G[:, :5], c)]
+    assert torch.autograd.gradcheck(Fn.apply, small, eps=1e-6, atol=1e-7)
+
+    for name, _, widths, cols, _ in R.NL_FOLD_CASES:
+        p = R.nl_fold_inputs(name)
+        dd, at = p["d"], p["col_at"]
+        bns = [torch.nn.BatchNorm1d(w, eps=eps).double().train() for w in widths]
+        lins = [torch.nn.Linear(w, 32).double() for w in widths]
+        with torch.no_grad():
+            for i in range(len(widths)):
+                bns[i].weight.copy_(p["gamma"][i]); bns[i].bias.copy_(p["beta"][i])
+                lins[i].weight.copy_(p["W"][i]); lins[i].bias.copy_(p["b"][i])
+        xr = torch.randn(64, dd, dtype=torch.float64)                   # the reference's column order
+        want = _bn_linear_chain([xr[:, c0:c0 + w] for c0, w in zip(cols, widths)], bns, lins).detach()
+        xk = xr if at is None else torch.zeros_like(xr).index_copy(1, torch.as_tensor(at), xr)   # column j kept at col_at[j]
+        f = lambda k: [t.double() for t in p[k]]
+        G_, c_ = R.nl_fold_f64(f("W"), f("b"), f("gamma"), f("beta"), widths, cols, dd, at)
+        m, v = R.nl_stats_f64(xk)
+        e = rel(R.nl_forward_f64(xk, G_, c_, m, 1.0 / torch.sqrt(v + eps)), want)
+        print(f"fold {name}: {e:.2e}")
+        assert e <= 1e-12
+        # the fold's backward is the autograd of the fold
+        leaves = [[t.clone().requires_grad_() for t in f(k)] for k in ("W", "b", "gamma", "beta")]
+        Ga, ca = R.nl_fold_f64(*leaves, widths, cols, dd, at)
+        ((Ga * p["dG"].double()).sum() + (ca * p["dc"].double()).sum()).backward()
+        got = R.nl_fold_backward_f64(p["dG"].double(), p["dc"].double(), f("W"), f("gamma"), f("beta"), widths, cols, at)
+        for i, (dW, db, dga, dbe) in enumerate(got):
+            for a, b_ in ((dW, leaves[0][i].grad), (db, leaves[1][i].grad), (dga, leaves[2][i].grad), (dbe, leaves[3][i].grad)):
+                assert float((a - b_).abs().max()) <= 1e-12 * max(1.0, float(b_.abs().max()))
+        # running statistics: nn.BatchNorm1d's own update (identity column map; the modules saw xr's blocks)
+        if at is None:
+            n = xr.shape[0]
+            m_, v_ = R.nl_stats_f64(xr)
+            old = [(torch.zeros(w, dtype=torch.float64), torch.ones(w, dtype=torch.float64)) for w in widths]
+            upd = R.nl_running_f64([o[0] for o in old], [o[1] for o in old], [0.1] * len(widths), m_, v_, n, widths, cols)
+            for bn_, (rm, rv) in zip(bns, upd):
+                assert float((bn_.running_mean - rm).abs().max()) <= 1e-12 and float((bn_.running_var - rv).abs().max()) <= 1e-12
+
+
+def _nl_host_cases():
+    """(name, inputs, eps, col_stats rows): every GPU case with V <= 4099 (x's layout changes no arithmetic)."""
+    out = [(f"rows V={V} d={d}", R.nl_inputs(V, d), 1e-5, 0) for d, _ in R.NL_ROW_DL for V in R.NL_ROW_V]
+    out += [(f"cols d={d}", R.nl_inputs(R.NL_COL_V, d), 1e-5, 0) for d in R.NL_COL_D]
+    out += [(f"grads d={d}", R.nl_inputs(R.NL_COL_V, d, seed=1), 1e-5, 0) for d in R.NL_GRAD_D]
+    out += [(f"slabs V={V} d={d}", R.nl_inputs(V, d), 1e-5, 0) for V, d, _ in R.NL_SLAB_CASES if V <= 4099]
+    out += [(f"cstats rows={r}", R.nl_inputs(R.NL_COLSTAT_V, 71), 1e-5, r) for r in R.NL_COLSTAT_ROWS]
+    x = R.nl_regime_matrix()
+    g = torch.Generator().manual_seed(8)
+    reg = dict(V=x.shape[0], d=8, x=x, G=torch.randn(32, 8, generator=g), c=torch.randn(32, generator=g),
+               dy=torch.randn(x.shape[0], 32, generator=g))
+    out += [(f"regime eps={eps:g} {'col_stats' if r else 'builtin'}", reg, eps, r) for eps in R.NL_EPS for r in (0, 9)]
+    return out
+
+
+def _nl_restated_figures(inp, eps, rows, fault=None, lanes="fp32"):
+    """{name: |got - ref| / bound} of f64_refs.nl_restated_f32 on one case, each launch against float64 on its own inputs.
+    lanes = "fp64": the slab sums as the kernel forms them, judged at the kernel's NL_STAT_COMBINE roundings."""
+    x, d = inp["x"], inp["d"]
+    stats = R.nl_col_stats(x, rows) if rows else None
+    pad = torch.full((inp["V"],), float("nan"))
+    o = R.nl_restated_f32(x, inp["G"], inp["c"], inp["dy"], eps, fault=fault, pad=pad, col_stats=stats, lanes=lanes)
+    n_s = R.NL_STAT_COMBINE if rows or lanes == "fp64" else R.nl_n_s(d)
+    fig = dict(R.nl_forward_figures(x, inp["G"], inp["c"], eps, o["y"], o["mean"], o["var"], o["inv"], n_s))
+    fig.update(R.nl_backward_figures(x, inp["dy"], inp["G"], o["mean"], o["inv"], o["dG"], o["dc"], o["coef"]))
+    fig.update(R.nl_dx_figures(x, inp["dy"], o["coef"], o["dx"]))
+    return fig
+
+
+@functools.lru_cache(maxsize=None)
+def _nl_all_restated():
+    """Every host case with fp32 slab sums; the built-in statistics cases again with the kernel's fp64 lanes."""
+    cases = _nl_host_cases()
+    return ([(name, _nl_restated_figures(inp, eps, rows)) for name, inp, eps, rows in cases]
+            + [(name + " fp64 lanes", _nl_restated_figures(inp, eps, rows, lanes="fp64")) for name, inp, eps, rows in cases if not rows])
+
+
+def test_correct_fp32_norm_linear_arithmetic_meets_the_a_priori_bounds():
+    """The condition under which the norm-linear tests of test_gpu_f64_parity may ask what they ask: the three launches in
+    plain fp32 torch (f64_refs.nl_restated_f32: the kernels' formulas, torch's summation order) are inside every bound on
+    every case with V <= 4099.  The statistics are judged twice: slab sums formed in fp32 against the 516- / 1026-term bound
+    of such a lane (nl_n_s), and slab sums formed in float64 and rounded to fp32 once -- what nl_stats_partial_kernel does and
+    what a caller's col_stats are -- against the NL_STAT_COMBINE = 2 roundings the GPU tests hold the kernel to.  The worst
+    ratio per bound is printed."""
+    worst = {}
+    for name, fig in _nl_all_restated():
+        for k, e in fig.items():
+            if e > worst.get(k, (-1.0, ""))[0]:
+                worst[k] = (e, name)
+    for k, (e, name) in worst.items():
+        print(f"norm-linear {k:5s} worst |got - ref| / bound {e:.3f}  ({name})")
+    assert all(e <= 1 for e, _ in worst.values()), worst
+
+
+def test_constant_and_single_row_columns_are_exact_in_the_restatement():
+    """What the regime test asks of the kernel holds for the formulas: a constant column has var == 0 and mean == the
+    constant, a one-row matrix var == 0 and mean == x[0], bit for bit."""
+    x = R.nl_regime_matrix()
+    z = torch.zeros(32, 8)
+    o = R.nl_restated_f32(x, z, z[:, 0], torch.zeros(x.shape[0], 32), 1e-5)
+    k = R.NL_REGIME_COLUMNS.index("constant")
+    assert float(o["var"][k]) == 0.0 and float(o["mean"][k]) == 3.25
+    inp = R.nl_inputs(1, 60)
+    o = R.nl_restated_f32(inp["x"], inp["G"], inp["c"], inp["dy"], 1e-5)
+    assert bool((o["var"] == 0).all()) and torch.equal(o["mean"], inp["x"][0])
+
+
+# fault -> (the case named for it, the figure that must leave its bound there).  The last two are faults of the parameter
+# fold: test_fp32_fold_arithmetic_meets_its_bounds_and_two_wrong_folds_do_not runs them on every fold case and asserts from
+# this table which see them (the cases of NL_FOLD_CASES; the row counts n of the running-statistics update)
+NL_FAULT_SEEN_BY = {
+    "stats_drop_last_row": ("regime eps=1e-05 builtin", "mean"),         # the last-row-only column: mean == 0
+    "pad_column_read": ("cols d=71", "y"),
+    "k1_without_inv2": ("grads d=60", "k1"),                              # inv = 3.3 in the log-scaling columns
+    "dG_without_sdy_mean": ("grads d=60", "dG"),                          # mean = -5 there
+    "fold_bwd_ignores_at": ({"L3_planes", "L3_random"}, "fold backward"),  # the cases with a column map, and no other
+    "unbias_n_over_n": ({1: False, 2: True}, "running statistics"),      # n / (n - 1) = 2 at n = 2; n = 1 has no factor
+}
+assert set(NL_FAULT_SEEN_BY) == set(R.NL_FAULTS)
+
+
+@pytest.mark.parametrize("fault", R.NL_FAULTS[:4])
+def test_a_wrong_norm_linear_restatement_misses_the_bounds_on_the_case_named_for_it(fault):
+    case, figure = NL_FAULT_SEEN_BY[fault]
+    name, inp, eps, rows = next(c for c in _nl_host_cases() if c[0] == case)
+    good, bad = _nl_restated_figures(inp, eps, rows), _nl_restated_figures(inp, eps, rows, fault=fault)
+    print(f"{fault}: {case}: {figure} {good[figure]:.3f} -> {bad[figure]:.3g} x bound")
+    assert good[figure] <= 1 < bad[figure]
+
+
+def test_fp32_fold_arithmetic_meets_its_bounds_and_two_wrong_folds_do_not():
+    """The fold launches in plain fp32 torch are inside the bounds of test_norm_fold_kernels_against_float64 on every case;
+    a backward that reads dG as it lies (col_at not applied) leaves them on the two cases with a column map and on no
+    other; running statistics with n / n in place of n / (n - 1) leave them at n = 2 and not at n = 1."""
+    for name, *_ in R.NL_FOLD_CASES:
+        p = R.nl_fold_inputs(name)
+        w, cols, at = p["widths"], p["cols"], p["col_at"]
+        f64 = lambda k: [t.double() for t in p[k]]
+        G32, c32 = R.nl_fold_f64(p["W"], p["b"], p["gamma"], p["beta"], w, cols, p["d"], at)
+        G64, c64 = R.nl_fold_f64(f64("W"), f64("b"), f64("gamma"), f64("beta"), w, cols, p["d"], at)
+        bG, bc = R.nl_fold_bounds(p)
+        eG, ec = R.nl_excess(G32, G64, bG), R.nl_excess(c32, c64, bc)
+        ref = R.nl_fold_backward_f64(p["dG"].double(), p["dc"].double(), f64("W"), f64("gamma"), f64("beta"), w, cols, at)
+        bnd = R.nl_fold_backward_bounds(p)
+        worst = {}
+        for apply_at in (True, False):
+            got = R.nl_fold_backward_f64(p["dG"], p["dc"], p["W"], p["gamma"], p["beta"], w, cols, at, apply_at=apply_at)
+            worst[apply_at] = max(R.nl_excess(a, r, b) for g4, r4, b4 in zip(got, ref, bnd) for a, r, b in zip(g4, r4, b4))
+        print(f"fold {name:12s} G {eG:.3f} c {ec:.3f} backward {worst[True]:.3f}; col_at ignored: {worst[False]:.3g}")
+        assert eG <= 1 and ec <= 1 and worst[True] <= 1
+        assert (worst[False] > 1) == (name in NL_FAULT_SEEN_BY["fold_bwd_ignores_at"][0]) == (at is not None)
+        for n in (1, 2):
+            want = R.nl_running_f64(f64("run_mean"), f64("run_var"), p["momentum"], p["mean"].double(), p["var"].double(), n, w, cols, at)
+            bd = R.nl_running_bounds(p, n)
+            for unbiased in (True, False):
+                got = R.nl_running_f64(p["run_mean"], p["run_var"], [torch.tensor(m) for m in p["momentum"]], p["mean"], p["var"], n,
+                                       w, cols, at, unbiased=unbiased)
+                e = max(max(R.nl_excess(g[0], r[0], b[0]), R.nl_excess(g[1], r[1], b[1])) for g, r, b in zip(got, want, bd))
+                print(f"fold {name:12s} running n={n} unbiased={unbiased}: {e:.3g}")
+                assert (e > 1) == (not unbiased and NL_FAULT_SEEN_BY["unbias_n_over_n"][0][n])
+
+
+def test_norm_linear_cases_reach_every_instantiation_and_loop_form():
+    """From the shapes alone (f64_refs.nl_case_facts): the column-edge cases reach Q = NT = 1 .. 5 of the forward, reduce and dx
+    kernels with aligned and unaligned rows and both statistics kernels; the gradient-layout cases leave the aligned dx kernel
+    from x's side and from dx's side; the row, slab and col_stats cases give the partial counts and loop forms named below."""
+    ld_off = lambda d, layout: R.nl_layout(torch.zeros(2, d), layout)[2:]
+    cols = {(d, l): R.nl_case_facts(R.NL_COL_V, d, *ld_off(d, l), lddx=R.nl_lddx(d)[1]) for d in R.NL_COL_D for l in R.NL_LAYOUTS}
+    assert {(f["Q"], f["aligned"]) for f in cols.values()} == {(q, a) for q in range(1, 6) for a in (True, False)}
+    assert {(f["Q"], f["aligned_dx"]) for f in cols.values()} == {(q, a) for q in range(1, 6) for a in (True, False)}
+    assert all(cols[(d, l)]["aligned"] == (l in ("padded", "block") or (l == "packed" and d % 4 == 0) or (l == "odd" and d % 4 == 1))
+               for d in R.NL_COL_D for l in R.NL_LAYOUTS)
+    for a, b in ((16, 17), (32, 33), (48, 49), (64, 65)):
+        assert cols[(a, "padded")]["Q"] + 1 == cols[(b, "padded")]["Q"]
+    assert cols[(64, "padded")]["CW"] == 64 and cols[(65, "padded")]["CW"] == 128
+    grads = {(d, k, xl): R.nl_case_facts(R.NL_COL_V, d, *ld_off(d, xl), lddx=R.nl_lddx(d)[k])
+             for d in R.NL_GRAD_D for k in range(3) for xl in R.NL_GRAD_X}
+    for d in R.NL_GRAD_D:
+        assert [grads[(d, k, "padded")]["aligned_dx"] for k in range(3)] == [d % 4 == 0, True, True]
+        assert not any(grads[(d, k, "off1")]["aligned_dx"] for k in range(3)) and not grads[(d, 1, "off1")]["aligned"]
+    assert [R.nl_partials(V) for V in (448, 512, 513)] == [7, 8, 9]
+    strides = [R.nl_case_facts(V, d, ld) for V, d, ld in R.NL_STRIDE_CASES]
+    assert [f["partials"] for f in strides] == [1024] * 3 and -(-70_001 // 64) > 1024
+    assert [f["strides"] for f in strides] == [1, 2, 2]
+    slabs = {(V, d): R.nl_case_facts(V, d, ld) for V, d, ld in R.NL_SLAB_CASES}
+    assert [slabs[(V, 7)]["slabs"] for V in (2047, 2048, 2049, 8 * 2048 + 1, 64 * 2048 + 1)] == [1, 1, 2, 9, 65]
+    assert slabs[(8 * 2048 + 1, 71)]["finish"] == {"tail"} and slabs[(64 * 2048 + 1, 7)]["finish"] == {"unrolled", "tail"}
+    # the row loop of the statistics kernel on the last slab: a row group unrolls once it owns 8 rows -- all 4 groups (d = 7) at
+    # 32 rows and the first of them at 29, both groups (d = 71) at 16 and the first at 15
+    want7 = {2047: {"unrolled", "tail"}, 2048: {"unrolled"}, 2049: {"tail"}, 2063: {"tail"}, 2064: {"tail"}, 2065: {"tail"},
+             2079: {"unrolled", "tail"}, 2080: {"unrolled"}, 2081: {"unrolled", "tail"}}
+    want71 = {2047: {"unrolled", "tail"}, 2048: {"unrolled"}, 2049: {"tail"}, 2063: {"unrolled", "tail"}, 2064: {"unrolled"},
+              2065: {"unrolled", "tail"}, 2079: {"unrolled", "tail"}, 2080: {"unrolled"}, 2081: {"unrolled", "tail"}}
+    assert {V: slabs[(V, 7)]["slab_tail"] for V in want7} == want7
+    assert {V: slabs[(V, 71)]["slab_tail"] for V in want71} == want71
+    # (an fp32 lane's chain: the restatement's bound; the kernel's lanes sum in fp64 and answer to NL_STAT_COMBINE)
+    fin = {r: R.nl_case_facts(R.NL_COLSTAT_V, 71, 72, stat_rows=r)["finish"] for r in R.NL_COLSTAT_ROWS}
+    assert fin[8] == fin[9] == fin[56] == {"tail"} and fin[57] == fin[58] == fin[64] == {"unrolled"}
+    assert fin[65] == {"unrolled", "tail"} and fin[2048] == fin[121] == {"unrolled"}       # (lane-group 0's view: partials 0, 8, .., 120)
+    assert R.nl_n_s(7) == 516 and R.nl_n_s(71) == 1026

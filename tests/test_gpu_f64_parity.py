@@ -1,5 +1,5 @@
-"""csrc/mlp_heads.hip, csrc/attention.hip, csrc/expand.hip and csrc/ssim.hip against float64, at the edges of their launch
-shapes.
+"""csrc/mlp_heads.hip, csrc/attention.hip, csrc/expand.hip, csrc/ssim.hip, csrc/anchor_gather.hip and csrc/normlinear.hip
+against float64, at the edges of their launch shapes.
 
 Every case runs, on the same packed fp32 inputs (drawn on the CPU, tests/f64_refs.py):
   the kernel, through the product wrapper (mlp_heads.mlp_heads, plane_attention.attended_pair_planes,
@@ -13,7 +13,8 @@ constants of test_fused_norm_linear_matches_batchnorm_linear_chain).  Every figu
 asserted (and appended to the file $SPLATCO_F64_PARITY_LOG names, if set); profiles/r08_f64_parity.txt is one such run,
 profiles/r13_loss_f64_parity.txt one of the image losses (l1_ssim, scaling_reg, pair_l1), profiles/r22_gather_f64_parity.txt
 one of csrc/anchor_gather.hip at its C ABI (the end of this file) and of the heads and the expansion reading feat /
-offsets in place from the gather's [V,72] matrix (layout `gather` of their tests).
+offsets in place from the gather's [V,72] matrix (layout `gather` of their tests), profiles/r23_norm_linear_f64_parity.txt one of
+csrc/normlinear.hip at its C ABI (the last section: every element against an a-priori bound, no chain).
 """
 import copy
 import functools
@@ -736,4 +737,276 @@ def test_gather_wrappers_against_float64(N, monkeypatch):
     for name, a_, b_, c_ in zip(("d anchor_feat", "d anchor", "d offset", "d scaling", "d G", "d c"), runs[0], chain, ref):
         rep.add(name, a_, b_, c_, rows=not name.endswith((" G", " c")))
     rep.require(_same_bits(*runs), "bit-reproducible")
+    rep.finish()
+
+
+# ---------------------------------------------------------------------------------------------------------- norm-linear
+# csrc/normlinear.hip at its own C ABI (include/splatco_raster.h: scr_norm_linear_forward / _backward / _dx, scr_norm_fold*),
+# on the shapes of f64_refs.NL_*: what each reaches (template instantiation, loop form, slabs, partials, grid rounds) is
+# asserted from the shapes alone in tests/test_f64_refs_host.py, which also shows that plain fp32 arithmetic meets every
+# bound used here and six wrong kernels do not.  (The statistics are held to 2 fp32 roundings per slab sum: the kernel's
+# lanes sum in fp64.  The host restatement meets that bound with its slab sums formed in float64 and rounded once, and on the
+# col_stats cases; with fp32 slab sums it is held to the 516- / 1026-term bound of such a lane instead.)  Every figure is |got - ref| / bound, the bound a-priori and per element
+# (f64_refs.nl_*_bounds): at most 1.  profiles/r23_norm_linear_f64_parity.txt is one run of this section.
+NL_SENTINEL = 0x7FC12345                                    # a quiet NaN with a payload: shows in a value, and its bits are checked
+
+
+def _sent(*shape):
+    return torch.full(shape, NL_SENTINEL, dtype=torch.int32, device=DEV).view(torch.float32)
+
+
+def _kept(t, used=None):
+    """Whether every element of t outside the boolean mask `used` (None: all of t) still holds the sentinel's bits."""
+    bits = t.view(torch.int32)
+    return bool((bits == NL_SENTINEL).all()) if used is None else bool((bits[~used] == NL_SENTINEL).all())
+
+
+def _nl_forward(xv, ld, G, c, eps, stats=None):
+    """scr_norm_linear_forward into sentinel-filled buffers: y [V + 1, 32] (one row to spare), mean / var / inv [80]."""
+    from splatco_amd import _C
+    V, d = xv.shape
+    y, mean, var, inv = _sent(V + 1, 32), _sent(R.NL_DP), _sent(R.NL_DP), _sent(R.NL_DP)
+    scratch = _C.scratch(_C.lib.scr_norm_linear_scratch_bytes(V), DEV)
+    _C.call("scr_norm_linear_forward", V, d, xv.data_ptr(), ld, G, c, float(eps), y, mean, var, inv, scratch,
+            stats, 0 if stats is None else stats.shape[0], device=DEV)
+    return y, mean, var, inv
+
+
+def _nl_backward(xv, ld, dyv, lddy, G, mean, inv, lddx, with_dx, with_coef):
+    """scr_norm_linear_backward into sentinel-filled buffers: dx [V + 1, lddx] or NULL, dG [32 d + 4], dc [36], coef_out
+    [34 x 80 + 4] or NULL."""
+    from splatco_amd import _C
+    V, d = xv.shape
+    dx = _sent(V + 1, lddx) if with_dx else None
+    dG, dc = _sent(32 * d + 4), _sent(36)
+    coef = _sent(34 * R.NL_DP + 4) if with_coef else None
+    scratch = _C.scratch(_C.lib.scr_norm_linear_scratch_bytes(V), DEV)
+    _C.call("scr_norm_linear_backward", V, d, xv.data_ptr(), ld, dyv.data_ptr(), lddy, G, mean, inv, _C.ptr(dx), lddx, dG, dc,
+            scratch, _C.ptr(coef), device=DEV)
+    return dx, dG, dc, coef
+
+
+def _nl_dx(xv, ld, dyv, lddy, coef, lddx):
+    from splatco_amd import _C
+    V, d = xv.shape
+    dx = _sent(V + 1, lddx)
+    _C.call("scr_norm_linear_dx", V, d, xv.data_ptr(), ld, dyv.data_ptr(), lddy, coef, dx, lddx, device=DEV)
+    return dx
+
+
+def _dx_kept(dx, V, d):
+    used = torch.zeros(dx.shape, dtype=torch.bool, device=dx.device)
+    used[:V, :d] = True
+    return _kept(dx, used)
+
+
+def _nl_drive(rep, inp, xlayout="packed", eps=1e-5, lddy=32, lddx=None, stats=None, backward=True, rows=()):
+    """One case through forward, backward with dx (+ coef_out), backward with dx = NULL + coef_out, scr_norm_linear_dx on that
+    block -- each call twice.  Adds every figure to rep; -> the forward's (y, mean, var, inv) on the CPU."""
+    V, d = inp["V"], inp["d"]
+    x, G, c = inp["x"], inp["G"].to(DEV), inp["c"].to(DEV)
+    _leaf, xv, ld, _off = R.nl_layout(x.to(DEV), xlayout)
+    fw = [_nl_forward(xv, ld, G, c, eps, stats) for _ in range(2)]
+    y, mean, var, inv = fw[0]
+    rep.require(_same_bits([t.view(torch.int32) for t in fw[0]], [t.view(torch.int32) for t in fw[1]]), "forward: same bits twice")
+    rep.require(_kept(y[V:]) and all(_kept(t[d:]) for t in (mean, var, inv)), "forward: sentinels kept")
+    yc, mc, vc, ic = y[:V].cpu(), mean[:d].cpu(), var[:d].cpu(), inv[:d].cpu()
+    for name, e in R.nl_forward_figures(x, inp["G"], inp["c"], eps, yc, mc, vc, ic, R.NL_STAT_COMBINE):
+        rep.within(name + " / bound", e, 1.0)
+    if backward:
+        lddx = lddx or R.nl_lddx(d)[1]
+        _dyleaf = torch.full((V, lddy), float("nan"), device=DEV)
+        _dyleaf[:, :32] = inp["dy"].to(DEV)
+        dyv = _dyleaf[:, :32]
+        mean_d, inv_d = mean[:d].clone(), inv[:d].clone()
+        bw = [_nl_backward(xv, ld, dyv, lddy, G, mean_d, inv_d, lddx, True, True) for _ in range(2)]
+        dx, dG, dc, coef = bw[0]
+        rep.require(_same_bits([t.view(torch.int32) for t in bw[0]], [t.view(torch.int32) for t in bw[1]]), "backward: same bits twice")
+        rep.require(_dx_kept(dx, V, d) and _kept(dG[32 * d:]) and _kept(dc[32:]) and _kept(coef[34 * R.NL_DP:]), "backward: sentinels kept")
+        cf = coef[:34 * R.NL_DP].view(34, R.NL_DP).cpu()
+        for name, e in R.nl_backward_figures(x, inp["dy"], inp["G"], mc, ic, dG[:32 * d].view(32, d).cpu(), dc[:32].cpu(), cf):
+            rep.within(name + " / bound", e, 1.0)
+        rep.require(bool((cf[:, d:] == 0).all()), "coef_out pads == 0")
+        for name, e in R.nl_dx_figures(x, inp["dy"], cf, dx[:V, :d].cpu(), rows):
+            rep.within(name + " / bound", e, 1.0)
+        # the split route: no dx here, the coefficients out, pass 3 on its own
+        sp = [_nl_backward(xv, ld, dyv, lddy, G, mean_d, inv_d, lddx, False, True) for _ in range(2)]
+        rep.require(all(torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)) for a in sp for b in (bw[0],) for k in (1, 2, 3)),
+                    "dx = NULL: dG, dc, coef same bits")
+        dx2 = [_nl_dx(xv, ld, dyv, lddy, sp[0][3], lddx) for _ in range(2)]
+        rep.require(torch.equal(dx2[0].view(torch.int32), dx.view(torch.int32)) and torch.equal(dx2[1].view(torch.int32), dx.view(torch.int32)),
+                    "split route: the call's dx bits")
+    return yc, mc, vc, ic
+
+
+@pytest.mark.parametrize("V", R.NL_ROW_V)
+@pytest.mark.parametrize("d,ld", R.NL_ROW_DL, ids=["d60", "d71ld72"])
+def test_norm_linear_row_edges_against_float64(d, ld, V):
+    """Row counts around the 16-row MFMA tile, the 64-row workgroup and 7 / 8 / 9 reduction partials (V = 448, 512, 513), x
+    packed (60) and padded (71 in 72).  V = 1: var == 0 exactly and mean == x[0] bit for bit; y inside its bound, which is what
+    counts there -- inv = 1 / sqrt(eps) amplifies the difference of two differently ordered sums."""
+    inp = R.nl_inputs(V, d)
+    rep = Report("nl rows", f"V={V} d={d}")
+    y, mean, var, inv = _nl_drive(rep, inp, "packed" if ld == d else "padded")
+    if V == 1:
+        rep.require(bool((var == 0).all()) and torch.equal(mean, inp["x"][0]), "V = 1: var == 0, mean == x[0]")
+    rep.finish()
+
+
+@pytest.mark.parametrize("layout", R.NL_LAYOUTS)
+@pytest.mark.parametrize("d", R.NL_COL_D)
+def test_norm_linear_column_edges_against_float64(d, layout):
+    """Every width next to a switch of Q = NT = ceil(d / 16) and of the statistics kernel's 64 / 128 lanes per row, x in all
+    five layouts (NaN around it: an unmasked over-read meets 0 x NaN in the MFMA), V = 193."""
+    rep = Report("nl cols", f"d={d} {layout}")
+    _nl_drive(rep, R.nl_inputs(R.NL_COL_V, d), layout)
+    rep.finish()
+
+
+def _nl_grad_cases():
+    return [pytest.param(d, lddy, k, xl, id=f"d{d}-lddy{lddy}-lddx{k}-{xl}") for d in R.NL_GRAD_D for lddy in R.NL_GRAD_LDDY
+            for k in range(3) for xl in R.NL_GRAD_X]
+
+
+@pytest.mark.parametrize("d,lddy,k,xlayout", _nl_grad_cases())
+def test_norm_linear_gradient_layouts_against_float64(d, lddy, k, xlayout):
+    """dy with row strides 32, 36 and 64 (NaN pads), dx with row strides d, roundup4(d) and roundup4(d) + 4 (the pads keep the
+    sentinel), x padded and one float behind a 16-byte boundary: both ALIGNED instantiations of the dx kernel, left from the
+    side of x and from the side of dx."""
+    rep = Report("nl grads", f"d={d} dy{lddy} dx{R.nl_lddx(d)[k]} {xlayout}")
+    _nl_drive(rep, R.nl_inputs(R.NL_COL_V, d, seed=1), xlayout, lddy=lddy, lddx=R.nl_lddx(d)[k])
+    rep.finish()
+
+
+@pytest.mark.parametrize("d,lddy,k,xlayout", _nl_grad_cases())
+def test_norm_linear_dx_on_a_free_standing_block_against_float64(d, lddy, k, xlayout):
+    """scr_norm_linear_dx on a drawn (not derived) Gi | k0 | k1 whose columns d.. are NaN: neither csrc/anchor_gather.hip (it
+    drops column 71 of its tile) nor csrc/triplane.hip (it reads its span's columns only) relies on those pads being 0, so
+    the kernel must not let them reach a stored column."""
+    inp = R.nl_inputs(R.NL_COL_V, d, seed=2)
+    V, lddx = inp["V"], R.nl_lddx(d)[k]
+    rep = Report("nl dx", f"d={d} dy{lddy} dx{lddx} {xlayout}")
+    coef = R.nl_coef_block(d, lddy + k)
+    _leaf, xv, ld, _off = R.nl_layout(inp["x"].to(DEV), xlayout)
+    dyl = torch.full((V, lddy), float("nan"), device=DEV)
+    dyl[:, :32] = inp["dy"].to(DEV)
+    runs = [_nl_dx(xv, ld, dyl[:, :32], lddy, coef.to(DEV), lddx) for _ in range(2)]
+    for name, e in R.nl_dx_figures(inp["x"], inp["dy"], coef, runs[0][:V, :d].cpu()):
+        rep.within(name + " / bound", e, 1.0)
+    rep.require(_dx_kept(runs[0], V, d), "sentinels kept")
+    rep.require(torch.equal(runs[0].view(torch.int32), runs[1].view(torch.int32)), "same bits twice")
+    rep.finish()
+
+
+@pytest.mark.parametrize("V,d,ld", R.NL_STRIDE_CASES, ids=lambda v: str(v))
+def test_norm_linear_grid_strides_against_float64(V, d, ld):
+    """V = 70 001: the reduction's grid is capped (1024 workgroups of 64 rows) and strides.  V = 140 001: more rows than one
+    round of the forward and dx grids holds (8 workgroups x 256 CUs x 64 rows).  Every element is inside its own bound; the
+    first row of the second round and the last row are shown on their own."""
+    rep = Report("nl stride", f"V={V} d={d}")
+    rows = tuple(r for r in (R.NL_FWD_GRID_ROWS, V - 1) if r < V)
+    _nl_drive(rep, R.nl_inputs(V, d), "packed" if ld == d else "padded", rows=rows)
+    rep.finish()
+
+
+@pytest.mark.parametrize("V,d,ld", R.NL_SLAB_CASES, ids=lambda v: str(v))
+def test_norm_linear_statistics_slabs_against_float64(V, d, ld):
+    """The built-in statistics pass: a last slab of 2047, 2048 and 1 rows, of 15 .. 33 rows (in and out of the eight-fold
+    unrolled row loop for 2 and 4 row groups), 9 and 65 partials (the unrolled loop of the finish kernel and its tail)."""
+    rep = Report("nl slabs", f"V={V} d={d}")
+    _nl_drive(rep, R.nl_inputs(V, d), "packed" if ld == d else "padded", backward=False)
+    rep.finish()
+
+
+@pytest.mark.parametrize("rows", R.NL_COLSTAT_ROWS)
+def test_norm_linear_caller_statistics_against_float64(rows):
+    """col_stats: fp32 roundings of float64 sums over a random partition of the 4099 rows into `rows` sets.  mean / var / inv
+    against the bound of sums rounded to fp32 once (the only fp32 roundings are the caller's), y against its own."""
+    inp = R.nl_inputs(R.NL_COLSTAT_V, 71)
+    rep = Report("nl cstats", f"rows={rows}")
+    _nl_drive(rep, inp, "padded", stats=R.nl_col_stats(inp["x"], rows).to(DEV), backward=False)
+    rep.finish()
+
+
+@pytest.mark.parametrize("path", ["builtin", "col_stats"])
+@pytest.mark.parametrize("eps", R.NL_EPS)
+def test_norm_linear_statistics_regimes_against_float64(eps, path):
+    """One [4099,8] matrix, a column per regime (f64_refs.nl_regime_matrix); the error of every column beside its bound.  The
+    constant column: var == 0 and mean == 3.25 exactly, inv within an ulp of 1 / sqrt(eps).  The column whose first row -- the
+    shift -- lies a thousand deviations off shows what the one-pass formula loses there: E t^2 = 1e6 is rounded to fp32 once
+    per slab before mean^2 is taken off a variance of 245."""
+    x = R.nl_regime_matrix()
+    g = torch.Generator().manual_seed(8)
+    inp = dict(V=x.shape[0], d=8, x=x, G=torch.randn(32, 8, generator=g), c=torch.randn(32, generator=g))
+    rep = Report("nl regime", f"eps={eps:g} {path}")
+    stats = R.nl_col_stats(x, 9).to(DEV) if path == "col_stats" else None
+    _, mean, var, inv = _nl_drive(rep, inp, "packed", eps=eps, stats=stats, backward=False)
+    sb = R.nl_stats_bounds(x, eps, R.NL_STAT_COMBINE)
+    for j, name in enumerate(R.NL_REGIME_COLUMNS):
+        for what, got in (("mean", mean), ("var", var), ("inv", inv)):
+            ref, b = sb[what]
+            rep.within(f"{what} {name}", abs(float(got[j].double() - ref[j])), float(b[j]))
+    k = R.NL_REGIME_COLUMNS.index("constant")
+    want = 1.0 / float(torch.tensor(eps, dtype=torch.float32)) ** 0.5
+    rep.require(float(var[k]) == 0.0 and float(mean[k]) == 3.25, "constant: var == 0, mean == 3.25")
+    rep.within("constant: inv, ulps", abs(float(inv[k].double()) - want) / (2.0 ** -23 * want), 1.0)
+    rep.require(float(mean[6]) != 0 and float(mean[7]) != 0, "single-row columns: mean != 0")
+    rep.finish()
+
+
+@pytest.mark.parametrize("name", [c[0] for c in R.NL_FOLD_CASES])
+def test_norm_fold_kernels_against_float64(name):
+    """scr_norm_fold, scr_norm_fold_backward and scr_norm_running_stats (n = 1 and 2 rows; with and without the batch
+    counters) against float64, per element: (L + 2) u sum |W gamma| for G, (sum d_i + L) u (sum |W beta| + |b|) for c, 3 u
+    of the two products for dW, 34 u of the 32 for the column sums, db == dc, 6 u of the two terms for the running
+    statistics; the counters advance by one."""
+    from splatco_amd import _C
+    p = R.nl_fold_inputs(name)
+    rep = Report("nl fold", name)
+    d, L = p["d"], len(p["widths"])
+    dev = lambda ts: [t.to(DEV) for t in ts]
+    f64 = lambda ts: [t.double() for t in ts]
+    W, b, ga, be = dev(p["W"]), dev(p["b"]), dev(p["gamma"]), dev(p["beta"])
+    wi, ci = _C.host_array(p["widths"]), _C.host_array(p["cols"])
+    at = None if p["col_at"] is None else _C.host_array(p["col_at"], _C.u8)
+    runs = []
+    for _ in range(2):
+        G, c = _sent(32 * d + 4), _sent(36)
+        _C.call("scr_norm_fold", L, d, wi, ci, at, _C.ptr_array(W), _C.ptr_array(b), _C.ptr_array(ga), _C.ptr_array(be), G, c, device=DEV)
+        dW, db = [_sent(32 * w + 4) for w in p["widths"]], [_sent(36) for _ in range(L)]
+        dga, dbe = [_sent(w + 4) for w in p["widths"]], [_sent(w + 4) for w in p["widths"]]
+        _C.call("scr_norm_fold_backward", L, d, wi, ci, at, _C.ptr_array(W), _C.ptr_array(ga), _C.ptr_array(be), p["dG"].to(DEV),
+                p["dc"].to(DEV), _C.ptr_array(dW), _C.ptr_array(db), _C.ptr_array(dga), _C.ptr_array(dbe), device=DEV)
+        runs.append([G, c, *dW, *db, *dga, *dbe])
+    rep.require(_same_bits([t.view(torch.int32) for t in runs[0]], [t.view(torch.int32) for t in runs[1]]), "same bits twice")
+    sizes = [32 * d, 32] + [32 * w for w in p["widths"]] + [32] * L + list(p["widths"]) * 2
+    rep.require(all(_kept(t[n:]) for t, n in zip(runs[0], sizes)), "sentinels kept")
+    G64, c64 = R.nl_fold_f64(f64(p["W"]), f64(p["b"]), f64(p["gamma"]), f64(p["beta"]), p["widths"], p["cols"], d, p["col_at"])
+    bG, bc = R.nl_fold_bounds(p)
+    rep.within("G / bound", R.nl_excess(G[:32 * d].view(32, d), G64, bG), 1.0)
+    rep.within("c / bound", R.nl_excess(c[:32], c64, bc), 1.0)
+    ref = R.nl_fold_backward_f64(p["dG"].double(), p["dc"].double(), f64(p["W"]), f64(p["gamma"]), f64(p["beta"]), p["widths"],
+                                 p["cols"], p["col_at"])
+    for i, (r4, b4) in enumerate(zip(ref, R.nl_fold_backward_bounds(p))):
+        w = p["widths"][i]
+        got = (dW[i][:32 * w].view(32, w), db[i][:32], dga[i][:w], dbe[i][:w])
+        for tag, g_, r_, b_ in zip(("dW", "db", "dgamma", "dbeta"), got, r4, b4):
+            rep.within(f"{tag}[{i}] / bound", R.nl_excess(g_, r_, b_), 1.0)
+    mom = _C.host_array(p["momentum"], _C.f32)
+    for n in (1, 2):
+        for counters in (False, True):
+            rm, rv = [_sent(w + 4) for w in p["widths"]], [_sent(w + 4) for w in p["widths"]]
+            for t, s in zip(rm + rv, p["run_mean"] + p["run_var"]):
+                t[:s.numel()] = s.to(DEV)
+            nb = [torch.full((1,), 41 + i, dtype=torch.int64, device=DEV) for i in range(L)]
+            _C.call("scr_norm_running_stats", L, d, wi, ci, at, mom, _C.ptr_array(rm), _C.ptr_array(rv),
+                    _C.ptr_array(nb) if counters else None, p["mean"].to(DEV), p["var"].to(DEV), n, device=DEV)
+            want = R.nl_running_f64(f64(p["run_mean"]), f64(p["run_var"]), p["momentum"], p["mean"].double(), p["var"].double(), n,
+                                    p["widths"], p["cols"], p["col_at"])
+            e = max(max(R.nl_excess(rm[i][:w], want[i][0], bd[0]), R.nl_excess(rv[i][:w], want[i][1], bd[1]))
+                    for i, (w, bd) in enumerate(zip(p["widths"], R.nl_running_bounds(p, n))))
+            tag = f"n={n}{' counters' if counters else ''}"
+            rep.within(f"running {tag} / bound", e, 1.0)
+            rep.require(all(_kept(t[w:]) for ts in (rm, rv) for t, w in zip(ts, p["widths"]))
+                        and all(int(t) == 41 + i + (1 if counters else 0) for i, t in enumerate(nb)), f"running {tag}: pads, counters")
     rep.finish()
